@@ -17,12 +17,17 @@ strip_kernel<ROLE_YF>, the row-side pass of the fused scoring / cross-entropy: A
 at the mean weighted-row count of the bracketed batches) over the mean launch time measured with HIP events on the launch stream
 inside the timed region; `traffic` = HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/).
 `roofline_attention` does the same for the K3 BiMAU forward launch and its three backward passes (the brackets rotate: one
-kernel id per step), with the PMC pipe utilisation of those kernels beside it.  `cpu_baseline` times the restated reference graph
-(oracle/torch_ref.py, float32, reference op order) on this host's cores at the same batch of 512 on a bounded sample;
-`cpu_baseline_1thread_batch16` is the reference's own single-thread setting.  At N = 1 `extras` adds the secondary rows of SURVEY
-§8(d): masklen 6, all rows weighted, dropout off, multi-hot marks, uniform item ids, the device masker inside the step, the
-published recipe's shape, the config-3 K1 encode line with Zipf and uniform ids (algorithmic and counter-side GB/s) and the
-sharded-eval step.
+kernel id per step), with the PMC pipe utilisation of those kernels beside it.
+
+A plain run sets up, warms up, times the K steps and prints the line; everything below needs `--full`.  `cpu_baseline` times the
+restated reference graph (oracle/torch_ref.py, float32, reference op order) on this host's cores at the same batch of 512 on a
+bounded sample; `cpu_baseline_1thread_batch16` is the reference's own single-thread setting.  At N = 1 `extras` adds the secondary
+rows of SURVEY §8(d): masklen 6, all rows weighted, dropout off, multi-hot marks, uniform item ids, the device masker inside the step,
+the published recipe's shape, the config-3 K1 encode line with Zipf and uniform ids (algorithmic and counter-side GB/s) and the
+sharded-eval step; at N > 1 it holds the sharded-eval and vocab-parallel rows.
+
+`--dump-outputs DIR` writes what the last timed step hands its caller, its loss, as DIR/loss.npy (float32).  The inputs and the
+initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 
     python bench.py --workload recipe            # the published recipe's shape (runme.sh:15-23: 512 units, 8 heads, L = 30, M = 6)
     python bench.py --workload encode [--ids uniform]    # K1 alone at config 3 (HBM roofline)
@@ -288,8 +293,11 @@ def main():
                     help="engine: static launch sequence issued eagerly (dominant kernel bracketed with HIP events); "
                          "graph: the same sequence replayed as one HIP graph; autograd: torch.autograd over the ops")
     ap.add_argument("--op-table", action="store_true", help="after the timed region, print a per-C-call time table to stderr")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary rows (M=6, all rows weighted, dropout off, "
-                                                             "config-3 encode, sharded eval) the default N=1 run appends")
+    ap.add_argument("--full", action="store_true", help="after the headline step, also measure the CPU baselines and the secondary "
+                                                        "rows (`extras`); a plain run times the headline step alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the loss of the last timed step as DIR/loss.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary rows (M=6, all rows weighted, dropout off, "
+                                                             "config-3 encode, sharded eval)")
     ap.add_argument("--ids", default="zipf", choices=["zipf", "uniform"], help="item-id distribution of the synthetic sequences "
                     "(--workload encode; the step workload reports the uniform variant as an extra)")
     ap.add_argument("--workload", default="step", choices=["step", "recipe", "encode", "eval", "tgat", "tisasrec", "ctsma"],
@@ -297,6 +305,8 @@ def main():
                          "(embedding gather + time code) alone at SURVEY §8d config 3 (|items| = 1M, L = 200, d = 256) — the "
                          "HBM-bound regime, reported as GB/s against the HBM roofline")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("step", "recipe"):
+        ap.error("--dump-outputs: only the optimizer-step workloads (--workload step | recipe)")
     if args.workload == "encode":
         return print(json.dumps(encode_bench(args)))
     if args.workload in ("tgat", "tisasrec", "ctsma"):
@@ -344,10 +354,12 @@ def main():
     dt, loss, dom = res["dt"], res["loss"], res["dom"]
     flash_engine = bool(getattr(res.get("engine"), "flash_ce", False))
     sync_loss = getattr(res.get("engine"), "sync_loss", None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss)
     # north_star's other multi-GPU path in the SAME line: the full-catalogue scoring step with the item table row-sharded over the
     # ranks and ONE packed RCCL all-gather of the local top-K.  Every rank takes part (collective); rank 0 reports.
     eval_sharded = vocab_parallel = None
-    if world > 1 and args.workload == "step" and not args.no_extras:
+    if world > 1 and args.workload == "step" and args.full and not args.no_extras:
         res.pop("engine", None)
         torch.cuda.empty_cache()
         eval_sharded = eval_rows(args, dev, world, rank, dist, steps=20, warmup=5, sizes=((20000, 128),))
@@ -478,11 +490,11 @@ def main():
                            "unbiasedness over 1600 masks, finite-difference backward under a fixed mask, stored keep bits == hashed "
                            "masks bit for bit (tests/test_gpu_coding.py, test_gpu_ops.py)",
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(c, budget_s=12.0)      # the GPU workload's own batch of 512
             # the reference's own thread setting (src/main.py:167-168: intra/inter-op parallelism = 1), on a batch of 16
             out["cpu_baseline_1thread_batch16"] = cpu_baseline(c, budget_s=8.0, nthreads=1, bs=16)
-        if world == 1 and not args.no_extras and args.path == "engine":
+        if world == 1 and args.full and not args.no_extras and args.path == "engine":
             out["extras"] = extras(c, args, dev)
         if eval_sharded is not None:
             out["extras"] = {"eval_sharded": eval_sharded, "vocab_parallel_ce": vocab_parallel}
@@ -502,6 +514,15 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, loss):
+    """--dump-outputs: the loss the last timed step returned, as `loss.npy` (float32, shape [1]).  The parameters the optimizer
+    leaves are not an output of the step but the state of the run, and they do not repeat from run to run: the embedding and label
+    scatters add their rows with f32 atomics, whose order varies, and Adam turns the rounding noise in gradients that are zero in
+    exact arithmetic (the key bias of the attention projection) into steps of +-lr, so such parameters drift apart over a run."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
 
 
 BRACKETS = (0, 2, 3)   # EDGL_KERNEL_SCORE_BWD_ROWS, EDGL_KERNEL_BIMAU_FWD, EDGL_KERNEL_BIMAU_BWD_ALL (include/easydgl_hip.h)

@@ -131,6 +131,18 @@ def test_bench_flop_model_matches_the_survey_numbers():
     assert abs(3 * f20 * 512 / 1e9 - 276.3) < 0.5
 
 
+def test_bench_dump_outputs_writes_the_returned_loss(tmp_path):
+    """bench.py --dump-outputs: the loss the last timed step returned, as DIR/loss.npy in float32 (the directory is created)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.dump_outputs(str(tmp_path / "out"), torch.tensor(3.25, dtype=torch.float64))
+    assert os.listdir(tmp_path / "out") == ["loss.npy"]
+    got = np.load(tmp_path / "out" / "loss.npy")
+    assert got.dtype == np.float32 and got.tolist() == [3.25]
+
+
 def test_key_mask_forms_accepted_by_the_attention_units():
     """BiMAU / MAU keep the reference's positional signature, whose `masks` is the [h*B, T, T] float key mask
     (EasyDGL.py:94-95); the kernels take a [B, T] int64 vector.  The module reduces the reference forms and rejects anything else."""

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 timeout 1500 python -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1
 echo "gpu tests rc=$?"; tail -3 "$OUT/gpu_tests.log"
-python bench.py > "$OUT/bench_default.log" 2>&1
+python bench.py --full > "$OUT/bench_default.log" 2>&1
 grep -h '"metric"' "$OUT/bench_default.log" | tail -1 > "$OUT/r06_bench_line.json"
 cut -c1-300 "$OUT/r06_bench_line.json"
 bash tools/refresh_profiles.sh > "$OUT/refresh.log" 2>&1
