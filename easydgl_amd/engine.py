@@ -13,6 +13,7 @@ weights against the autograd path and the fp64 oracle.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Dict, Optional
 
@@ -26,12 +27,39 @@ EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_MUL_DGELU, EPI_ACCUM, EPI_OUT_F32 = 1, 2, 
 
 
 class TrainEngine:
+    """One optimizer step of an EasyDGL model at a fixed batch shape: step() / load_batch() / bind_batch() / join_loss().
+
+    Environment switches.  Each is the reference leg of a parity test (tests/test_gpu_engine.py, test_gpu_tpp_fused.py,
+    test_gpu_bimau_skip.py, test_train_driver.py).  All are read ONCE, when the engine is constructed, and kept as `sw_*`
+    attributes: set them before building the engine — a change afterwards has no effect on it.  (EDGL_DEFER_LOSS and
+    EDGL_PREP_IN_ENCODER used to be looked up at every step.)
+
+        EDGL_FLASH_CE=0          scoring as two passes (LSE forward, gradient backward) instead of the one-sweep "flash" form;
+                                 the constructor argument `flash_ce` overrides it
+        EDGL_TPP_FUSED=0         the TPP regulariser as launches of its own instead of inside the attention kernels
+        EDGL_PREP_IN_ENCODER=0   batch preparation (row compaction, regulariser slots) on the second side stream instead of the
+                                 first workgroups of the encoder's launch
+        EDGL_BIMAU_ORDER=1       attention jobs launched by falling key-tile count (edgl_bimau_job_order)
+        EDGL_CE_PARTS=0          the loss launch sweeps the rows' lse / label logits instead of adding per-workgroup sums
+        EDGL_DEFER_LOSS=0        with sync_loss False the loss launches still run at the end of their own step's backward, not at
+                                 the start of the next step
+        EDGL_ADAM_EX=0           plain optimizer launch + slab reduction + step-counter launch instead of edgl_adam_apply_ex
+
+    EDGL_SCORE_STRIP belongs to the library (csrc/k_score_strip.hip latches it once per process); the engine reads it at the same
+    place because only the strip passes leave the one-hot term of the table gradient to the embedding scatter (`_label_fused`)."""
     _SIDE_STREAMS = {}
 
     def __init__(self, model, batch: int, use_graph: bool = True, process_group=None, fused_tail=None, flash_ce=None):
-        if use_graph and os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") == "1":
-            raise _lib.EdglError("TrainEngine: EDGL_ENGINE_LEGACY_FORK=1 is an A/B switch of the eager path (the captured sequence "
-                                 "relies on the step counters being advanced behind the optimizer)")
+        # the environment switches (class docstring): read here, once, and nowhere else in the engine
+        env = os.environ.get
+        self.sw_flash_ce = env("EDGL_FLASH_CE", "1") != "0"
+        self.sw_tpp_fused = env("EDGL_TPP_FUSED", "1") != "0"
+        self.sw_prep_in_encoder = env("EDGL_PREP_IN_ENCODER", "1") != "0"
+        self.sw_bimau_order = env("EDGL_BIMAU_ORDER", "0") == "1"
+        self.sw_ce_parts = env("EDGL_CE_PARTS", "1") != "0"
+        self.sw_defer_loss = env("EDGL_DEFER_LOSS", "1") != "0"
+        self.sw_adam_ex = env("EDGL_ADAM_EX", "1") != "0"
+        self.sw_score_strip = env("EDGL_SCORE_STRIP", "1") != "0"      # (the library's: csrc/k_score_strip.hip latches it per process)
         self.m = model
         self.B = batch
         self.use_graph = use_graph
@@ -44,9 +72,9 @@ class TrainEngine:
         self.code = ops._DT[self.dt]
         B, T, C, H, E, M, I = batch, m.seqslen, m.num_units, m.num_heads, m.num_events, m.masklen, m.num_items
         self.T, self.C, self.H, self.E, self.M, self.I = T, C, H, E, M, I
-        self.pad = tuple(getattr(m, "pad", (0, 0)))             # (dh_pad, dh_true) of a channel-padded model (model/easydgl.py)
+        self.pad = tuple(m.pad)             # (dh_pad, dh_true) of a channel-padded model (model/easydgl.py)
         self.c_true = int(m.width_true) if self.pad[0] else 0
-        self.qk_scale = float(getattr(m, "qk_scale", 0.0))      # 0: 1 / sqrt(head dim); a channel-padded model passes 1 / sqrt(true head dim)
+        self.qk_scale = float(m.qk_scale)      # 0: 1 / sqrt(head dim); a channel-padded model passes 1 / sqrt(true head dim)
         # More mark types than one attention launch takes (16; EasyDGL.py:45-46: E is the width of the data set's mark.pkl): the
         # marks run as groups, as in module/temporal.py modulated_attention — G = sum_e marks.lambda_e is a sum over marks, the
         # output (G * P) V is linear in G and lambda_e reads only its own dh columns of the intensity MLP.  One attention launch
@@ -62,9 +90,9 @@ class TrainEngine:
         # TPP regulariser inside the attention kernels (csrc/bimau_common.h TppDesc): the forward forms the two loss sums from the
         # lambda rows it holds in registers, sweep 1 recomputes d lambda — no [H*B, T, E] d lambda array, no TPP launch between the
         # attention forward and the block tail (the loss kernel needs the term at the end of the backward only: flash_ce form)
-        fce = (os.environ.get("EDGL_FLASH_CE", "1") != "0") if flash_ce is None else bool(flash_ce)
+        self.flash_ce = self.sw_flash_ce if flash_ce is None else bool(flash_ce)
         self.fused_tpp = (self.code == _lib.BF16 and C // H == 16 and E == 16 and not self.mgroups and M <= 256 and T <= 128
-                          and m.ct_reg != 0.0 and fce and nb > 0 and os.environ.get("EDGL_TPP_FUSED", "1") != "0")
+                          and m.ct_reg != 0.0 and self.flash_ce and nb > 0 and self.sw_tpp_fused)
         e = lambda *s, dtype=None: torch.empty(s, device=dev, dtype=dtype or self.dt)  # noqa: E731
         f32 = torch.float32
         # ---- static inputs ----------------------------------------------------------------------------------
@@ -89,7 +117,7 @@ class TrainEngine:
             # stored keep bits of the attention dropout: hashed once per step on the side stream, read by the forward and both
             # backward sweeps (csrc/bimau_common.h; 0 bytes = no stored-bits form at this T)
             nb_bits = int(lib.edgl_bimau_dropbits_bytes(B, T, H)) if m.attention_probs_dropout_rate > 0 else 0
-            d["dbits"] = e(nb_bits // 4, dtype=torch.int32) if nb_bits > 0 and os.environ.get("EDGL_DROPBITS", "1") != "0" and os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") != "1" else None
+            d["dbits"] = e(nb_bits // 4, dtype=torch.int32) if nb_bits > 0 else None
             if self.mgroups:
                 dh = C // H
                 d["grp"] = []
@@ -109,7 +137,7 @@ class TrainEngine:
         # padding only (0.4 % at the headline shape: DESIGN.md rule 50) — nothing to skip, nothing to balance.  Evaluation batches
         # (mask_last) keep their left padding: there the skip is real.
         self.job_order = (torch.arange(2 * B, device=dev, dtype=torch.int32)     # (order | the launches' scratch)
-                          if (not self.mgroups and B <= 16384 and nb > 0 and os.environ.get("EDGL_BIMAU_ORDER", "0") == "1") else None)
+                          if (not self.mgroups and B <= 16384 and nb > 0 and self.sw_bimau_order) else None)
         self.tpp_desc = torch.zeros(int(lib.edgl_tpp_prep_bytes(B, T, M)), device=dev, dtype=torch.uint8) if self.fused_tpp else None
         self.zero_resid = torch.zeros((B, T, C), device=dev, dtype=self.dt) if self.mgroups else None
         self.pre_t, self.so, self.st3 = e(B, T, C), e(B, T, C), e(B, 2, dtype=f32)
@@ -118,16 +146,14 @@ class TrainEngine:
         # beyond what the BiMAU kernels take (T <= 208), checked here so that a future relaxation fails at construction)
         if m.ct_reg != 0.0 and (M > 256 or T > 1024):
             raise _lib.EdglError(f"TrainEngine: masklen {M} > 256 or T {T} > 1024 exceeds the fused TPP kernel (edgl_tpp_fwd_bwd_ex)")
-        # (channel-padded models: the _ct forms take the LayerNorms' moments over the real channels; EDGL_FUSED_TAIL_PAD=0: unfused)
-        ok = bool(lib.edgl_tail_supported(T, C, self.code)) and M <= 256 and os.environ.get("EDGL_FUSED_TAIL", "1") != "0" \
-            and (not self.pad[0] or os.environ.get("EDGL_FUSED_TAIL_PAD", "1") != "0")
+        # (channel-padded models: the _ct forms take the LayerNorms' moments over the real channels)
+        ok = bool(lib.edgl_tail_supported(T, C, self.code)) and M <= 256
         self.fused_tail = ok if fused_tail is None else (bool(fused_tail) and ok)
         self.tail_pack = [e(int(lib.edgl_tail_pack_elems(C))) for _ in range(nb)] if self.fused_tail else []
         if self.fused_tail:   # outputs of the fused backward: the gradients w.r.t. the four dense outputs (operands of the dW GEMMs)
             self.d_pre_t, self.d_o, self.d_pre_f, self.d_ao = e(B, T, C), e(B, T, C), e(B, T, 2 * C), e(B, T, C)
         # "flash" scoring: the forward LSE pass also accumulates the row gradients (edgl_score_flash_fwd / _bwd); its
         # workspace carries the slabs from the forward to the backward and is therefore private
-        self.flash_ce = (os.environ.get("EDGL_FLASH_CE", "1") != "0") if flash_ce is None else bool(flash_ce)
         self.ws_flash = e(int(lib.edgl_score_flash_workspace(self.R, C, I, I, self.code)), dtype=f32) if self.flash_ce else None
         self.hrows, self.hrows_c = e(self.R, C), e(self.R, C)
         self.hrows_c.zero_()   # rows behind the weighted ones are never written on the fused path (and never read as data)
@@ -137,7 +163,7 @@ class TrainEngine:
         self.lse, self.lab_logit, self.coef = e(self.R, dtype=f32), e(self.R, dtype=f32), e(self.R, dtype=f32)
         self.loss = e(1, dtype=f32)
         # per-workgroup sums of the loss numerator, left by the one-launch row finish of the scoring forward (0: this width has none)
-        self.ce_nparts = int(lib.edgl_score_ce_nparts(self.R, C)) if (self.flash_ce and os.environ.get("EDGL_CE_PARTS", "1") != "0") else 0
+        self.ce_nparts = int(lib.edgl_score_ce_nparts(self.R, C)) if (self.flash_ce and self.sw_ce_parts) else 0
         self.ce_part = torch.zeros(self.ce_nparts + 1, device=dev, dtype=f32) if self.ce_nparts > 0 else None   # (+ the row count)
         # L2 + TPP terms (accumulated before the cross-entropy kernel, which adds them to its own term)
         self.loss_aux, self.loss_tpp = torch.zeros(1, device=dev, dtype=f32), torch.zeros(1, device=dev, dtype=f32)
@@ -150,7 +176,7 @@ class TrainEngine:
         # step, checkpoint, an autograd-path step) the term is recomputed from the arena.
         self.l2_nparts = int(lib.edgl_adam_l2_parts(m._arena.numel()))
         self.l2_parts = [torch.zeros(self.l2_nparts, device=dev, dtype=f32) for _ in range(2)] \
-            if (m.l2_reg != 0.0 and not use_graph and os.environ.get("EDGL_L2_PARTS", "1") != "0") else None
+            if (m.l2_reg != 0.0 and not use_graph) else None
         self._l2p_cur, self._l2p_ready = 0, False
         # two side streams per DEVICE, shared by every engine of the process: the runtime multiplexes streams onto a handful of
         # hardware queues, and a process that builds engine after engine (bench.py's extra rows) otherwise ends up with its main
@@ -167,33 +193,25 @@ class TrainEngine:
         self.loss_sum = torch.zeros(1, device=dev, dtype=torch.float64)
         self._pending_label = None
         self._lazy_loss, self._side_has_grads, self._loss_unjoined = False, False, False
-        # weight-gradient GEMMs beside the kernels that do not need them (bit 0: the block tail's four products under the attention
-        # backward; bit 1: the QKVT product beside the dX GEMM / embedding backward): _issue_backward
-        self.dw_overlap = int(os.environ.get("EDGL_DW_OVERLAP", "0"))
+        self._label_fused = False      # the one-hot term of the table gradient rides in the embedding scatter's launch (_issue_backward)
         # training batches of the reference's masker leave no key tile of pure padding (MASK tokens sit on padded positions: rule 50),
-        # so the engine launches the BiMAU kernels that walk every tile (identical results; EDGL_ENGINE_SKIP=1: the skipping ones)
-        # A/B switch: the table-gradient pass adds its row chunks into the zero-filled gradient with f32 atomics (no slabs, no
-        # slab_reduce launch between the scoring and the block-tail backward)
-        self.score_atomic = (os.environ.get("EDGL_SCORE_ATOMIC", "0") == "1" and self.code == _lib.BF16 and self.C == 128
-                             and os.environ.get("EDGL_SCORE_STRIP", "1") != "0" and bool(self.blk))
-        self.mau_flags = 0 if os.environ.get("EDGL_ENGINE_SKIP", "0") == "1" else _lib.MAU_NO_SKIP
+        # so the engine launches the BiMAU kernels that walk every tile (identical results; the skipping ones measured +- 0 to +3 us)
+        self.mau_flags = _lib.MAU_NO_SKIP
         # The optimizer launch of the eager step (edgl_adam_apply_ex): (a) it sums the row-chunk slabs of the tied table's / output bias's
         # scoring gradient itself — no slab_reduce launch between the scoring and the block-tail backward (the embedding scatter adds
         # into the gradient zero-filled under the encoder) —, (b) it writes the NEXT step's counters into a second pair of buffers that
         # the host swaps in behind it — no single-thread step_begin launch at the end of the step's chain.  step() only (a bare
         # _issue() leaves complete gradients in the arena), single process only (the all-reduce wants complete gradients), never with a
         # captured graph on the model (a graph bakes the counters' addresses in).  EDGL_ADAM_EX=0: the round-5 launches.
-        self.adam_ex = (not use_graph) and os.environ.get("EDGL_ADAM_EX", "1") != "0" and os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") != "1" \
-            and os.environ.get("EDGL_ADAM_NEXT", "0") != "1"
+        self.adam_ex = (not use_graph) and self.sw_adam_ex
         self._rng_alt, self._adam_alt = torch.zeros_like(m._rng_state), torch.zeros_like(m._adam_state)
         self._slabs = None          # (table slabs ptr, bias slabs ptr, nslab) left by the scoring backward of the current step
         self._slab_info = None
         if self.adam_ex and self.flash_ce:
-            import ctypes
             info = (ctypes.c_long * 4)()
             check(lib.edgl_score_flash_slab_info(self.R, C, I, I, self.code, info), "edgl_score_flash_slab_info")
             self._slab_info = (int(info[0]), int(info[1]), int(info[2]))
-        self._dw_forked = False
+        self._ar_events = None     # bench.py: a list that collects HIP event pairs around the data-parallel step's one collective
         self.sync_loss = True      # step(): order the returned loss on the caller's stream (a cross-stream wait behind the optimizer)
         # sync_loss False, the loss launches reading nothing of the batch (ce_part): they are not launched at the end of the backward
         # — the fork for them is an event record behind a kernel of the main stream, 6-8 us of idle — but by the NEXT step on the
@@ -285,50 +303,82 @@ class TrainEngine:
         m, st = self.m, _stream()
         self._lazy_loss = bool(lazy_loss) and bool(self.blk)
         # (fold_slabs: step() lets the optimizer launch sum the scoring gradient's slabs — see __init__)
-        self._fold = bool(fold_slabs) and self._slab_info is not None and bool(self.blk) and not self.score_atomic and not self._dp
+        self._fold = bool(fold_slabs) and self._slab_info is not None and bool(self.blk) and not self._dp
         self._slabs = None
         if not self._fold:
             m._table_grad_zero = None      # (this issue's slab reduction ASSIGNS the table / bias gradient)
-        B, T, C, H, E, M, I, R = self.B, self.T, self.C, self.H, self.E, self.M, self.I, self.R
-        code = self.code
-        hd, ad = m.hidden_dropout_rate, m.attention_probs_dropout_rate
         drop = lambda rate, sid: ops.Drop(rate, m._rng_state, sid) if rate > 0 else ops.NO_DROP  # noqa: E731
         tab = m.item_embs.lookup_table
         tab_c = m.compute(tab)
+        # the sums of squares the last optimizer launch of THIS engine left are the L2 term's input iff nobody touched the state since
+        # (ownership on the MODEL: another engine of the same model, load_tf_variables / _load_padded / a checkpoint — anything that
+        #  rewrites the arena goes through sync_shadow / settle_state or another engine's _optimizer and takes the token away)
+        l2_from_parts = self.l2_parts is not None and self._l2p_ready and m._state_ahead and m._l2_parts_owner == id(self)
         # dropout step counter, Adam step counter and learning rate of this step (one single-thread launch): normally already in
         # place — _optimizer advances them for the NEXT step behind its last kernel, so that the fork below costs the main stream
         # nothing (an event record behind a kernel idles the stream ~6-13 us before its next launch) while the side stream can hash
         # the keep bits of the attention dropout from the advanced counter.  First step, or an _issue() without _optimizer: here.
-        legacy = os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") == "1"   # A/B switch: round-3 order (one side stream, fork first)
-        # the sums of squares the last optimizer launch of THIS engine left are the L2 term's input iff nobody touched the state since
-        # (ownership on the MODEL: another engine of the same model, load_tf_variables / _load_padded / a checkpoint — anything that
-        #  rewrites the arena goes through sync_shadow / settle_state or another engine's _optimizer and takes the token away)
-        l2_from_parts = self.l2_parts is not None and self._l2p_ready and getattr(m, "_state_ahead", False) and not legacy \
-            and getattr(m, "_l2_parts_owner", None) == id(self)
-        if not legacy:
-            if not getattr(m, "_state_ahead", False):
-                self._advance_state(st)
-            m._state_ahead = False
-        # ---- side streams: launches that depend on the weights / labels / the step counter only start with the step and run
-        # under the encoder / QKVT projection: few-microsecond kernels that would otherwise sit in the critical path, each behind
-        # a full launch.  (Small kernels next to the one-workgroup-per-CU kernels — block tail, scoring — is what NOT to do: the
-        # fat workgroups cannot be placed while small ones hold registers of a CU; measured 84 -> 247 us.)
-        # The first attention kernel waits for this chain, and a cross-stream edge takes ~12 us to arrive: everything it needs
-        # must be through ~25 us before the QKVT projection ends (timeline of round 4: the chain ended 10 us AFTER it and the
-        # main stream idled 22 us).  Hence: the row-compaction scan — one 1024-thread workgroup, ~24 us — on a stream of its own,
-        # the chain itself without the memset of the normaliser, the L2 term BEHIND the event (its consumer, the loss kernel,
-        # runs on this same side stream at the end of the backward).
-        main, side, side2 = torch.cuda.current_stream(), self.side, self.side2
-        if legacy:
-            side2 = side
+        if not m._state_ahead:
+            self._advance_state(st)
+        m._state_ahead = False
+        main = torch.cuda.current_stream()
+        ev_pack = self._issue_side_chain(main, l2_from_parts)
+        self._issue_forward(main, ev_pack, drop, tab_c, st)
+        lab = self.labels_c
+        self._issue_scoring_fwd(tab_c, lab, st)
+        # ================= backward =================
+        self._ws_i = 0
+        check(lib.edgl_reduce_defer(1, st), "edgl_reduce_defer")
+        try:
+            self._issue_backward(st, drop, tab, tab_c, lab)
+        except BaseException:
+            # never leave the thread in deferred mode: later ops would queue reductions that nobody flushes
+            lib.edgl_reduce_defer(-1, st)
+            lib.edgl_gemm_dw_defer(-1, st)
+            self._pending_loss = None
+            self._pending_label = None
+            raise
+        check(lib.edgl_reduce_defer(0, st), "edgl_reduce_defer")   # runs the remaining queued reductions in one launch
+        if self._pending_loss is not None:   # (no block: no side-stream join in the backward)
+            self._pending_loss(st)
+            self._pending_loss = None
+            if self.accumulate_loss:         # (the loss launch of a model without blocks runs on the main stream)
+                self.loss_sum.add_(self.loss)
+        if self._lazy_loss and not self._side_has_grads:
+            self._loss_unjoined = True       # (step() joins behind the optimizer, or the caller does: join_loss())
+        else:
+            torch.cuda.current_stream().wait_stream(self.side)
+            self._loss_unjoined = False
+
+    def _l2_term(self, from_parts, sst):
+        m = self.m
+        if m.l2_reg != 0.0 and from_parts:
+            check(lib.edgl_l2_from_parts(_ptr(self.l2_parts[self._l2p_cur]), self.l2_nparts, float(m.l2_reg), _ptr(self.loss_aux), 0,
+                                         sst), "edgl_l2_from_parts")
+        elif m.l2_reg != 0.0:
+            check(lib.edgl_l2_loss(_ptr(m._arena), _ptr(self.l2_seg), self.nseg, float(m.l2_reg), _ptr(self.loss_aux), 0,
+                                   _ptr(self.ws_l2), sst), "edgl_l2_loss")
+
+    def _issue_side_chain(self, main, l2_from_parts):
+        """Side streams: launches that depend on the weights / labels / the step counter only start with the step and run
+        under the encoder / QKVT projection: few-microsecond kernels that would otherwise sit in the critical path, each behind
+        a full launch.  (Small kernels next to the one-workgroup-per-CU kernels — block tail, scoring — is what NOT to do: the
+        fat workgroups cannot be placed while small ones hold registers of a CU; measured 84 -> 247 us.)
+        The first attention kernel waits for this chain, and a cross-stream edge takes ~12 us to arrive: everything it needs
+        must be through ~25 us before the QKVT projection ends (timeline of round 4: the chain ended 10 us AFTER it and the
+        main stream idled 22 us).  Hence the chain without the memset of the normaliser.  Returns the event at its end."""
+        m = self.m
+        B, T, C, H, E, M, R = self.B, self.T, self.C, self.H, self.E, self.M, self.R
+        code, ad = self.code, m.attention_probs_dropout_rate
+        side, side2 = self.side, self.side2
         sst = side.cuda_stream
-        if getattr(self, "_loss_unjoined", False) and self.ce_part is None:
+        if self._loss_unjoined and self.ce_part is None:
             # the previous step left its loss kernel (the form that sweeps lse / label logits / compacted labels) unjoined on the side
             # stream, and this step's first launch rewrites the compacted labels and the row count on the main stream
             main.wait_stream(side)
             self._loss_unjoined = False
         side.wait_stream(main)
-        if self._deferred_loss is not None and not legacy:
+        if self._deferred_loss is not None:
             # the previous step's loss launches are still to come (behind ev_pack below): this step writes the other copy of their input
             a = self._alt
             self.ce_part, a["ce_part"] = a["ce_part"], self.ce_part
@@ -336,20 +386,14 @@ class TrainEngine:
             self.tpp_desc, a["tpp_desc"] = a["tpp_desc"], self.tpp_desc
             for j, bj in enumerate(self.blk):
                 bj["tpp_part"], a["tpp_part"][j] = a["tpp_part"][j], bj["tpp_part"]
-        # The batch preparation (row compaction map, slot data of the regulariser) as the first workgroups of the encoder's launch:
-        # on a second side stream its join sat in the chain the first attention kernel waits for — a wait costs the waiting stream
-        # ~6 us wherever its event stands (measured without it: -5 us of the step)
-        prep_enc = not legacy and os.environ.get("EDGL_PREP_IN_ENCODER", "1") != "0"
-        if not legacy:
-            if not prep_enc:
-                side2.wait_stream(main)
-                if getattr(self, "_loss_unjoined", False):
-                    side2.wait_stream(side)     # the previous steps' loss kernels (side) read buffers that this stream's first kernels rewrite
-        else:
-            if not getattr(m, "_state_ahead", False):
-                self._advance_state(st)
-            m._state_ahead = False
-        if not prep_enc:
+        # The batch preparation (row compaction map, slot data of the regulariser) runs as the first workgroups of the encoder's
+        # launch (_issue_forward): on a second side stream its join sat in the chain the first attention kernel waits for — a wait
+        # costs the waiting stream ~6 us wherever its event stands (measured without it: -5 us of the step).
+        # EDGL_PREP_IN_ENCODER=0: the second side stream.
+        if not self.sw_prep_in_encoder:
+            side2.wait_stream(main)
+            if self._loss_unjoined:
+                side2.wait_stream(side)     # the previous steps' loss kernels (side) read buffers that this stream's first kernels rewrite
             with torch.cuda.stream(side2):
                 # needed by the scoring: row compaction map (labels only).  Its one 1024-thread workgroup needs a whole CU's worth of
                 # free wave slots, which it gets beside the small encoder kernel but not once the QKVT projection fills the chip
@@ -362,37 +406,27 @@ class TrainEngine:
                     # _global_counts is used instead).  Behind the scan: this stream is joined in front of the first attention kernel.
                     check(lib.edgl_tpp_prep(_ptr(self.mpos), _ptr(self.labels), _ptr(self.ts), _ptr(m.mark_lookup_table), B, T, E, M,
                                             _ptr(self.tpp_desc), side2.cuda_stream), "edgl_tpp_prep")
-
-        def l2_term():
-            if m.l2_reg != 0.0 and l2_from_parts:
-                check(lib.edgl_l2_from_parts(_ptr(self.l2_parts[self._l2p_cur]), self.l2_nparts, float(m.l2_reg), _ptr(self.loss_aux), 0,
-                                             sst), "edgl_l2_from_parts")
-            elif m.l2_reg != 0.0:
-                check(lib.edgl_l2_loss(_ptr(m._arena), _ptr(self.l2_seg), self.nseg, float(m.l2_reg), _ptr(self.loss_aux), 0,
-                                       _ptr(self.ws_l2), sst), "edgl_l2_loss")
-
-        # The fused TPP form has no normaliser launch in this chain (edgl_tpp_prep on the other side stream leaves per-sample counts)
-        split = self.fused_tpp and not legacy
         with torch.cuda.stream(side):
             # needed by the first BiMAU forward (the one join of the forward): TPP normaliser (labels only), weight packs, keep bits
-            def late(i, blk, b):
-                if m.ct_reg != 0.0 and not self._dp and not split:    # (data parallel: _global_counts put the all-reduced count there)
-                    check(lib.edgl_tpp_norm(_ptr(self.labels), _ptr(m.mark_lookup_table), B, M, E, _ptr(b["tpp"]), sst),
-                          "edgl_tpp_norm")
-                if self.fused_tail:
-                    check(lib.edgl_tail_pack(_ptr(m.compute(blk.att_out.kernel)), _ptr(m.compute(blk.inter.kernel)),
-                                             _ptr(m.compute(blk.out.kernel)), _ptr(m.compute(m.transform.kernel)), C,
-                                             _ptr(self.tail_pack[i]), sst), "edgl_tail_pack")
             # (fold: the optimizer launch of the previous step left the two gradients at zero behind its reads — a zero-fill only
             #  when somebody else wrote them since: first step, a bare _issue(), an autograd-path step)
-            if self.score_atomic or (self._fold and getattr(m, "_table_grad_zero", None) != id(self)):
+            if self._fold and m._table_grad_zero != id(self):
+                tab = m.item_embs.lookup_table
                 tab.grad.zero_()      # (behind the previous step's optimizer: this stream waited for the main stream above)
                 m.output_bias.grad.zero_()
             if self.job_order is not None:   # ids only: under the encoder, in front of everything the first attention kernel waits for
                 check(lib.edgl_bimau_job_order(_ptr(self.ids), B, T, _ptr(self.job_order), sst), "edgl_bimau_job_order")
             for i, (blk, b) in enumerate(zip(m.layers, self.blk)):
                 att = blk.attention
-                late(i, blk, b)
+                # (the fused TPP form has no normaliser launch in this chain: the batch preparation leaves per-sample counts;
+                #  data parallel: _global_counts put the all-reduced count there)
+                if m.ct_reg != 0.0 and not self._dp and not self.fused_tpp:
+                    check(lib.edgl_tpp_norm(_ptr(self.labels), _ptr(m.mark_lookup_table), B, M, E, _ptr(b["tpp"]), sst),
+                          "edgl_tpp_norm")
+                if self.fused_tail:
+                    check(lib.edgl_tail_pack(_ptr(m.compute(blk.att_out.kernel)), _ptr(m.compute(blk.inter.kernel)),
+                                             _ptr(m.compute(blk.out.kernel)), _ptr(m.compute(m.transform.kernel)), C,
+                                             _ptr(self.tail_pack[i]), sst), "edgl_tail_pack")
                 if self.mgroups:
                     dh = C // H
                     for (e0, e1), gb in zip(self.mgroups, b["grp"]):
@@ -402,32 +436,40 @@ class TrainEngine:
                 else:
                     check(lib.edgl_bimau_pack(_ptr(att.st_kernel), _ptr(att.st_bias), _ptr(att.weight), _ptr(att.scaling), C, H, E,
                                               _ptr(b["pack"]), code, sst), "edgl_bimau_pack")
-                if b["dbits"] is not None and not legacy:
+                if b["dbits"] is not None:
                     check(lib.edgl_bimau_dropbits(B, T, H, float(ad), _ptr(m._rng_state), 10 + 4 * i, _ptr(b["dbits"]), sst),
                           "edgl_bimau_dropbits")
             # The L2 term reads the parameter arena, which the optimizer at the END of this step rewrites on the main stream — and in
             # the lazy-loss mode nothing joins the side stream in front of the optimizer any more.  In FRONT of the event the first
-            # attention kernel waits for, the term is ordered before everything the main stream does from there on (round 4 had it
-            # behind the event, when the chain still ended after the QKVT projection; since the batch preparation moved into the
-            # encoder's launch the chain has ~17 us of slack: rule 49).  EDGL_L2_EARLY=0: behind the event (the A/B switch).
-            l2_early = os.environ.get("EDGL_L2_EARLY", "1") != "0" and not l2_from_parts     # (from the optimizer's sums: no arena read, behind the event)
-            if not self.blk or legacy or l2_early:
-                l2_term()      # (no block: the loss kernel runs on the main stream behind this one event)
-            if not legacy and not prep_enc:
+            # attention kernel waits for, the term is ordered before everything the main stream does from there on (since the batch
+            # preparation moved into the encoder's launch the chain has ~17 us of slack: rule 49; behind the event measured +2.6 us).
+            # From the optimizer's sums there is no arena read: behind the event, where nothing of this step waits for it (its
+            # consumer, the loss kernel, runs on this same stream) — unless there is no block and the loss kernel runs on the main
+            # stream behind this one event.
+            l2_behind = l2_from_parts and bool(self.blk)
+            if not l2_behind:
+                self._l2_term(l2_from_parts, sst)
+            if not self.sw_prep_in_encoder:
                 side.wait_stream(side2)
             ev_pack = side.record_event()
-            if self._deferred_loss is not None and not legacy:
+            if self._deferred_loss is not None:
                 # the previous step's loss: behind the event (nothing of this step waits for it), in front of this step's L2 term
                 self._deferred_loss(sst)
                 self._deferred_loss = None
-            # L2 term: not needed before the loss kernel at the end of the backward (same stream)
             # (the transposed table image is NOT prepared here, although it depends on the weights only: written 200 us before
             # its use it has left the L2 by then and the scoring pass measured 109 -> 118 us — edgl_score_prepare_table)
-            if self.blk and not legacy and not l2_early:
-                l2_term()
-        # ================= forward (EasyDGL.py:70-151) =================
+            if l2_behind:
+                self._l2_term(l2_from_parts, sst)
+        return ev_pack
+
+    def _issue_forward(self, main, ev_pack, drop, tab_c, st):
+        """Forward (EasyDGL.py:70-151): encoder, blocks, head, the weighted head rows compacted into `hrows_c`."""
+        m = self.m
+        B, T, C, H, E, M, I, R = self.B, self.T, self.C, self.H, self.E, self.M, self.I, self.R
+        code = self.code
+        hd, ad = m.hidden_dropout_rate, m.attention_probs_dropout_rate
         d0 = drop(hd, 1)
-        if prep_enc:
+        if self.sw_prep_in_encoder:
             check(lib.edgl_encode_fwd_prep(_ptr(self.ids), _ptr(self.ts), _ptr(tab_c), _ptr(m.pcoding.pembs.lookup_table),
                                            _ptr(m.mark_embs.lookup_table), _ptr(m.mark_lookup_table), _ptr(m.tcoding.scale), B, T, C,
                                            E, I, int(m.mask), float(m.time_scale), float(d0.rate), d0.ptr(), d0.stream_id,
@@ -489,7 +531,12 @@ class TrainEngine:
         if not (self.fused_tail and self.blk):   # the fused tail writes its head rows compacted (row map = inv)
             check(lib.edgl_compact_gather(_ptr(self.hrows), _ptr(self.labels), _ptr(self.perm), R, C, _ptr(self.hrows_c),
                                           _ptr(self.labels_c), code, st), "edgl_compact_gather")
-        lab = self.labels_c
+
+    def _issue_scoring_fwd(self, tab_c, lab, st):
+        """Scoring forward over the compacted rows, and the loss launch that goes with it: `_pending_loss` (flash form: launched
+        by the backward on the side stream, or by the next step) or inline on the main stream (two-pass form)."""
+        m = self.m
+        C, I, R, code = self.C, self.I, self.R, self.code
         aux = _ptr(self.loss_aux) if m.l2_reg != 0.0 else None
         tpp = _ptr(self.loss_tpp) if (m.ct_reg != 0.0 and self.blk) else None
         if self.flash_ce:
@@ -519,32 +566,6 @@ class TrainEngine:
                                              aux, tpp, self.counts.data_ptr() if self._dp else None, st), "edgl_ce_loss_fwd_add")
             if self.accumulate_loss:     # (two-pass form: the loss is written inline, on the main stream)
                 self.loss_sum.add_(self.loss)
-        # ================= backward =================
-        self._ws_i = 0
-        check(lib.edgl_reduce_defer(1, st), "edgl_reduce_defer")
-        try:
-            self._issue_backward(st, drop, tab, tab_c, lab)
-        except BaseException:
-            # never leave the thread in deferred mode: later ops would queue reductions that nobody flushes
-            lib.edgl_reduce_defer(-1, st)
-            lib.edgl_gemm_dw_defer(-1, st)
-            self._pending_loss = None
-            self._pending_label = None
-            raise
-        if self._dw_forked:     # the weight-gradient slabs written on the second side stream
-            torch.cuda.current_stream().wait_stream(self.side2)
-            self._dw_forked = False
-        check(lib.edgl_reduce_defer(0, st), "edgl_reduce_defer")   # runs the remaining queued reductions in one launch
-        if self._pending_loss is not None:   # (no block: no side-stream join in the backward)
-            self._pending_loss(st)
-            self._pending_loss = None
-            if self.accumulate_loss:         # (the loss launch of a model without blocks runs on the main stream)
-                self.loss_sum.add_(self.loss)
-        if self._lazy_loss and not self._side_has_grads:
-            self._loss_unjoined = True       # (step() joins behind the optimizer, or the caller does: join_loss())
-        else:
-            torch.cuda.current_stream().wait_stream(self.side)
-            self._loss_unjoined = False
 
     def join_loss(self) -> None:
         """Orders the current stream behind the kernels that write `self.loss` (launching them first if the last step left them
@@ -554,7 +575,7 @@ class TrainEngine:
             self._deferred_loss(self.side.cuda_stream)
             self._deferred_loss = None
             self._loss_unjoined = True
-        if getattr(self, "_loss_unjoined", False):
+        if self._loss_unjoined:
             torch.cuda.current_stream().wait_stream(self.side)
             self._loss_unjoined = False
 
@@ -567,8 +588,6 @@ class TrainEngine:
             # d_rows: written by the forward call.  The one-hot term of the table / bias gradient (a scatter of the weighted rows:
             # f32 atomics that commute with the embedding scatter's) is deferred to the side stream at the end of the backward
             defer = 1 if self.blk else 0
-            if self.score_atomic:
-                defer |= 2      # d_table / d_bias zero-filled under the encoder (below): the row chunks add up in them, no slab reduction
             if self._fold:
                 defer |= 4      # the slabs stay in the flash workspace: the optimizer launch sums them (no slab_reduce launch)
                 o_t, o_b, ns = self._slab_info
@@ -579,21 +598,14 @@ class TrainEngine:
                   "edgl_score_flash_bwd")
             # the one-hot term as extra blocks of the embedding scatter's launch at the end of the backward (no launch, no fork)
             self._label_fused = bool((defer & 1) and self.code == _lib.BF16 and C == 128 and lib.edgl_encode_bwd_label_fused(C, code)
-                                     and os.environ.get("EDGL_LABEL_FUSED", "1") != "0"
-                                     and os.environ.get("EDGL_SCORE_STRIP", "1") != "0")    # (only the strip passes leave the term out)
+                                     and self.sw_score_strip)    # (only the strip passes leave the term out)
             if (defer & 1) and not self._label_fused:
                 self._pending_label = lambda s: check(lib.edgl_score_flash_label_term(
                     _ptr(self.hrows_c), _ptr(lab), _ptr(self.coef), None, R, C, I, 0, I, _ptr(self.nvalid), _ptr(tab.grad),
                     _ptr(m.output_bias.grad), code, s), "edgl_score_flash_label_term")
-                # ... started right here on the side stream, beside the block-tail backward (measured on one box, 3 x 300 steps each:
-                # 0.8895 ms against 0.8946 with the launch at the end of the backward, where it sat in front of the slab reductions
-                # of the final join; the tail kernel itself takes 88 instead of 82 us next to it).  EDGL_LABEL_EARLY=0: at the end.
-                # Default (2): behind the tail backward, beside the BiMAU sweeps (2 waves per SIMD at 256 registers, no LDS
-                # pressure from the scatter): 0.868 ms against 0.876 (1) and 0.879 (0), 3 x 300 steps each on one box.
-                if os.environ.get("EDGL_LABEL_EARLY", "2") == "1":
-                    self.side.wait_stream(torch.cuda.current_stream())
-                    self._pending_label(self.side.cuda_stream)
-                    self._pending_label = None
+                # ... launched on the side stream behind the tail backward, beside the BiMAU sweeps (2 waves per SIMD at 256 registers,
+                # no LDS pressure from the scatter): measured 0.868 ms against 0.876 beside the tail backward itself and 0.879 at the
+                # end of the backward, 3 x 300 steps each on one box.  Unfused tail: at the end of the backward (_issue_backward_end).
         else:
             check(lib.edgl_score_ce_bwd(_ptr(self.hrows_c), _ptr(tab_c), _ptr(m.output_bias), _ptr(lab), _ptr(self.lse),
                                         _ptr(self.coef), None, R, C, I, 0, I, _ptr(self.nvalid), _ptr(self.d_rows), _ptr(tab.grad),
@@ -612,9 +624,6 @@ class TrainEngine:
             x_in, cin = (self.x0, 3 * C) if i == 0 else (self.blk[i - 1]["y"], C)
             dh2, dh1 = drop(hd, 12 + 4 * i), drop(hd, 11 + 4 * i)
             if self.fused_tail:
-                if self._dw_forked:     # the previous block's products on the side stream read what this block's kernels rewrite
-                    torch.cuda.current_stream().wait_stream(self.side2)
-                    self._dw_forked = False
                 # the five weight-gradient products of the block run as one grouped launch after the BiMAU backward
                 check(lib.edgl_gemm_dw_defer(1, st), "edgl_gemm_dw_defer")
                 # one launch: LN3' -> GELU' -> dX(Wt) -> LN2' -> dX(Wout) * GELU' -> dX(Wi) -> LN1' -> dX(Wo)  (csrc/k_tail.hip)
@@ -631,7 +640,7 @@ class TrainEngine:
                                         _ptr(blk.att_ln.gamma.grad), _ptr(blk.att_ln.beta.grad), _ptr(blk.out_ln.gamma.grad),
                                         _ptr(blk.out_ln.beta.grad), _ptr(tl.gamma.grad), _ptr(tl.beta.grad),
                                         _ptr(self._ws(lib.edgl_tail_bwd_workspace(B, C))), self.pad[0], self.pad[1], code, st), "edgl_tail_bwd")
-                if self._pending_label is not None and os.environ.get("EDGL_LABEL_EARLY", "2") == "2":   # beside the BiMAU sweeps
+                if self._pending_label is not None:   # beside the BiMAU sweeps
                     self.side.wait_stream(torch.cuda.current_stream())
                     self._pending_label(self.side.cuda_stream)
                     self._pending_label = None
@@ -640,15 +649,6 @@ class TrainEngine:
                 self._dense_dw(b["f"], self.d_o, blk.out.kernel, blk.out.bias, 2 * C, C)
                 self._dense_dw(b["a1"], self.d_pre_f, blk.inter.kernel, blk.inter.bias, C, 2 * C)
                 self._dense_dw(b["att"], self.d_ao, blk.att_out.kernel, blk.att_out.bias, C, C)
-                if self.dw_overlap & 1:
-                    # The tail's weight-gradient products depend on the tail backward only: their grouped launch goes to the second
-                    # side stream, UNDER the attention backward (VALU / transcendental bound, matrix pipe > 80 % idle) instead of
-                    # behind it on the main stream.  Their split slabs are reduced by the step's one reduction launch (the deferred
-                    # reduction queue is not bound to a stream); the main stream joins in front of that launch.
-                    self.side2.wait_stream(torch.cuda.current_stream())
-                    check(lib.edgl_gemm_dw_defer(0, self.side2.cuda_stream), "edgl_gemm_dw_defer")
-                    check(lib.edgl_gemm_dw_defer(1, st), "edgl_gemm_dw_defer")
-                    self._dw_forked = True
             else:
                 # y = LN(drop(o) + a1)
                 self._ln_bwd(b["o"], b["a1"], C, blk.out_ln, b["st2"], dY, dh2, self.G3, self.G4 if dh2.active else None)
@@ -682,48 +682,11 @@ class TrainEngine:
                                              _ptr(self.job_order), self.mau_flags, code, st), "edgl_bimau_bwd_ord")
             self._dense_dw(x_in, self.G4c, att.dense_kernel, att.dense_bias, cin, 4 * C)
             if self.fused_tail:
-                if self.dw_overlap & 2:
-                    # ... and the QKVT product beside the dX GEMM / embedding backward chain that does not need it
-                    self.side2.wait_stream(torch.cuda.current_stream())
-                    check(lib.edgl_gemm_dw_defer(0, self.side2.cuda_stream), "edgl_gemm_dw_defer")
-                    self._dw_forked = True
-                else:
-                    check(lib.edgl_gemm_dw_defer(0, st), "edgl_gemm_dw_defer")
+                check(lib.edgl_gemm_dw_defer(0, st), "edgl_gemm_dw_defer")
             d_in = self.G3c if i == 0 else self.G3
             self._dense_dx(self.G4c, att.dense_kernel, d_in, cin, 4 * C)
             if i == 0:
-                # every slab reduction queued so far (weight-gradient GEMMs, BiMAU / LayerNorm partials) runs on the side
-                # stream under the embedding backward, whose atomics leave the CUs mostly idle
-                # (bound of this fork, measured with the loss kernels left out: 6-8 us of the step — the event record behind the dX GEMM)
-                pending, self._pending_loss = self._pending_loss, None
-
-                def loss_launches(s, pending=pending, parts=[bj["tpp_part"] for bj in self.blk], desc=self.tpp_desc):
-                    if self.fused_tpp:    # the regulariser from sweep 1's partial sums, block by block
-                        for j, bj in enumerate(self.blk):
-                            # (the count sweep 1 used rides behind the sums: nothing of the batch is read here)
-                            check(lib.edgl_tpp_finish_parts_n(_ptr(parts[j]), B * H, float(m.ct_reg / H), H, _ptr(bj["tpp"]),
-                                                              _ptr(self.loss_tpp), 1 if j > 0 else 0, s), "edgl_tpp_finish_parts")
-                    if pending is not None:
-                        pending(s)
-                        if self.accumulate_loss:     # running sum of the step losses where they are produced (train.py reads it at its logging points)
-                            with torch.cuda.stream(self.side):
-                                self.loss_sum.add_(self.loss)
-
-                self._side_has_grads = self._pending_label is not None      # (the one-hot term's atomics: Adam must wait for them)
-                if self._lazy_loss and not self.sync_loss and not self._side_has_grads and self.ce_part is not None and \
-                        (self.fused_tpp or m.ct_reg == 0.0) and os.environ.get("EDGL_DEFER_LOSS", "1") != "0" and \
-                        os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") != "1":
-                    self._deferred_loss = loss_launches      # no fork here: _issue() of the next step, or join_loss()
-                else:
-                    self.side.wait_stream(torch.cuda.current_stream())
-                    loss_launches(self.side.cuda_stream)
-                if self._pending_label is not None:
-                    self._pending_label(self.side.cuda_stream)
-                    self._pending_label = None
-                if not self._lazy_loss or self._side_has_grads:
-                    if self._dw_forked:
-                        self.side.wait_stream(self.side2)
-                    check(lib.edgl_reduce_flush(self.side.cuda_stream), "edgl_reduce_flush")
+                self._issue_backward_end()
             # both residual branches feed the first C channels of the block input (temporal.py:447, EasyDGL.py:116)
             if i > 0:
                 check(lib.edgl_add_cols(_ptr(d_in), cin, _ptr(self.G1), _ptr(self.G2), C, self.rows, C, code, st), "edgl_add_cols")
@@ -734,7 +697,7 @@ class TrainEngine:
                 dY = d_in   # first block: the embedding backward adds the two branches itself (one pass less over dX0)
         d0 = drop(hd, 1)
         add1, add2 = (self.G1, self.G2) if self.blk else (None, None)
-        if getattr(self, "_label_fused", False):
+        if self._label_fused:
             check(lib.edgl_encode_bwd_add_label(_ptr(self.ids), _ptr(self.marks), _ptr(dY), _ptr(add1), _ptr(add2), B, T, C, E, I,
                                                 float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad),
                                                 _ptr(m.pcoding.pembs.lookup_table.grad), _ptr(m.mark_embs.lookup_table.grad),
@@ -746,6 +709,40 @@ class TrainEngine:
                                              float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad), _ptr(m.pcoding.pembs.lookup_table.grad),
                                              _ptr(m.mark_embs.lookup_table.grad), _ptr(self._ws(lib.edgl_encode_bwd_workspace(B, T, C))),
                                              self.c_true, code, st), "edgl_encode_bwd_add")
+
+    def _issue_backward_end(self):
+        """Behind the dX GEMM of the first block: every slab reduction queued so far (weight-gradient GEMMs, BiMAU / LayerNorm partials)
+        runs on the side stream under the embedding backward, whose atomics leave the CUs mostly idle — with the loss launches
+        and the one-hot term of the table gradient, unless they ride elsewhere.
+        (bound of this fork, measured with the loss kernels left out: 6-8 us of the step — the event record behind the dX GEMM)"""
+        m = self.m
+        B, H = self.B, self.H
+        pending, self._pending_loss = self._pending_loss, None
+
+        def loss_launches(s, pending=pending, parts=[bj["tpp_part"] for bj in self.blk]):
+            if self.fused_tpp:    # the regulariser from sweep 1's partial sums, block by block
+                for j, bj in enumerate(self.blk):
+                    # (the count sweep 1 used rides behind the sums: nothing of the batch is read here)
+                    check(lib.edgl_tpp_finish_parts_n(_ptr(parts[j]), B * H, float(m.ct_reg / H), H, _ptr(bj["tpp"]),
+                                                      _ptr(self.loss_tpp), 1 if j > 0 else 0, s), "edgl_tpp_finish_parts")
+            if pending is not None:
+                pending(s)
+                if self.accumulate_loss:     # running sum of the step losses where they are produced (train.py reads it at its logging points)
+                    with torch.cuda.stream(self.side):
+                        self.loss_sum.add_(self.loss)
+
+        self._side_has_grads = self._pending_label is not None      # (the one-hot term's atomics: Adam must wait for them)
+        if self._lazy_loss and not self.sync_loss and not self._side_has_grads and self.ce_part is not None and \
+                (self.fused_tpp or m.ct_reg == 0.0) and self.sw_defer_loss:
+            self._deferred_loss = loss_launches      # no fork here: _issue() of the next step, or join_loss()
+        else:
+            self.side.wait_stream(torch.cuda.current_stream())
+            loss_launches(self.side.cuda_stream)
+        if self._pending_label is not None:
+            self._pending_label(self.side.cuda_stream)
+            self._pending_label = None
+        if not self._lazy_loss or self._side_has_grads:
+            check(lib.edgl_reduce_flush(self.side.cuda_stream), "edgl_reduce_flush")
 
     # ---- more than 16 mark types: the attention of a block as mark groups (see __init__) -----------------------------------
     def _attention_fwd_groups(self, b, x, cin, da, st):
@@ -796,31 +793,8 @@ class TrainEngine:
     def _optimizer(self):
         m = self.m
         m.mask_padded_grads()     # (channel-padded models: the one gradient that is not zero on a padded entry by itself)
-        if os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") == "1":     # A/B switch: no look-ahead of the step counters
-            seg = self.l2_seg if m.l2_reg != 0.0 else None
-            check(lib.edgl_adam_apply(_ptr(m._arena), _ptr(m._grad_arena), _ptr(m._adam_m), _ptr(m._adam_v), m._arena.numel(), 0.9,
-                                      0.999, 1e-8, _ptr(m._adam_state), float(m.l2_reg), _ptr(seg),
-                                      0 if seg is None else seg.numel() // 2, _ptr(m._shadow), _stream()), "edgl_adam_apply")
-            return
         seg = self.l2_seg if m.l2_reg != 0.0 else None
-        if os.environ.get("EDGL_ADAM_NEXT", "0") == "1":
-            # optimizer + the counters of the next step in ONE launch (the last workgroup to finish advances them)
-            l2p = None
-            if self.l2_parts is not None and seg is not None:
-                self._l2p_cur ^= 1       # the copy the NEXT step reads
-                l2p = self.l2_parts[self._l2p_cur]
-                self._l2p_ready = True
-                m._l2_parts_owner = id(self)
-            if getattr(self, "_adam_ticket", None) is None:
-                self._adam_ticket = torch.zeros(int(lib.edgl_adam_next_tickets(m._arena.numel())), device=m._arena.device, dtype=torch.int32)
-            check(lib.edgl_adam_apply_l2p_next(_ptr(m._arena), _ptr(m._grad_arena), _ptr(m._adam_m), _ptr(m._adam_v), m._arena.numel(),
-                                               0.9, 0.999, 1e-8, _ptr(m._adam_state), float(m.l2_reg), _ptr(seg),
-                                               0 if seg is None else seg.numel() // 2, _ptr(m._shadow), _ptr(l2p), _ptr(m._rng_state),
-                                               float(m.learning_rate), _ptr(self._adam_ticket), _stream()), "edgl_adam_apply_l2p_next")
-            m._state_ahead = True
-            return
-        if self.adam_ex and not getattr(m, "_state_pinned", False):
-            import ctypes
+        if self.adam_ex and not m._state_pinned:
             l2p = None
             if self.l2_parts is not None and seg is not None:
                 self._l2p_cur ^= 1       # the copy the NEXT step reads
@@ -940,11 +914,10 @@ class TrainEngine:
         if not self.use_graph:
             if distributed:
                 self._global_counts()
-            self._issue(lazy_loss=not distributed and os.environ.get("EDGL_LAZY_LOSS", "1") != "0",
-                        fold_slabs=self.adam_ex and not distributed and not getattr(self.m, "_state_pinned", False))
+            self._issue(lazy_loss=not distributed, fold_slabs=self.adam_ex and not distributed and not self.m._state_pinned)
             out = self.loss
             if distributed:
-                evs = getattr(self, "_ar_events", None)      # bench.py: HIP events around the step's one collective (its EXPOSED time:
+                evs = self._ar_events      # bench.py: HIP events around the step's one collective (its EXPOSED time:
                 if evs is not None:                         # nothing of the step runs beside it — the last gradients are final only now)
                     e0 = torch.cuda.Event(enable_timing=True); e0.record()
                 out = self._dp_allreduce()
@@ -974,8 +947,7 @@ class TrainEngine:
                 self._global_counts()      # (the capture below reads the counts of the current batch)
             # (the warm-up's optimizer left the counters of the next step in place: the captured sequence starts without the
             #  single-thread update and — with its own optimizer — ends with it)
-            # (the A/B switch EDGL_ENGINE_LEGACY_FORK=1 has no look-ahead: its _issue() carries the update itself)
-            assert getattr(self.m, "_state_ahead", False) or os.environ.get("EDGL_ENGINE_LEGACY_FORK", "0") == "1"
+            assert self.m._state_ahead
             self.m._state_pinned = True      # (the captured launches keep the counters' addresses: no engine swaps them from here on)
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
@@ -989,7 +961,7 @@ class TrainEngine:
             return self.loss
         if self._distributed:
             self._global_counts()
-        if not getattr(self.m, "_state_ahead", False):   # somebody settled the counters (a checkpoint, an autograd-path step)
+        if not self.m._state_ahead:   # somebody settled the counters (a checkpoint, an autograd-path step)
             self._advance_state(_stream())
         self.graph.replay()
         self.m._state_ahead = not self._distributed       # the captured optimizer ends with the next step's counters

@@ -29,6 +29,11 @@ class Sequential(nn.Module):
         self.act_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}[cd]
         self._arena: Optional[torch.Tensor] = None
         self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (EasyDGL at a head dim the kernels do not tile)
+        # hand-over state between this model and the static engines that train it (engine.TrainEngine)
+        self._state_ahead = False        # the step counters already hold the NEXT step's values (settle_state undoes it)
+        self._state_pinned = False       # a captured graph keeps the counters' addresses: no engine swaps the buffers any more
+        self._table_grad_zero = None     # id of the engine whose optimizer launch left the tied table's / output bias's gradient at zero
+        self._l2_parts_owner = None      # id of the engine whose optimizer launch left the sums of squares of the current weights
 
     # ---- flat parameter arena -------------------------------------------------------------------------
     def finalize(self, device) -> "Sequential":
@@ -300,7 +305,7 @@ class Sequential(nn.Module):
         calls this first: the counters go back to "steps taken so far"."""
         self._l2_parts_owner = None      # (whoever settles the counters is about to read or rewrite the state itself)
         self._table_grad_zero = None     # (... or the gradient arena: engine.TrainEngine zero-fills the tied table's gradient again)
-        if getattr(self, "_state_ahead", False):
+        if self._state_ahead:
             self._rng_state[1] -= 1
             self._adam_state[0] -= 1
             self._state_ahead = False

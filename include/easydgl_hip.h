@@ -468,7 +468,9 @@ int edgl_score_flash_bwd(const void* rows, const void* table, const float* out_b
  * -= gscale coef[r] over the weighted rows (f32 atomics: commutes with every other accumulation into the two arrays).
  * edgl_score_flash_bwd_ex(defer_label_term = 1) leaves exactly this out where its product pass does not contain it (bf16, C = 128 / 256 / 512: the strip kernels);
  * edgl_score_flash_label_term then applies it — and is a no-op for every other configuration.  A training loop may run it off the
- * critical path (any time after the table-side reduction of edgl_score_flash_bwd_ex wrote d_table / d_bias). */
+ * critical path (any time after the table-side reduction of edgl_score_flash_bwd_ex wrote d_table / d_bias).
+ * Bit 1 (value 2) of defer_label_term, the form that adds the row chunks into a zero-filled d_table / d_bias with f32 atomics, is no
+ * longer used by the training engine. */
 int edgl_score_flash_bwd_ex(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                             const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int i0,
                             int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias, float* workspace,
@@ -576,13 +578,6 @@ int edgl_adam_apply(float* param, const float* grad, float* m, float* v, long n,
 int edgl_adam_l2_parts(long n);
 int edgl_adam_apply_l2p(float* param, const float* grad, float* m, float* v, long n, float beta1, float beta2, float eps,
                         const uint64_t* step_state, float l2, const int64_t* seg, int nseg, void* shadow, float* l2_part, void* stream);
-/* edgl_adam_apply_l2p (l2_part may be NULL) + edgl_step_begin in ONE launch: the last workgroup to finish advances the dropout step
- * counter, the Adam step and its bias-corrected learning rate (Base.py:142-144's global step) for the NEXT step.  ticket:
- * edgl_adam_next_tickets(n) zero-initialised uint32 of the caller's, left at zero.  An A/B switch of the training engine. */
-int edgl_adam_next_tickets(long n);
-int edgl_adam_apply_l2p_next(float* param, const float* grad, float* m, float* v, long n, float beta1, float beta2, float eps,
-                             uint64_t* step_state, float l2, const int64_t* seg, int nseg, void* shadow, float* l2_part,
-                             uint64_t* rng_state, float lr, uint32_t* ticket, void* stream);
 /* The eager engine's optimizer launch: edgl_adam_apply_l2p that also (a) adds the sum of `nslab` partial-gradient slabs to two ranges of
  * the gradient arena — grad[lo .. hi) += sum_s slabs[s * stride + (i - lo)]; the first `zero_first_a` elements of range a take none (row 0
  * of the used item table is the zero constant, coding.py:56-57): the row-chunk slabs that edgl_score_flash_bwd_ex(defer_label_term & 4)

@@ -1,4 +1,4 @@
-"""Three rocprofv3 --kernel-trace --pmc passes over the default bench command (tools/r06_call1.sh) -> the per-kernel table of
+"""Three rocprofv3 --kernel-trace --pmc passes over the default bench command -> the per-kernel table of
 profiles/rNN_step_pmc.txt (the format tools/make_valu_floor.py reads).
    python tools/make_step_pmc.py PASS1.db PASS2.db PASS3.db [round tag] > profiles/rNN_step_pmc.txt
 pass 1: SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
