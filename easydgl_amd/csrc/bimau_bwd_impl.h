@@ -5,10 +5,6 @@
 
 #include "bimau_common.h"
 
-#ifndef EDGL_EXP_SKIP_TILES
-#define EDGL_EXP_SKIP_TILES 0   // timing experiment: query tiles left out at the end (wrong results, bounds the cost of the remainder tile)
-#endif
-
 #ifdef EDGL_PHASE_TIMING
 extern __device__ unsigned long long g_phase_cycles[16];
 #endif
@@ -24,10 +20,8 @@ constexpr int KY_BLOCKS = 384;   // workgroups of kernel Y per mark group (x KY_
 // big_nj(dh) channel tiles of 16.  Enough row splits for ~512 workgroups, at least 16.  Head dim 64: four tiles — 64
 // accumulator registers, 253 in all, two waves per SIMD; with eight (402 registers, one wave per SIMD, nothing to hide its
 // LDS / MFMA / sigmoid chain behind) the kernel measured 167 us at the recipe shape against 122.
-#ifndef EDGL_WG_NJ64
-#define EDGL_WG_NJ64 4
-#endif
-constexpr int big_nj(int dh) { return dh == 64 ? EDGL_WG_NJ64 : 32 / (dh / 16); }   // channel tiles of a weight-gradient workgroup
+constexpr int WG_NJ64 = 4;
+constexpr int big_nj(int dh) { return dh == 64 ? WG_NJ64 : 32 / (dh / 16); }   // channel tiles of a weight-gradient workgroup
 inline int big_row_splits(int dh, int E) {
     const int nc = big_nj(dh) * 16;
     const int groups = std::max(1, (dh * E + nc - 1) / nc);
@@ -235,7 +229,7 @@ __global__ __launch_bounds__(256) void bimau_bwd_sweep1_kernel(BwdP p) {   // (f
             if (lane < 16) p.rowdot_ws[bp * p.T + pend_q] = pend_rowdot;
         }
     };
-    for (int qt = 0; qt < NT - EDGL_EXP_SKIP_TILES; ++qt) {
+    for (int qt = 0; qt < NT; ++qt) {
         asm volatile("" ::: "memory");   // keep loop-invariant LDS operands from being hoisted into registers
         const int q = qt * 16 + l15;
         const bool qok = q < p.T;
@@ -521,7 +515,7 @@ __global__ __launch_bounds__(256) void bimau_bwd_sweep2_kernel(BwdP p) {
     };
 #pragma unroll
     for (int ut = 0; ut < DTS; ++ut) pend_dq[ut] = frag_zero<T>();
-    for (int qt = 0; qt < NT - EDGL_EXP_SKIP_TILES; ++qt) {
+    for (int qt = 0; qt < NT; ++qt) {
         asm volatile("" ::: "memory");
         const int q = qt * 16 + l15;
         const bool qok = q < p.T;

@@ -183,8 +183,7 @@ __device__ __forceinline__ KeyMask<NK> keymask_tail(const KeyMask<NT>& km) {
 }
 // host side: EDGL_BIMAU_SKIP=0 launches the kernels that walk every key tile (read per launch: tests flip it)
 inline bool bimau_skip_enabled() {
-    const char* e = getenv("EDGL_BIMAU_SKIP");
-    return !(e && e[0] == '0');
+    return edgl_env_on("EDGL_BIMAU_SKIP");
 }
 // run f(std::integral_constant<int, NK>) for the wave-uniform nk in 1 .. NT
 template <int N, typename F>

@@ -9,16 +9,9 @@
 
 #include "bimau_common.h"
 
-#ifndef EDGL_EXP_SKIP_TILES
-#define EDGL_EXP_SKIP_TILES 0   // timing experiment: query tiles left out at the end (wrong results, bounds the cost of the remainder tile)
-#endif
-
-#ifndef EDGL_BIMAU_FWD_WAVES
-#define EDGL_BIMAU_FWD_WAVES 2   // waves per SIMD the headline instance (bf16, head dim 16, E = 16) is compiled for (3: 168 registers, 4 spilled — 79 -> 84 us)
-#endif
-
 namespace bimau {
 
+constexpr int FWD_WAVES = 2;   // waves per SIMD the headline instance (bf16, head dim 16, E = 16) is compiled for (3: 168 registers, 4 spilled — 79 -> 84 us)
 
 struct FwdP {
     const void* qkvt; const void* resid; int ld_res;
@@ -53,7 +46,7 @@ __host__ __device__ constexpr size_t fwd_wave_bytes() {
 //     query loop exists once per key-tile count NK = 1 .. NT (straight-line code with NK-entry register arrays each); the wave
 //     picks its copy by a scalar branch.  Bidirectional flags only (a causal row's score replacement depends on q).
 template <typename T, int DT, int NT, int EC, int PHASE = 0, bool DB = false, bool SK = false>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 && DT == 1 && EC == 16 && PHASE == 0) ? EDGL_BIMAU_FWD_WAVES : 1) void bimau_fwd_kernel(FwdP p) {
+__global__ __launch_bounds__(256, (sizeof(T) == 2 && DT == 1 && EC == 16 && PHASE == 0) ? FWD_WAVES : 1) void bimau_fwd_kernel(FwdP p) {
     constexpr int dh = 16 * DT, Tp = 16 * NT, LDT = Tp + 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int E = EC ? EC : p.E;
@@ -104,9 +97,6 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DT == 1 && EC == 16 && PHAS
         reinterpret_cast<float*>(Ms + (HAS_M ? Tp * EP : 0)), p.T, LDT, lane);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-#ifdef EDGL_PROLOGUE_ONLY   // diagnostic build (not the product): time of the LDS staging alone — rule 9 of DESIGN.md §4.2
-    if (p.B > 0) { if (km.pad == 0x1234567ull) reinterpret_cast<T*>(p.out)[0] = Ks[lane] + Ms[lane]; return; }
-#endif
 
     const float cscale = p.qk_scale > 0.f ? p.qk_scale : rsqrtf((float)dh);
     const DropKey dk = make_dropkey(p.rng, p.stream_id, p.rate);
@@ -158,7 +148,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 && DT == 1 && EC == 16 && PHAS
             }
         }
     };
-    for (int qt = 0; qt < NT - EDGL_EXP_SKIP_TILES; ++qt) {
+    for (int qt = 0; qt < NT; ++qt) {
         const int q = qt * 16 + l15;
         const bool qok = q < p.T;
         const QOps qnext = load_q(qt + 1 < NT ? qt + 1 : qt);

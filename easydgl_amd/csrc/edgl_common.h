@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 #include "../../include/easydgl_hip.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -36,6 +38,11 @@ extern "C" void edgl_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int edgl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// The environment switches of the library (table in DESIGN.md, "Environment variables") are read through these and nowhere else.
+inline const char* edgl_env(const char* name) { return getenv(name); }
+inline int edgl_env_int(const char* name, int dflt) { const char* e = edgl_env(name); return e ? atoi(e) : dflt; }
+inline bool edgl_env_on(const char* name) { const char* e = edgl_env(name); return !(e && e[0] == '0'); }   // on unless the value starts with '0'
 
 // out[n] (+)= sum_{p<P} part[p*ld + n], fixed summation order (k_misc.hip).  Used for every
 // "per-workgroup partials -> parameter gradient" reduction.
@@ -332,9 +339,6 @@ __device__ __forceinline__ uint32_t drop_hash_pair(const DropKey& k, uint32_t id
 // >= t16.  The top field ranges over [0, 0xFFF1] only: |p_eff - p| <= 2.3e-4 p there, 8e-6 on the others (tools/ hash statistics in
 // rates, field / lag / step correlations at the noise level of 2^18 samples).  Half the VALU work of two paired hashes.
 __device__ __forceinline__ uint64_t drop_hash_quad(const DropKey& k, uint32_t idx0) {
-#ifdef EDGL_EXP_NOHASH   // timing experiment (tools/build_variant.sh): the cost of the hash itself — every element kept
-    return ~0ull;
-#endif
     uint32_t h = (idx0 ^ k.k0) * 0x9E3779B1u + k.k1;
     h ^= h >> 15; h *= 0x85ebca6bu; h ^= h >> 13;
     return (uint64_t)h * 0xFFF1AFD7u;

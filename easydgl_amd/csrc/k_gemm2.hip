@@ -45,16 +45,12 @@ struct EpiP {
 // different L2s and every one of them would fetch those rows again (QKVT projection: 162 MB fetched for 40 MB of activations, its
 // dX 167 for 53, the grouped dW 434 for ~110).  With a grid padded to a multiple of 8 the virtual id  v = (b % 8) * (G / 8) + b / 8
 // hands every XCD one contiguous run of virtual ids; ids >= n_real are padding.  Returns -1 for padding workgroups.
-__device__ __forceinline__ int xcd_virtual_id(int b, int grid, int n_real, int on) {
-    if (!on || (grid & 7)) return b < n_real ? b : -1;
+__device__ __forceinline__ int xcd_virtual_id(int b, int grid, int n_real) {
+    if (grid & 7) return b < n_real ? b : -1;
     const int v = (b & 7) * (grid >> 3) + (b >> 3);
     return v < n_real ? v : -1;
 }
 static inline int xcd_grid(int n_real) { return (n_real + 7) / 8 * 8; }
-static inline int xcd_on() {
-    static const int on = getenv("EDGL_XCD_ORDER") ? atoi(getenv("EDGL_XCD_ORDER")) : 1;
-    return on;
-}
 __device__ __forceinline__ void epi_store4(const EpiP& e, bf16* C, void* Cany, long idx, int n, float x[4]) {
     if (e.flags & EDGL_EPI_BIAS) {
         const float4 b = *reinterpret_cast<const float4*>(e.bias + n);
@@ -105,8 +101,6 @@ struct StripP {
     const bf16* A; const bf16* B; void* C;
     int M, N, K, lda, ldb, ldc;
     EpiP epi;
-    int dbg;   // EDGL_DBG ablation bits (profiling only): 1 skip epilogue stores, 2 skip MFMA loop, 4 skip B streaming
-    int xcd;   // tile_nn_kernel: XCD-aware workgroup order (xcd_virtual_id)
 };
 
 // Epilogue of one [32 rows x 64 columns] accumulator block of a wave.  acc[jz][ix] = L(first = n, second = m): a lane holds 4
@@ -137,7 +131,6 @@ __device__ __forceinline__ void strip_epilogue(const StripP& p, StripEpi& e, f32
     const int g4 = (lane >> 4) * 4, l15 = lane & 15;
     bf16* const Ostage = e.Ostage;
     float* const OstageF = e.OstageF;
-    if (p.dbg & 1) return;
     if (e.staged) {
 #pragma unroll
         for (int ix = 0; ix < 2; ++ix) {
@@ -260,7 +253,6 @@ __global__ __launch_bounds__(W_NT) void strip_gemm_kernel(StripP p) {
     float* const OstageF = reinterpret_cast<float*>(Ws + WELEMS + 256) + wave * 16 * LDOF;
     const int nbase = blockIdx.y * NP;
     const int ncols = min(NP, p.N - nbase);          // multiple of 64
-    if (p.dbg & 16) { if (tid < NP) biasS[tid] = 0.f; __syncthreads(); goto main_loop; }   // ablation: no weight staging
     if (tid < NP) biasS[tid] = ((p.epi.flags & EDGL_EPI_BIAS) && nbase + tid < p.N) ? p.epi.bias[nbase + tid] : 0.f;
     // ---- weights slice -> LDS (once).  Unconditional loads (row / column clamped into the slice: the clamped copies land
     //      in rows / columns >= ncols that no strip reads) issued in batches of 4, so the slice arrives in a few memory
@@ -293,7 +285,6 @@ __global__ __launch_bounds__(W_NT) void strip_gemm_kernel(StripP p) {
         }
     }
     __syncthreads();
-main_loop:
     PH_MARK(0);   // weight slice staged
     const bool staged = !(p.epi.flags & EDGL_EPI_OUT_F32) && !fstage;
     StripEpi se;
@@ -312,7 +303,6 @@ main_loop:
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 bf16x8 f;
-                if (p.dbg & 8) { *reinterpret_cast<uint4*>(&f) = make_uint4(lane, kb, 0, 0); xf[ix][kb] = f; continue; }   // ablation: no A loads
                 if constexpr (B_KC) {
                     *reinterpret_cast<uint4*>(&f) = *reinterpret_cast<const uint4*>(row + kb * 32 + G * 8);
                 } else {
@@ -328,7 +318,6 @@ main_loop:
 #pragma unroll
             for (int jz = 0; jz < 4; ++jz) { acc[jz][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[jz][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
             strip_prefetch_combine(p, se, m0, nbase + nc, lane);
-            if (!(p.dbg & 2))
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
 #pragma unroll
@@ -480,7 +469,7 @@ __global__ __launch_bounds__(G_NT, EPI ? 2 : 3) void tile_nn_kernel(StripP p) {
     const int G = lane >> 4, g4 = G * 4, l15 = lane & 15;
     // consecutive workgroups share the row block (its A rows stay in L2 across the N / 128 column tiles)
     const int nbn = p.N / G_BN;
-    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, ((p.M + G_BM - 1) / G_BM) * nbn, p.xcd);
+    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, ((p.M + G_BM - 1) / G_BM) * nbn);
     if (vid < 0) return;
     const int m0 = (vid / nbn) * G_BM, n0 = (vid % nbn) * G_BN;
     uint4 pa0, pa1, pa2, pa3, pb0, pb1, pb2, pb3;   // named registers (arrays captured by a lambda end up in scratch here)
@@ -592,9 +581,7 @@ static int launch_tile_nn(const StripP& p, hipStream_t st) {
     auto k = tile_nn_kernel<B_KC, EPI>;
     hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     const int nbm = (p.M + G_BM - 1) / G_BM, nbn = p.N / G_BN;
-    StripP q = p;
-    q.xcd = xcd_on();
-    hipLaunchKernelGGL(k, dim3((unsigned)(q.xcd ? xcd_grid(nbm * nbn) : nbm * nbn)), dim3(G_NT), smem, st, q);
+    hipLaunchKernelGGL(k, dim3((unsigned)xcd_grid(nbm * nbn)), dim3(G_NT), smem, st, p);
     EDGL_LAUNCH_CHECK();
     return 1;
 }
@@ -609,10 +596,12 @@ struct TnP {
     int rows_per_split;
     float* partial;   // [splits][Kf + 1][N]  (row Kf = column sums of Y)
     int with_colsum;
-    int tiles_n, tiles_k, nblocks, xcd;   // tn_gemm_kernel: 1-D grid (padded to a multiple of 8 with the XCD-aware order)
+    int tiles_n, tiles_k, nblocks;   // tn_gemm_kernel: 1-D grid (padded to a multiple of 8 with the XCD-aware order)
 };
 
-// TM = output tile edge of a workgroup (4 waves in a 2 x 2 arrangement): 128 (default) or 64 (see tn_tile)
+// TM = output tile edge of a workgroup (4 waves in a 2 x 2 arrangement).  64-tiles quarter the partial slabs of the 128 x 128 layers
+// but every operand column block is then read by twice as many workgroups: measured +18 us in the GEMMs for -12 us in the slab
+// reduction.
 template <int TM>
 __device__ __forceinline__ void tn_body(const TnP& p, int bx, int by, int bz, bf16* Xs, bf16* Ys) {
     constexpr int NI = TM / 32, LDT = TM + 16, PCS = TM / 8, NLD = T_BR * PCS / T_NT;   // 16-byte pieces per row / per thread
@@ -720,7 +709,7 @@ __global__ __launch_bounds__(T_NT) void tn_gemm_kernel(TnP p) {
     bf16* Xs = reinterpret_cast<bf16*>(tn_smem);
     bf16* Ys = Xs + T_BR * (TM + 16);
     // tiles of one row split are consecutive virtual ids: they stream the same rows of X and Y and share one XCD's L2
-    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, p.nblocks, p.xcd);
+    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, p.nblocks);
     if (vid < 0) return;
     tn_body<TM>(p, vid % p.tiles_n, (vid / p.tiles_n) % p.tiles_k, vid / (p.tiles_n * p.tiles_k), Xs, Ys);
 }
@@ -729,13 +718,13 @@ __global__ __launch_bounds__(T_NT) void tn_gemm_kernel(TnP p) {
 // other and individually too small for the chip — the 128 x 128 layers run two 64-row steps per workgroup and leave 25 MB of
 // partial slabs each.  Grouped, they share the launch with the wide QKVT product and get row splits of similar length.
 constexpr int TN_MAX_JOBS = 8;
-struct TnGroupP { TnP job[TN_MAX_JOBS]; int tiles_n[TN_MAX_JOBS], tiles_k[TN_MAX_JOBS], blk0[TN_MAX_JOBS + 1]; int n, xcd; };
+struct TnGroupP { TnP job[TN_MAX_JOBS]; int tiles_n[TN_MAX_JOBS], tiles_k[TN_MAX_JOBS], blk0[TN_MAX_JOBS + 1]; int n; };
 __global__ __launch_bounds__(T_NT) void tn_gemm_group_kernel(TnGroupP g) {
     extern __shared__ __attribute__((aligned(16))) char tn_smem[];
     bf16* Xs = reinterpret_cast<bf16*>(tn_smem);
     bf16* Ys = Xs + T_BR * (128 + 16);
     // (the tiles of one row split are consecutive ids: with the XCD-aware order they share one L2)
-    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, g.blk0[g.n], g.xcd);
+    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, g.blk0[g.n]);
     if (vid < 0) return;
     int j = 0;
     for (int i = 1; i < g.n; ++i)
@@ -793,22 +782,19 @@ int edgl_gemm2_try_strip(const void* A, const void* B, void* C, int M, int N, in
                     (ldc % 4 == 0) && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0 &&
                     (!aux || ((uintptr_t)aux & 7) == 0) && (!bias || ((uintptr_t)bias & 15) == 0);
     if (!ok) return 0;
-    static const int dbg = getenv("EDGL_DBG") ? atoi(getenv("EDGL_DBG")) : 0;
-    StripP p{(const bf16*)A, (const bf16*)B, C, M, N, K, lda, ldb, ldc, EpiP{bias, aux, flags}, dbg, 0};
+    StripP p{(const bf16*)A, (const bf16*)B, C, M, N, K, lda, ldb, ldc, EpiP{bias, aux, flags}};
     int rc;
     // wide projections with a plain (bias-only) epilogue: the 128 x 128 tiled kernel
-    static const int use_tile = getenv("EDGL_GEMM_TILE") ? atoi(getenv("EDGL_GEMM_TILE")) : 1;
-    if (use_tile && M >= 4096 && N >= 256 && (N % G_BN) == 0 && (K % G_BK) == 0 && K >= 128 && (flags & ~EDGL_EPI_BIAS) == 0 &&
+    if (M >= 4096 && N >= 256 && (N % G_BN) == 0 && (K % G_BK) == 0 && K >= 128 && (flags & ~EDGL_EPI_BIAS) == 0 &&
         (ldc % 8) == 0)
         return b_kc ? launch_tile_nn<true>(p, st) : launch_tile_nn<false>(p, st);
     // beyond the register strips (K <= 512): the tiled kernel with the general epilogue
     if (K > 512) {
-        if (use_tile && M >= 1024 && (N % G_BN) == 0 && (K % G_BK) == 0)
+        if (M >= 1024 && (N % G_BN) == 0 && (K % G_BK) == 0)
             return b_kc ? launch_tile_nn<true, true>(p, st) : launch_tile_nn<false, true>(p, st);
         return 0;
     }
-    static const int stream_min_n = getenv("EDGL_GEMM_STREAM_N") ? atoi(getenv("EDGL_GEMM_STREAM_N")) : 384;
-    if (N >= stream_min_n && (K == 384 || K == 512) && M >= 4096) {   // A would be re-read by >= 3 column slices
+    if (N >= 384 && (K == 384 || K == 512) && M >= 4096) {   // A would be re-read by >= 3 column slices
         rc = 0;
         if (K == 384) rc = b_kc ? launch_stream<12, true>(p, st) : launch_stream<12, false>(p, st);
         else rc = b_kc ? launch_stream<16, true>(p, st) : launch_stream<16, false>(p, st);
@@ -822,21 +808,13 @@ int edgl_gemm2_try_strip(const void* A, const void* B, void* C, int M, int N, in
     }
 #undef STRIP_CASE
     // shapes the strips decline (their weight slice + staging exceed the LDS, e.g. K = 512 with N = 1024 and an epilogue)
-    if (rc == 0 && use_tile && M >= 1024 && (N % G_BN) == 0 && (K % G_BK) == 0 && K >= 128)
+    if (rc == 0 && M >= 1024 && (N % G_BN) == 0 && (K % G_BK) == 0 && K >= 128)
         return b_kc ? launch_tile_nn<true, true>(p, st) : launch_tile_nn<false, true>(p, st);
     return rc;
 }
 
 // C[Kf,N] = X^T . Y (f32, overwritten or accumulated); if dbias != nullptr also dbias[N] = colsum(Y).
 // workspace floats: edgl_gemm2_tn_workspace(R, Kf, N).
-static int tn_tile(int Kf, int N) {
-    // 128-tiles by default.  64-tiles (EDGL_TN_TILE=64, experiment) quarter the partial slabs of the 128 x 128 layers but
-    // every operand column block is then read by twice as many workgroups: measured +18 us in the GEMMs for -12 us in
-    // the slab reduction.
-    (void)Kf; (void)N;
-    static const int force = getenv("EDGL_TN_TILE") ? atoi(getenv("EDGL_TN_TILE")) : 0;
-    return force == 64 ? 64 : 128;
-}
 // Row splits of a TN product (or of a group of them: `tiles` output tiles in all, `out_elems` f32 of output in all, `flop` =
 // 2 R sum(Kf N)).  The chip takes workgroups in rounds of its CU count: 192 tiles x 2 splits = 384 workgroups run as TWO
 // rounds (the 512-unit QKVT weight gradient: 229 us), x 4 = 768 as three of half the length (143 us) — but every split
@@ -845,9 +823,7 @@ static int tn_tile(int Kf, int N) {
 // of prologue / slab write per workgroup, x1.25 below two resident workgroups per CU, ~4 TB/s of slab reduction), the
 // cheapest split count wins: 4 for that product (768 workgroups), 28 for the headline's grouped launch (504, as before).
 static int tn_choose_splits(int R, int tiles, double flop, double out_elems, int cap) {
-    static const int forced = getenv("EDGL_TN_TARGET") ? atoi(getenv("EDGL_TN_TARGET")) : 0;   // experiments: fixed workgroup target
     const int smax = std::max(1, std::min(cap, R / 128));
-    if (forced > 0) return std::max(1, std::min(forced / std::max(1, tiles), smax));
     static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
@@ -866,8 +842,7 @@ static int tn_choose_splits(int R, int tiles, double flop, double out_elems, int
     return best;
 }
 static int tn_splits(int R, int Kf, int N) {
-    const int tm = tn_tile(Kf, N);
-    const int tiles = ((Kf + tm - 1) / tm) * ((N + tm - 1) / tm);
+    const int tiles = ((Kf + 127) / 128) * ((N + 127) / 128);
     return tn_choose_splits(R, tiles, 2.0 * R * Kf * N, (double)(Kf + 1) * N, 1 << 20);
 }
 long edgl_gemm2_tn_workspace(int R, int Kf, int N) { return (long)tn_splits(R, Kf, N) * (Kf + 1) * N; }
@@ -901,21 +876,15 @@ static int tn_flush(hipStream_t st) {
         total_tiles += g.tiles_n[i] * g.tiles_k[i];
     }
     // one split count for the whole group (row ranges of similar length), capped by what each job's workspace was sized for
-    static const int target = getenv("EDGL_TN_GROUP_TARGET") ? atoi(getenv("EDGL_TN_GROUP_TARGET")) : 0;
-    int group_splits;
-    if (target > 0) {
-        group_splits = std::max(1, target / std::max(1, total_tiles));
-    } else {
-        double flop = 0.0, elems = 0.0;
-        int rmin = 1 << 30;
-        for (int i = 0; i < n; ++i) {
-            const TnP& q = g_tn_q[i].p;
-            flop += 2.0 * q.R * q.Kf * q.N;
-            elems += (double)(q.Kf + 1) * q.N;
-            rmin = std::min(rmin, q.R);
-        }
-        group_splits = tn_choose_splits(rmin, total_tiles, flop, elems, 1 << 20);
+    double flop = 0.0, elems = 0.0;
+    int rmin = 1 << 30;
+    for (int i = 0; i < n; ++i) {
+        const TnP& q = g_tn_q[i].p;
+        flop += 2.0 * q.R * q.Kf * q.N;
+        elems += (double)(q.Kf + 1) * q.N;
+        rmin = std::min(rmin, q.R);
     }
+    const int group_splits = tn_choose_splits(rmin, total_tiles, flop, elems, 1 << 20);
     int splits[TN_MAX_JOBS], blocks = 0;
     for (int i = 0; i < n; ++i) {
         TnP& p = g_tn_q[i].p;
@@ -929,10 +898,9 @@ static int tn_flush(hipStream_t st) {
         blocks += g.tiles_n[i] * g.tiles_k[i] * sp;
     }
     g.blk0[n] = blocks;
-    g.xcd = xcd_on();
     const size_t tn_lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
     hipFuncSetAttribute((const void*)tn_gemm_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn_lds);
-    hipLaunchKernelGGL(tn_gemm_group_kernel, dim3(g.xcd ? xcd_grid(blocks) : blocks), dim3(T_NT), tn_lds, st, g);
+    hipLaunchKernelGGL(tn_gemm_group_kernel, dim3(xcd_grid(blocks)), dim3(T_NT), tn_lds, st, g);
     EDGL_LAUNCH_CHECK();
     for (int i = 0; i < n; ++i) {
         const TnP& p = g_tn_q[i].p;
@@ -963,8 +931,8 @@ int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int
     int splits = tn_splits(R, Kf, N);
     int rps = ((R + splits - 1) / splits + T_BR - 1) / T_BR * T_BR;
     splits = (R + rps - 1) / rps;
-    TnP p{(const bf16*)X, (const bf16*)Y, R, Kf, N, ldx, ldy, rps, workspace, dbias ? 1 : 0, 0, 0, 0, 0};
-    if (g_tn_defer && tn_tile(Kf, N) == 128) {
+    TnP p{(const bf16*)X, (const bf16*)Y, R, Kf, N, ldx, ldy, rps, workspace, dbias ? 1 : 0, 0, 0, 0};
+    if (g_tn_defer) {
         if (g_tn_n == TN_MAX_JOBS) {
             const int rc = tn_flush(st);
             if (rc) return rc;
@@ -972,17 +940,10 @@ int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int
         g_tn_q[g_tn_n++] = TnQueued{p, C, dbias, accumulate, splits};
         return 1;
     }
-    if (tn_tile(Kf, N) == 64) {
-        const size_t lds = (size_t)2 * T_BR * (64 + 16) * sizeof(bf16);
-        hipFuncSetAttribute((const void*)tn_gemm_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        p.tiles_n = (N + 63) / 64; p.tiles_k = (Kf + 63) / 64; p.nblocks = p.tiles_n * p.tiles_k * splits; p.xcd = xcd_on();
-        hipLaunchKernelGGL(tn_gemm_kernel<64>, dim3(p.xcd ? xcd_grid(p.nblocks) : p.nblocks), dim3(T_NT), lds, st, p);
-    } else {
-        const size_t lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
-        hipFuncSetAttribute((const void*)tn_gemm_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        p.tiles_n = (N + 127) / 128; p.tiles_k = (Kf + 127) / 128; p.nblocks = p.tiles_n * p.tiles_k * splits; p.xcd = xcd_on();
-        hipLaunchKernelGGL(tn_gemm_kernel<128>, dim3(p.xcd ? xcd_grid(p.nblocks) : p.nblocks), dim3(T_NT), lds, st, p);
-    }
+    const size_t lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
+    hipFuncSetAttribute((const void*)tn_gemm_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    p.tiles_n = (N + 127) / 128; p.tiles_k = (Kf + 127) / 128; p.nblocks = p.tiles_n * p.tiles_k * splits;
+    hipLaunchKernelGGL(tn_gemm_kernel<128>, dim3(xcd_grid(p.nblocks)), dim3(T_NT), lds, st, p);
     EDGL_LAUNCH_CHECK();
     const int rc = tn_reduce(workspace, splits, C, Kf, N, dbias, accumulate, st);
     return rc ? rc : 1;

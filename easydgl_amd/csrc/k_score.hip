@@ -1351,7 +1351,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
     __shared__ int wave_eq[4];
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float* x = logits + (long)row * n;
-#ifndef TK_NOMASK
     if (seen) {
         for (int t = tid; t < T; t += 256) {
             const long id = seen[(long)row * T + t] - i0;
@@ -1359,7 +1358,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
         }
         __syncthreads();
     }
-#endif
     // The row as aligned 16-byte pieces (a row of odd length starts anywhere): piece q = tid + 256 jq of the pieces from the aligned
     // address below the row's first element; register j = 4 jq + c holds element  i = 4 q + c - d  (d = the row's offset into its
     // first piece), or key 0 — below every float's key — outside the row.  (4-byte loads: 256 bytes per wave instruction, 1.3 TB/s.)
@@ -1416,9 +1414,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
         if (lane == 0) wcnt[0][w] = c;
         __syncthreads();
         const int C = wcnt[0][0] + wcnt[0][1] + wcnt[0][2] + wcnt[0][3];
-#ifdef TK_ONLYLOAD
-        if (C >= 0) { if (tid == 0) out_idx[(long)row * K] = C; return; }
-#endif
         if (C <= TK_CAP) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
@@ -1480,9 +1475,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
     }
     // ---- the K-th largest key: the largest P with |{key >= P}| >= K -------------------------------------------------------------
     uint32_t prefix = 0u;
-#ifdef TK_NOSEARCH   // timing experiments only
-    prefix = 0xfff00000u;
-#else
     for (int bit = 31; bit >= 0; --bit) {
         const uint32_t cand = prefix | (1u << bit);
         int c = 0;
@@ -1493,7 +1485,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
         const int tot = wcnt[bit & 1][0] + wcnt[bit & 1][1] + wcnt[bit & 1][2] + wcnt[bit & 1][3];
         if (tot >= Keff) prefix = cand;
     }
-#endif
     // ---- gather: keys above the prefix (any order), ties at the prefix (the `remaining` lowest indices) ----------------------------
     if (tid == 0) { cnt_gt = 0; cnt_eq = 0; }
     if (tid < 128) { cval[tid] = -INFINITY; cidx[tid] = 0x7fffffff; }
@@ -1508,7 +1499,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
     if (tid == 0) { cnt_gt = 0; cnt_eq = 0; }
     __syncthreads();
     const bool all_ties = n_eq <= remaining;     // (n_eq >= remaining by construction: == means every tie is taken)
-#ifndef TK_NOGATHER
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int i = elem(j);
@@ -1520,7 +1510,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
             if (pos < 128) { cval[pos] = key_float(key[j]); cidx[pos] = i; }
         }
     }
-#endif
     if (!all_ties) {      // more ties than places: index order — one pass per 1024 consecutive elements (a thread's piece = 4 of them)
 #pragma unroll 1
         for (int jq = 0; jq < NJ / 4; ++jq) {
@@ -1557,7 +1546,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
         }
     }
     __syncthreads();
-#ifndef TK_NOSORT
     // bitonic sort of 128 candidates by (value desc, index asc)
     for (int k = 2; k <= 128; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -1573,7 +1561,6 @@ __global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R
             }
             __syncthreads();
         }
-#endif
     for (int i = tid; i < K; i += 256) {
         out_val[(long)row * K + i] = i < Keff ? cval[i] : -INFINITY;
         out_idx[(long)row * K + i] = i < Keff ? cidx[i] + i0 : -1;
@@ -1750,14 +1737,11 @@ inline int xblocks_of(int n, int xb) { return (n + xb - 1) / xb; }
 // waves per workgroup of the generic product passes where the shape allows both: 8 (two waves per SIMD, bf16 C >= 256: half the
 // output channels per pass, the logits recomputed per half) or 4 (one wave per SIMD, all channels in one pass).  Measured in the
 // engine step (tools/try_shape.py, round 5): C = 256 — equal at 20 K items, 4 waves - 10 % at 100 K, - 13 % at 300 K / 1 M items
-// (config 3: 53.0 -> 45.4 ms); C = 512 — 8 waves - 5..8 % (recipe 1.94 against 2.03 ms).  EDGL_SCORE_NW overrides.
-inline int score_nw(int C, size_t esize) {
-    static const int env = getenv("EDGL_SCORE_NW") ? atoi(getenv("EDGL_SCORE_NW")) : 0;
-    if (env == 4 || env == 8) return env;
-    return (C == 256 && esize == 2) ? 4 : 8;
-}
-inline int score_ftarget() { static const int t = getenv("EDGL_SCORE_FTARGET") ? atoi(getenv("EDGL_SCORE_FTARGET")) : 256; return t; }
-inline int score_target() { static const int t = getenv("EDGL_SCORE_TARGET") ? atoi(getenv("EDGL_SCORE_TARGET")) : 256; return t; }
+// (config 3: 53.0 -> 45.4 ms); C = 512 — 8 waves - 5..8 % (recipe 1.94 against 2.03 ms).
+inline int score_nw(int C, size_t esize) { return (C == 256 && esize == 2) ? 4 : 8; }
+// workgroups the chunk planners aim for: the backward product passes / the flash forward (one per CU).  Constants: the workspace
+// sizes and slab offsets that edgl_score_*_workspace / edgl_score_flash_slab_info report follow from them, and callers cache those.
+constexpr int SCORE_TARGET = 256, SCORE_FTARGET = 256;
 inline long up8(long v) { return (v + 7) / 8 * 8; }
 
 // z tiles per chunk that keep a chunk's streamed range within ~2 MB (half an XCD's L2); `images` = 2 when the kernel reads the
@@ -1783,20 +1767,20 @@ inline BwdPlan bwd_plan(int R, int C, int I, int n_items, size_t esize, int stri
     const RtCfg cf = rt_cfg(C, esize);
     const int nw = strip ? 8 : (cf.nwb == 8 ? score_nw(C, esize) : cf.nwb), zb = strip ? 128 : cf.zb;   // strip: pairs of its 64-z tiles
     const int xb = strip ? strip_xb(strip) : 16 * cf.ix * nw;
-    b.y = pick_chunks(xblocks_of(R, xb), n_items, score_target(), zb, l2_tiles_for(C, esize, 2, zb));
+    b.y = pick_chunks(xblocks_of(R, xb), n_items, SCORE_TARGET, zb, l2_tiles_for(C, esize, 2, zb));
     {   // every chunk writes an [R, C] f32 slab that a later kernel sums: keep that side traffic bounded (1M-item tables would
         // otherwise ask for hundreds of chunks)
         const long slab_bytes = (long)xblocks_of(R, xb) * xb * C * 4;
-        const int cap = (int)std::max<long>(score_target() / std::max(1, xblocks_of(R, xb)), (256L << 20) / std::max(1L, slab_bytes));
+        const int cap = (int)std::max<long>(SCORE_TARGET / std::max(1, xblocks_of(R, xb)), (256L << 20) / std::max(1L, slab_bytes));
         if (b.y.nchunk > cap) b.y = pick_chunks(xblocks_of(R, xb), n_items, cap * xblocks_of(R, xb), zb);
     }
-    b.w = pick_chunks(xblocks_of(n_items, xb), R, score_target(), zb);
+    b.w = pick_chunks(xblocks_of(n_items, xb), R, SCORE_TARGET, zb);
     long o = 0;
     auto take = [&](long floats) { const long at = o; o += (floats + 63) / 64 * 64; return at; };
     b.off_rowsT = take(((long)C * up8(R) * (long)esize + 3) / 4);
     b.off_tableT = take(((long)C * up8(I) * (long)esize + 3) / 4);
-    // G workgroups x one [xb, C] tile each (strip: the grid is at least score_target() workgroups, split on the device)
-    const long gy = strip ? std::max<long>((long)b.y.nchunk * xblocks_of(R, xb), score_target()) : (long)b.y.nchunk * xblocks_of(R, xb);
+    // G workgroups x one [xb, C] tile each (strip: the grid is at least SCORE_TARGET workgroups, split on the device)
+    const long gy = strip ? std::max<long>((long)b.y.nchunk * xblocks_of(R, xb), SCORE_TARGET) : (long)b.y.nchunk * xblocks_of(R, xb);
     b.off_slabY = take(gy * xb * C);
     b.off_slabW = take((long)b.w.nchunk * I * C);
     b.off_slabB = take((long)b.w.nchunk * (I - 1));
@@ -1867,7 +1851,7 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
     const int nw = Cfg::NWB == 8 ? score_nw(p.C, sizeof(T)) : Cfg::NWB;
     const size_t smem_nw = nw == 8 ? smem : BUF;
     const int xb = strip ? strip_xb(strip) : 16 * Cfg::IX * nw;
-    const int G = strip ? std::max(xblocks_of(p.R, xb) * plan.y.nchunk, score_target()) : xblocks_of(p.R, xb) * plan.y.nchunk;
+    const int G = strip ? std::max(xblocks_of(p.R, xb) * plan.y.nchunk, SCORE_TARGET) : xblocks_of(p.R, xb) * plan.y.nchunk;
     float* part = ws + plan.off_part;
     // rows finished in one launch (flash_finish_lse_kernel): the strip row pass then leaves bf16 slabs
     const bool one_launch = MODE == 1 && d_rows && (p.C == 128 || p.C == 64 || p.C == 256 || p.C == 512) && p.i0 == 0 && p.i1 == p.I;
@@ -2031,7 +2015,7 @@ extern "C" int edgl_score_chunks(int R, int n_items) {
     long best = 1;   // C is not an argument: take the largest need over the tile shapes of ScoreCfg
     for (int xb : {256, 128})
         for (int zb : {128, 64, 32}) {
-            const long g = (long)xblocks_of(R, xb) * pick_chunks(xblocks_of(R, xb), n_items, score_ftarget(), zb, F_L2_TILES_MIN).nchunk;
+            const long g = (long)xblocks_of(R, xb) * pick_chunks(xblocks_of(R, xb), n_items, SCORE_FTARGET, zb, F_L2_TILES_MIN).nchunk;
             best = std::max(best, (g * xb + R - 1) / R);
         }
     return (int)best;
@@ -2102,7 +2086,7 @@ extern "C" int edgl_score_lse_fwd(const void* rows, const void* table, const flo
     const size_t esize = dtype == EDGL_BF16 ? 2 : 4;
     const RtCfg cf = rt_cfg(C, esize);
     const int xbf = 16 * cf.ix * (SNT / 64);
-    const Chunking ch = pick_chunks(xblocks_of(R, xbf), i1 - i0, score_ftarget(), cf.zb, l2_tiles_for(C, esize, 1, cf.zb));
+    const Chunking ch = pick_chunks(xblocks_of(R, xbf), i1 - i0, SCORE_FTARGET, cf.zb, l2_tiles_for(C, esize, 1, cf.zb));
     p.nchunk = ch.nchunk; p.zchunk = ch.zchunk;
     hipStream_t st = (hipStream_t)stream;
     rc = dtype == EDGL_F32 ? fwd_dispatch<float>(p, C, st) : fwd_dispatch<bf16>(p, C, st);
@@ -2357,7 +2341,7 @@ extern "C" int edgl_mask_topk(float* logits, int R, int n, int i0, const int64_t
                               int32_t* out_idx, void* stream) {
     EDGL_REQUIRE(logits && out_val && out_idx, EDGL_ERR_NULL, "edgl_mask_topk: null pointer");
     EDGL_REQUIRE(R > 0 && n > 0 && K > 0 && K <= 128, EDGL_ERR_SHAPE, "edgl_mask_topk: bad shape R=%d n=%d K=%d", R, n, K);
-    static const int reg_form = getenv("EDGL_TOPK_REG") ? atoi(getenv("EDGL_TOPK_REG")) : 1;
+    static const int reg_form = edgl_env_int("EDGL_TOPK_REG", 1);
     hipStream_t st = (hipStream_t)stream;
     if (reg_form && n <= 256 * 16 - 8) hipLaunchKernelGGL(mask_topk_reg_kernel<16>, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);
     else if (reg_form && n <= 256 * 40 - 8) hipLaunchKernelGGL(mask_topk_reg_kernel<40>, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);

@@ -150,9 +150,6 @@ struct Stage {
         for (int i = 0; i < 5; ++i) load_piece(i);
     }
     __device__ __forceinline__ void store_piece(char* slot, int i) {
-#ifdef STRIP_T_WAITONLY    // (timing experiments only: the staged registers are waited for and consumed, nothing is written)
-        if (z0_ > 128) { const uint4& g = i == 0 ? g0 : (i == 1 ? g1 : (i == 2 ? g2 : g3)); if (i < 4) asm volatile("" ::"v"(g.x), "v"(g.y), "v"(g.z), "v"(g.w)); else asm volatile("" ::"v"(cinfo), "v"(cinfo2)); return; }
-#endif
         if (i < 4) {
             *reinterpret_cast<uint4*>(slot + loff_ + i * 16 * ROWB) = i == 0 ? g0 : (i == 1 ? g1 : (i == 2 ? g2 : g3));
         } else {
@@ -231,11 +228,7 @@ __device__ __forceinline__ void settle_o(f32x16 (&O)[2][4]) {
 //   row sum += T[e-1];  after every odd logit the pair before it is packed
 // slot_tail() finishes the tile (sum / pack of logits 14, 15).
 #define VALU_E0 "v_fma_f32 %[cur], %[cur], %[l2e], %[add]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_exp_f32 %[cur], %[cur]"
-#ifdef STRIP_T_NOSUM      // (timing experiment only: the row sums are not formed — bounds what a sum on the matrix pipe could give)
-#define VALU_ODD "v_exp_f32 %[cur], %[cur]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]"
-#else
 #define VALU_ODD "v_exp_f32 %[cur], %[cur]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_add_f32 %[sum], %[sum], %[p1]"
-#endif
 #define VALU_EVEN VALU_ODD "\n\tv_cvt_pk_bf16_f32 %[pk], %[p2], %[p1]"
 #define VALU_E15 "v_exp_f32 %[cur], %[cur]\n\tv_add_f32 %[sum], %[sum], %[p1]"
 #define MF_S0 "v_mfma_f32_32x32x16_bf16 %[d], %[a], %[b], %[c]\n\t"
@@ -244,11 +237,6 @@ __device__ __forceinline__ void settle_o(f32x16 (&O)[2][4]) {
 template <int KIND>
 __device__ __forceinline__ void slot(f32x16& d, const v4i& a, const v4i& b, const f32x16& c, f32x16& T, int (&pk)[8], float& lsum,
                                      float add, int e) {
-#ifdef STRIP_NOVALU
-    if (KIND == 0) mfma_s0(d, a, b, c); else if (KIND == 1) mfma_s(d, a, b); else mfma_o(d, a, b);
-    if (e & 1) pk[e >> 1] = __builtin_bit_cast(int, T[e]);
-    return;
-#else
     float cur = T[e], nxt = T[e < 15 ? e + 1 : 15];
     int r = 0;
 #define SLOT_ASM(MF, VA, DC, BC)                                                                                                  \
@@ -276,14 +264,11 @@ __device__ __forceinline__ void slot(f32x16& d, const v4i& a, const v4i& b, cons
     T[e] = cur;
     if (e < 15) T[e + 1] = nxt;
     if (e >= 2 && (e & 1) == 0) pk[(e - 2) >> 1] = r;
-#endif
 }
 __device__ __forceinline__ void slot_tail(f32x16& T, int (&pk)[8], float& lsum) {
-#ifndef STRIP_NOVALU
     int r;
     asm volatile("v_add_f32 %0, %0, %2\n\tv_cvt_pk_bf16_f32 %1, %3, %2" : "+v"(lsum), "=&v"(r) : "v"(T[15]), "v"(T[14]));
     pk[7] = r;
-#endif
 }
 
 // One pipeline iteration u: S(u+1) -> Sn, P(u) <- exp of Sc, O += P(u-1) . Z(u-1).
@@ -309,16 +294,8 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[2][4], const v4i (&XF)[2][
     int pk[2][8];
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-#ifndef STRIP_T_NOZF
         if (ks + 3 < 8) zf[(ks + 3) % 4] = lds_b128(s_unit + lo.zf + (ks + 3) * 32);
-#else
-        if (ks == 0) zf[3] = cy.zf0;
-#endif
-#ifndef STRIP_T_NOTF
         if (ks >= 5) tf[ks - 5] = lds_tr(o_unit + lo.tr + (ks - 5) * 64);     // (tile u-1: resident long before this iteration)
-#else
-        if (ks == 6) { tf[0] = cy.zf0; tf[1] = cy.zf1; tf[2] = cy.zf0; tf[3] = cy.zf1; }
-#endif
 #pragma unroll
         for (int xt = 0; xt < 2; ++xt) {
             // (kind 0: slot 0 starts the x tile: VALU_E0; slot 1 is an odd slot)
@@ -329,12 +306,8 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[2][4], const v4i (&XF)[2][
             // it stays an operand of an (empty) statement for two more MFMA pairs.
             if (ks == 1 || ks == 2) asm volatile("" ::"v"(cy.ci));
             const int sl = 2 * ks + xt;                          // one staging piece per slot
-#ifndef STRIP_T_NOSTORE
             if (STAGE && sl >= 4 && sl <= 12 && (sl & 1) == 0) stg.store_piece(st_slot, (sl - 4) >> 1);
-#endif
-#ifndef STRIP_T_NOLOADS
             if (LOAD && sl >= 2 && sl < 7) stg.load_piece(sl - 2);
-#endif
             SPIN();
             if (sl == 3) PHT(STAGE ? 0 : 4);
             if (sl == 12) PHT(STAGE ? 1 : 5);
@@ -342,27 +315,21 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[2][4], const v4i (&XF)[2][
     }
     slot_tail(Sc[0], pk[0], lsum[0]);
     PHT(STAGE ? 2 : 6);
-#ifndef STRIP_T_NOBAR
     // Workgroup barrier behind the staged stores.  Only the stores have to be complete: LDS operations retire in order, so
     // lgkmcnt(2) lets the two youngest ones — the transpose reads of tf[2], issued at ks = 7 behind the last store piece (slot 12)
     // — stay in flight; a full drain exposed their whole latency once per tile.  The count must never exceed the number of LDS
     // operations issued after the last store piece: 2.
     if (STAGE) asm volatile("s_waitcnt lgkmcnt(2)\n\ts_barrier" ::: "memory");
-#endif
     SPIN();
     PHT(STAGE ? 3 : 7);
     // ---- O half: 16 MFMAs beside the 16 logits of x tile 1 --------------------------------------------------------------------
 #pragma unroll
     for (int f = 0; f < 8; ++f) {          // f = ks2 * 4 + ct
         const int ks2 = f >> 2, ct = f & 3;
-#ifndef STRIP_T_NOTF
         if (f + 3 < 8) tf[(f + 3) % 4] = lds_tr(o_unit + lo.tr + ((f + 3) >> 2) * 16 * ROWB + ((f + 3) & 3) * 64);
-#endif
-#ifndef STRIP_T_NOCARRY
         if (f == 4) cy.zf0 = lds_b128(nx_unit + lo.zf);
         if (f == 5) { fetch_ci(cy.ci, nx_info, lo); cy.zf1 = lds_b128(nx_unit + lo.zf + 32); }
         if (f == 6) cy.zf2 = lds_b128(nx_unit + lo.zf + 64);
-#endif
 #pragma unroll
         for (int xt = 0; xt < 2; ++xt) {
             slot<2>(O[xt][ct], Pp[xt][ks2], tf[f % 4], Sc[1], Sc[1], pk[1], lsum[1], add[1], 2 * f + xt);
@@ -731,13 +698,11 @@ __global__ __launch_bounds__(NTHR, 1) void strip_kernel(StripP p) {
             return;
         }
     }
-#ifndef STRIP_TEST_NOFALLBACK
     if (YS) {   // copies: the structs the hot path reads must not be address-taken (they would live in scratch)
         const StripP p2 = p;
         const Geo g2 = g;
         fallback_exact(&p2, &g2, smem);
     }
-#endif
 }
 
 // d_table[label[r]] -= coef[r] rows[r];  d_bias[label[r] - 1] -= coef[r]   over the weighted rows (label != 0): the one-hot part of
@@ -799,7 +764,7 @@ extern "C" void edgl_debug_strip_stamps(void* buf) { g_strip_stamps = (unsigned 
 extern "C" void edgl_debug_strip_phases(unsigned long long* out4) { hipMemcpyFromSymbol(out4, HIP_SYMBOL(strip::g_ph), 384); }
 #endif
 bool edgl_strip_enabled() {
-    static const int on = getenv("EDGL_SCORE_STRIP") ? atoi(getenv("EDGL_SCORE_STRIP")) : 1;
+    static const int on = edgl_env_int("EDGL_SCORE_STRIP", 1);
     return on != 0;
 }
 

@@ -38,19 +38,10 @@ namespace stripw {
 
 constexpr int NTHR = 256, XW = 32, XB = 128, ZU = 32, ZQ = 128;     // ZQ: chunk granularity of the planners
 constexpr int INFOB = 256;                 // one global_load_lds_dword: 64 floats (the unit's 32 + the next unit's, unused)
-#ifndef STRIPW_AHEAD
-#define STRIPW_AHEAD 5
-#endif
-constexpr int AHEAD = STRIPW_AHEAD, NSLOT = AHEAD + 2;     // iteration u issues the loads of unit u + AHEAD; ring slots
+constexpr int AHEAD = 5, NSLOT = AHEAD + 2;     // iteration u issues the loads of unit u + AHEAD; ring slots
 static_assert(AHEAD >= 3 && AHEAD <= 5, "ring of 5 .. 7 units");
 constexpr int CPAD = 512;                  // -inf entries behind the C-operand arrays (units past a chunk's end read them)
-#ifndef STRIPW_PF
-#define STRIPW_PF 6
-#endif
-#ifndef STRIPW_SPREAD
-#define STRIPW_SPREAD 1
-#endif
-constexpr int PF = STRIPW_PF, RING = 8;    // operand prefetch distance (MFMA slots) / ring size
+constexpr int PF = 6, RING = 8;    // operand prefetch distance (MFMA slots) / ring size
 static_assert(PF >= 2 && PF < RING, "operand rings");
 constexpr float L2E = 1.4426950408889634f;
 constexpr float LSUM_LIMIT = 1.2676506e30f;   // 2^100
@@ -143,9 +134,6 @@ struct Dma {
     }
     __device__ __forceinline__ void begin(int z0) { z0_ = z0; }
     __device__ __forceinline__ void piece(unsigned slot_lds, int k) {       // k = 0..3: one block;  k = 4: the C operands (wave 0)
-#if defined(STRIPW_NOSTAGE)
-        return;
-#endif
         if (k < 4) {
             const int gz = max(min(z0_ + 4 * wave_ + k + lrow_, zend_ - 1), 0);
             glds16(Z_ + (long)gz * (CW * 2) + lcol_, slot_lds + boff_[k]);
@@ -261,28 +249,18 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[8], const v4i (&XF)[16], f
     for (int ks = 0; ks < 16; ++ks) {
         if (ks + PF < 16) zf[(ks + PF) % RING] = lds_b128(s_unit + lo.zf + (ks + PF) * 32);
         else { const int f = ks + PF - 16; tf[f % RING] = lds_tr<BLKB>(o_unit + lo.tr + (f >> 3) * 512 + (f & 7) * 64); }
-#if STRIPW_SPREAD
         if (ks == 0) slot<0>(Sn, zf[0], XF[0], cy.ci, Sc, pk, lsum, add, 0);
         else if ((ks & 1) == 0) slot<1>(Sn, zf[ks % RING], XF[ks], cy.ci, Sc, pk, lsum, add, ks >> 1);
         else mfma_s(Sn, zf[ks % RING], XF[ks]);
-#else
-        if (ks == 0) slot<0>(Sn, zf[0], XF[0], cy.ci, Sc, pk, lsum, add, 0);
-        else slot<1>(Sn, zf[ks % RING], XF[ks], cy.ci, Sc, pk, lsum, add, ks);
-#endif
         // SrcC of the ks = 0 MFMA is read late in its passes: nothing may be allocated over `ci` until it is done (16 wait states:
         // the slots without a logit are two instructions long)
         if (ks >= 1 && ks <= 8) asm volatile("" ::"v"(cy.ci));
         SPIN();
     }
-#if !STRIPW_SPREAD
-    slot_tail(Sc, pk, lsum);
-#endif
     // Unit u+2 landed (this wave's share: the loads of units u+3 and u+4 — 2 x 4 — may stay in flight), then the workgroup barrier:
     // everybody's share landed, and everybody is past the O half of iteration u-1 (the slot the loads below overwrite).
     // (LDS reads in flight cross the barrier freely: they target other slots.)
-#ifndef STRIPW_NOBAR
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(4 * (AHEAD - 3)) : "memory");
-#endif
     SPIN();
     // ---- O half: 16 MFMAs; operands of the next S half, the loads of unit u + AHEAD -----------------------------------------------
 #pragma unroll
@@ -292,17 +270,11 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[8], const v4i (&XF)[16], f
         else cy.zf[fn - 16] = lds_b128(nx_unit + lo.zf + (fn - 16) * 32);
         if (f >= 4 && f < 8) fetch_ci_part(cy.ci, nx_unit + Cf::UNITB, lo, f - 4);
         if (f < 10 && (f & 1)) dma.piece(ld_slot, f >> 1);
-#if STRIPW_SPREAD
         if ((f & 1) == 0) slot<2>(O[f & 7], Pp[f >> 3], tf[f % RING], cy.ci, Sc, pk, lsum, add, 8 + (f >> 1));
         else mfma_o(O[f & 7], Pp[f >> 3], tf[f % RING]);
-#else
-        mfma_o(O[f & 7], Pp[f >> 3], tf[f % RING]);
-#endif
         SPIN();
     }
-#if STRIPW_SPREAD
     slot_tail(Sc, pk, lsum);
-#endif
     Pc[0] = v4i{pk[0], pk[1], pk[2], pk[3]};
     Pc[1] = v4i{pk[4], pk[5], pk[6], pk[7]};
     SPIN();
@@ -560,9 +532,6 @@ __global__ __launch_bounds__(NTHR, 1) void stripw_kernel(StripP p) {
             const float s = lsum + __shfl_xor(lsum, 32, 64);
             bad = (g.xbase + g.l31 < g.xend) && !(s < LSUM_LIMIT);
         }
-#ifdef STRIPW_T_NOFALLBACK
-        bad = false;
-#endif
         if (!YS || !__syncthreads_or(bad ? 1 : 0)) {
             epilogue<ROLE, CW>(p, g, smem, O, m2, lsum);
             return;
@@ -977,11 +946,11 @@ __global__ __launch_bounds__(256) void info_rows_kernel(const float* coef, const
 
 // ---- host side (called from k_score.hip) --------------------------------------------------------------------------------------
 bool edgl_stripw_enabled() {
-    static const int on = getenv("EDGL_SCORE_STRIPW") ? atoi(getenv("EDGL_SCORE_STRIPW")) : 1;
+    static const int on = edgl_env_int("EDGL_SCORE_STRIPW", 1);
     return on != 0;
 }
 bool edgl_stripw_supports(int C) {      // 256: stripw_kernel; 512: stripw5_kernel (EDGL_SCORE_STRIPW512=0: the generic kernels, the A/B switch)
-    static const int on512 = getenv("EDGL_SCORE_STRIPW512") ? atoi(getenv("EDGL_SCORE_STRIPW512")) : 1;
+    static const int on512 = edgl_env_int("EDGL_SCORE_STRIPW512", 1);
     return C == 256 || (C == 512 && on512 != 0);
 }
 

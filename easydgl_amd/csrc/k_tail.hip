@@ -51,7 +51,6 @@ struct TailP {
     float *st1, *st2, *st3;
     int dhp, dht;   // channel-padded model (head dim dht stored as dhp, the padded channels all zero): the LayerNorms' moments are
                     // those of the real channels (edgl_tail_fwd_ct); 0, 0: none
-    int stagger;    // t2 kernels: the second half of the grid starts this many s_sleep(127) later (the two workgroups of a CU out of phase)
 };
 
 template <int CT>
@@ -1021,8 +1020,6 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     float* red = reinterpret_cast<float*>(smem + OFF_RED);
     float* par = reinterpret_cast<float*>(smem + OFF_PAR);
     const int b = blockIdx.x, T = p.T;
-    if (p.stagger > 0 && 2 * b >= (int)gridDim.x)
-        for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     const Lane L = make_lane();
     const int n0 = L.wave * 16, nl = L.nl, l15 = L.l15;
     const long row0 = (long)b * T;
@@ -1211,12 +1208,8 @@ __global__ void tail_pack_kernel(const bf16* Wo, const bf16* Wi, const bf16* Wou
 // EDGL_TAIL2=0 / edgl_tail_variant(0): the one-workgroup-per-CU kernels for every shape (A/B switch)
 static int g_tail2 = -1;
 static bool tail2_enabled() {
-    if (g_tail2 < 0) { const char* e = getenv("EDGL_TAIL2"); g_tail2 = (e && e[0] == '0') ? 0 : 1; }
+    if (g_tail2 < 0) g_tail2 = edgl_env_on("EDGL_TAIL2") ? 1 : 0;
     return g_tail2 != 0;
-}
-static int tail2_stagger() {
-    static const int v = [] { const char* e = getenv("EDGL_TAIL2_STAGGER"); return e ? atoi(e) : 0; }();
-    return v;
 }
 extern "C" int edgl_tail_variant(int variant) {
     const int prev = tail2_enabled() ? 1 : 0;
@@ -1257,7 +1250,7 @@ extern "C" int edgl_tail_fwd_ct(const void* att, const void* xin, int ld_x, cons
     const long cc = (long)C * C;
     TailP p{(const bf16*)att, (const bf16*)xin, ld_x, pk, pk + cc, pk + 3 * cc, pk + 5 * cc, bo, bi, bout, bt, g1, b1, g2, b2, g3, b3,
             B, T, C, drop_rate, rng_state, sid1, sid2, masked_pos, M, head, hrow_map, (bf16*)ao, (bf16*)a1, (bf16*)pre_f, (bf16*)f, (bf16*)o,
-            (bf16*)y, (bf16*)pre_t, (bf16*)so, (bf16*)hrows, st1, st2, st3, dh_pad, dh_true, tail2_stagger()};
+            (bf16*)y, (bf16*)pre_t, (bf16*)so, (bf16*)hrows, st1, st2, st3, dh_pad, dh_true};
     hipStream_t st = (hipStream_t)stream;
     const int nrt = (T + 15) / 16;
     if (tail2_enabled() && C == 128 && T <= t2::TMAX) {      // two workgroups per CU (see namespace t2)

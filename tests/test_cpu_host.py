@@ -163,3 +163,23 @@ def test_key_mask_forms_accepted_by_the_attention_units():
             key_ids_from_masks(bad, B, T, h)
     with pytest.raises(TypeError):
         key_ids_from_masks([[1, 2]], B, T, h)
+
+
+def test_library_env_switches_match_the_design_table():
+    """The EDGL_* variables the library reads (through edgl_env* of edgl_common.h, the only place that calls getenv) are exactly the
+    `library` rows of the table in DESIGN.md §9: a switch added or retired in csrc/ without its line there fails here."""
+    csrc = os.path.join(ROOT, "easydgl_amd", "csrc")
+    read, getenv_sites = set(), []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, name)).read()
+        read |= set(re.findall(r'\b(?:edgl_env(?:_int|_on)?|getenv)\s*\(\s*"(EDGL_[A-Z0-9_]+)"', text))
+        getenv_sites += [name] * len(re.findall(r"\bgetenv\b", text))
+    assert getenv_sites == ["edgl_common.h"], getenv_sites
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("## 9. Environment variables"):]
+    rows = [[c.strip() for c in line.strip().strip("|").split("|")] for line in section.splitlines() if line.startswith("| `")]
+    assert rows, "no table rows parsed"
+    table = {v for r in rows if r[1].startswith("library") for v in re.findall(r"`(EDGL_[A-Z0-9_]+)`", r[0])}
+    assert read and read == table, read ^ table

@@ -16,6 +16,10 @@ CASES = {
     "t31": dict(num_units=128, num_heads=8, num_blocks=1, seqslen=30, masklen=6, num_events=16, num_items=700),           # two row tiles
     "t50": dict(num_units=128, num_heads=4, num_blocks=2, seqslen=49, masklen=9, num_events=7, num_items=300),            # four row tiles
     "t97": dict(num_units=128, num_heads=8, num_blocks=1, seqslen=96, masklen=20, num_events=16, num_items=300),          # one row in the last tile
+    # row-tile edges of the t2 forward: T = 16 fills one row tile, T = 17 puts one row into a second, T = 2 is the shortest sequence
+    "t16": dict(num_units=128, num_heads=8, num_blocks=1, seqslen=15, masklen=3, num_events=16, num_items=300),
+    "t17": dict(num_units=128, num_heads=8, num_blocks=1, seqslen=16, masklen=3, num_events=16, num_items=300),
+    "t2": dict(num_units=128, num_heads=8, num_blocks=1, seqslen=1, masklen=1, num_events=16, num_items=300),
     "padded": dict(num_units=100, num_heads=2, num_blocks=2, seqslen=40, masklen=8, num_events=5, num_items=200),         # head dim 50 stored as 64
 }
 
@@ -44,7 +48,7 @@ def _run(prob, batch, drop, variant):
 
 
 @pytest.mark.parametrize("name,drop", [("headline", 0.0), ("headline", 0.1), ("two_blocks", 0.1), ("t31", 0.1), ("t50", 0.0), ("t97", 0.1),
-                                       ("padded", 0.1)])
+                                       ("padded", 0.1), ("t16", 0.1), ("t17", 0.1), ("t2", 0.1)])
 def test_two_per_cu_tail_is_bit_identical_to_the_one_per_cu_kernels(name, drop):
     batch = 9
     prob = make_problem(seed=70 + len(name), batch=batch, **CASES[name])

@@ -1,4 +1,4 @@
-"""Times edgl_gemm / edgl_gemm_dw on the hot-path shapes (HIP events), optionally under EDGL_DBG ablations."""
+"""Times edgl_gemm / edgl_gemm_dw on the hot-path shapes (HIP events)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

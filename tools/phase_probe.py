@@ -1,5 +1,6 @@
 """Diagnostic: per-phase wave cycles of the BiMAU backward kernel (needs a library built with -DEDGL_PHASE_TIMING, see
-k_bimau_bwd.hip; cycles are per wave with the other resident waves of the SIMD competing).  python tools/phase_probe.py path/to/lib_phase.so"""
+k_bimau_bwd.hip; cycles are per wave with the other resident waves of the SIMD competing).
+  bash tools/build_variant.sh phase_k_bimau_bwd -DEDGL_PHASE_TIMING k_bimau_bwd -> python tools/phase_probe.py tools/variants/lib_phase_k_bimau_bwd.so"""
 import ctypes
 import os
 import shutil

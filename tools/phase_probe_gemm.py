@@ -1,5 +1,6 @@
 """Diagnostic: per-phase wave cycles of strip_gemm_kernel on the headline QKVT projection (library built with
--DEDGL_PHASE_TIMING for k_gemm2.hip).  python tools/phase_probe_gemm.py path/to/lib.so [M K N b_kc]"""
+-DEDGL_PHASE_TIMING for k_gemm2.hip).
+  bash tools/build_variant.sh phase_k_gemm2 -DEDGL_PHASE_TIMING k_gemm2 -> python tools/phase_probe_gemm.py tools/variants/lib_phase_k_gemm2.so [M K N b_kc]"""
 import ctypes
 import os
 import shutil

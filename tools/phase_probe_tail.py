@@ -1,6 +1,8 @@
 """Diagnostic: per-phase wave cycles of the fused tail kernels at the headline shape.  Library variants:
-  forward : tools/build_phase_variant.sh k_tail                      -> python tools/phase_probe_tail.py variants/lib_phase_k_tail.so
-  backward: EXTRA=-DEDGL_PHASE_BWD tools/build_phase_variant.sh k_tail -> python tools/phase_probe_tail.py variants/lib_phase_k_tail.so bwd"""
+  forward : bash tools/build_variant.sh phase_k_tail -DEDGL_PHASE_TIMING k_tail
+            -> python tools/phase_probe_tail.py tools/variants/lib_phase_k_tail.so
+  backward: bash tools/build_variant.sh phase_k_tail_bwd "-DEDGL_PHASE_TIMING -DEDGL_PHASE_BWD" k_tail
+            -> python tools/phase_probe_tail.py tools/variants/lib_phase_k_tail_bwd.so bwd"""
 import ctypes
 import os
 import shutil

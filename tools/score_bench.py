@@ -28,4 +28,4 @@ def bwd():
                                 _ptr(d_rows), _ptr(d_tab), _ptr(d_bias), _ptr(ws), 1, _stream()))
 t_b = timeit(bwd)
 gf = 2.0 * R * C * I / 1e9
-print(f"EDGL_DBG={os.environ.get('EDGL_DBG','0'):>2s}  fwd {t_f:7.1f} us ({gf/t_f*1e6/1e3:6.0f} TF)   bwd(dy+dw) {t_b:7.1f} us ({4*gf/t_b*1e6/1e3:6.0f} TF)")
+print(f"fwd {t_f:7.1f} us ({gf/t_f*1e6/1e3:6.0f} TF)   bwd(dy+dw) {t_b:7.1f} us ({4*gf/t_b*1e6/1e3:6.0f} TF)")

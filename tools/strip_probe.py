@@ -1,4 +1,4 @@
-"""Per-phase shader-clock stamps of the strip scoring kernels (a -DSTRIP_TIMING build: tools/build_strip_variant.sh timing -DSTRIP_TIMING):
+"""Per-phase shader-clock stamps of the strip scoring kernels (a -DSTRIP_TIMING build: bash tools/build_variant.sh timing -DSTRIP_TIMING k_score_strip):
     EDGL_LIB_PATH=tools/variants/lib_timing.so python tools/strip_probe.py
 Prints, per role, mean / max over the workgroups of: x fragments, prologue, main loop (and cycles per MFMA slot), drain, epilogue."""
 import ctypes

@@ -7,10 +7,7 @@ OUT=$ROOT/gpurun_out/sweep
 mkdir -p "$OUT"
 cd "$ROOT"
 REPS=${1:-3}
-CFGS=("base=1" "EDGL_TN_GROUP_TARGET=384" "EDGL_TN_GROUP_TARGET=448" "EDGL_TN_GROUP_TARGET=576" "EDGL_TN_GROUP_TARGET=640" "EDGL_TN_GROUP_TARGET=768"
-      "EDGL_SCORE_TARGET=240" "EDGL_SCORE_TARGET=248" "EDGL_SCORE_TARGET=264" "EDGL_SCORE_TARGET=512" "EDGL_SCORE_FTARGET=240" "EDGL_SCORE_FTARGET=248" "EDGL_SCORE_FTARGET=512"
-      "EDGL_TAIL2=0" "EDGL_TAIL2_STAGGER=1" "EDGL_BIMAU_ORDER=1" "EDGL_ADAM_EX=0" "EDGL_PREP_IN_ENCODER=0" "EDGL_XCD_ORDER=0" "EDGL_TPP_FUSED=0"
-      "EDGL_CE_PARTS=0")
+CFGS=("base=1" "EDGL_TAIL2=0" "EDGL_BIMAU_ORDER=1" "EDGL_ADAM_EX=0" "EDGL_PREP_IN_ENCODER=0" "EDGL_TPP_FUSED=0" "EDGL_CE_PARTS=0")
 : > "$OUT/raw.txt"
 for rep in $(seq 1 "$REPS"); do
   for cfg in "${CFGS[@]}"; do

@@ -1,6 +1,6 @@
 """On the GPU box: engine step time of the headline workload with overrides, e.g.
    python tools/try_shape.py num_units=256 num_items=20000 [steps=100]
-(A/B of library switches at shapes bench.py has no row for: EDGL_SCORE_NW=4 python tools/try_shape.py num_units=256 ...)"""
+(A/B of library switches or of library variants (EDGL_LIB_PATH) at shapes bench.py has no row for)"""
 import sys
 sys.path.insert(0, ".")
 import torch  # noqa: E402
