@@ -30,7 +30,8 @@ inline int big_row_splits(int dh, int E) {
 
 // workspace of edgl_bimau_bwd: dz [R,16] | dH partial slabs | row term [R] | dscaling partials | weight-gradient partials
 struct WsLayout { size_t dz, dh, rowdot, dsc, wpart, total; };
-inline WsLayout ws_layout(int B, int T_, int C, int H, int E) {
+// dsc_rows: rows of the dscaling partials (0: one per (sample, head) job; the key-streamed sweep 1 leaves one per job and query tile)
+inline WsLayout ws_layout(int B, int T_, int C, int H, int E, long dsc_rows = 0) {
     const int dh = C / H;
     const bool big = dh >= 64;
     const size_t R = (size_t)B * H * T_;
@@ -40,7 +41,7 @@ inline WsLayout ws_layout(int B, int T_, int C, int H, int E) {
     w.dz = take(R * EP * sizeof(float));
     w.dh = take((size_t)(big ? 1 : KY_NY) * R * dh * sizeof(float));
     w.rowdot = take(R * sizeof(float));
-    w.dsc = take((size_t)B * H * EP * sizeof(float));
+    w.dsc = take((size_t)(dsc_rows > 0 ? dsc_rows : (long)B * H) * EP * sizeof(float));
     w.wpart = take((size_t)(big ? big_row_splits(dh, E) : KY_BLOCKS) * ((size_t)(dh + 3) * dh * E + EP) * sizeof(float));
     w.total = o;
     return w;
@@ -685,6 +686,33 @@ __global__ __launch_bounds__(256) void bimau_bwd_sweep2_kernel(BwdP p) {
 #endif
 }
 
+
+// the workspace of a form (bimau_common.h: bimau_form)
+inline WsLayout ws_layout_form(int B, int T_, int C, int H, int E, int form) {
+    return ws_layout(B, T_, C, H, E, form == 1 ? (long)B * H * ((T_ + 15) / 16) : 0);
+}
+
+// parameter gradients from the `nparts` partial rows the intensity backward left in wpart (fixed order: edgl_reduce_rows)
+inline int reduce_wparts(const float* wpart, int nparts, int dh, int E, float* dW1, float* db1, float* dw, float* dscaling, hipStream_t st) {
+    const int JE = dh * E, NPAR = (dh + 3) * JE, NPARX = NPAR + EP;
+    if (db1 == dW1 + (dh + 1) * JE && dw == db1 + JE && dscaling == dw + JE)   // flat-arena layout: one reduction
+        return edgl_reduce_rows(wpart, nparts, NPAR + E, NPARX, dW1, 0, st);
+    int rc = edgl_reduce_rows(wpart, nparts, (dh + 1) * JE, NPARX, dW1, 0, st);
+    if (rc) return rc;
+    rc = edgl_reduce_rows(wpart + (dh + 1) * JE, nparts, JE, NPARX, db1, 0, st);
+    if (rc) return rc;
+    rc = edgl_reduce_rows(wpart + (dh + 2) * JE, nparts, JE, NPARX, dw, 0, st);
+    if (rc) return rc;
+    return edgl_reduce_rows(wpart + NPAR, nparts, E, NPARX, dscaling, 0, st);
+}
+
+// The row-wise middle stage of the backward on its own, for the key-streamed form (k_bimau_stream.hip): the intensity backward
+// kernels over the dz / H rows of p (workspace pointers set), reading `dsc_rows` rows of dscaling partials, then the parameter
+// reductions.  Head dims 16 / 32: k_bimau_bwd.hip; 64 / 128: k_bimau_big.hip.
+int intensity_bwd_small(const BwdP& p, long dsc_rows, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st);
+int intensity_bwd_big(const BwdP& p, long dsc_rows, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st);
+// key-streamed backward (k_bimau_stream.hip); stats: the row statistics region of `saved`
+int stream_bwd(const BwdP& p, const float* stats, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st);
 
 // head dims 64 / 128 (k_bimau_big.hip)
 int big_bwd(const BwdP& p, char* ws, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st);

@@ -117,6 +117,41 @@ inline SavedLayout saved_layout(int B, int T, int C, int H, size_t esize) {
     return s;
 }
 
+// The key-streamed form (k_bimau_stream.hip) keeps, behind the two regions above, the softmax statistics of every row: f32 [H*B*T, 2]
+// = (row maximum of the log2-scaled masked scores, 1 / sum of exp2(score - maximum)) — its values phase and its backward sweeps form
+// P from them instead of running a second online pass.
+struct SavedLayoutStream { size_t off_hin, off_z, off_stats, bytes; };
+inline SavedLayoutStream saved_layout_stream(int B, int T, int C, int H, size_t esize) {
+    const SavedLayout b = saved_layout(B, T, C, H, esize);
+    SavedLayoutStream s;
+    s.off_hin = b.off_hin; s.off_z = b.off_z;
+    s.off_stats = (b.bytes + 255) & ~(size_t)255;
+    s.bytes = s.off_stats + (size_t)B * H * T * 2 * sizeof(float);
+    return s;
+}
+
+// Which kernel family takes a shape (edgl_bimau_form): 0 = the in-register kernels (one instance per key-tile count; bounds of
+// DESIGN.md "Known limits": registers and the wave-private LDS images), 1 = the key-streamed kernels (any T <= STREAM_MAX_T; forced at an
+// in-register shape by EDGL_MAU_STREAM), negative = unsupported.  Decided by (T, head dim, dtype) alone, so that the size queries
+// and the launches of a forward / backward pair agree.
+constexpr int STREAM_MAX_T = 1024;   // the bound of the TPP row kernels and the static engine
+inline int bimau_form(int T, int C, int H, int dtype, int flags) {
+    if (T <= 0 || H <= 0 || C <= 0 || C % H) return EDGL_ERR_SHAPE;
+    if (dtype != EDGL_F32 && dtype != EDGL_BF16) return EDGL_ERR_DTYPE;
+    const int dh = C / H;
+    const bool h = dtype == EDGL_BF16;
+    int tmax;
+    switch (dh) {
+        case 16: tmax = 208; break;
+        case 32: tmax = h ? 208 : 128; break;
+        case 64: tmax = h ? 128 : 112; break;
+        case 128: tmax = h ? 128 : 64; break;
+        default: return EDGL_ERR_SHAPE;
+    }
+    if (T > STREAM_MAX_T) return EDGL_ERR_SHAPE;
+    return (T > tmax || (flags & EDGL_MAU_STREAM)) ? 1 : 0;
+}
+
 template <typename T>
 __global__ void pack_kernel(const float* W1, const float* b1, const float* w, const float* scaling, int dh, int E,
                             char* pack) {

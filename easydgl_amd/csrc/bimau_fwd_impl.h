@@ -452,5 +452,9 @@ int dispatch_nt(FwdP p, hipStream_t st) {
 
 // head dims 64 / 128 (k_bimau_big.hip): scores phase -> intensity kernel -> values phase
 int big_fwd(const FwdP& p, int dtype, hipStream_t st);
+// the row-tile intensity forward of k_bimau_big.hip at any head dim (H rows of p.hin_out -> p.z_out, p.lam), for the key-streamed form
+int intensity_fwd_rows(const FwdP& p, int dtype, hipStream_t st);
+// key-streamed forward (k_bimau_stream.hip): scores phase -> intensity_fwd_rows -> values phase; stats: the row statistics region of `saved`
+int stream_fwd(const FwdP& p, float* stats, int dtype, hipStream_t st);
 
 }  // namespace bimau

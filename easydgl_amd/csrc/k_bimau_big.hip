@@ -485,6 +485,32 @@ int fwd_big(FwdP p, hipStream_t st) {
     return launch_fwd_e<T, DT, NT, 0, 2>(p, st);          // values
 }
 
+// Y stage of the backward: dH rows, then the weight-gradient partials (wpart: big_row_splits rows).  dsc_rows: rows of dscaling
+// partials sweep 1 left in p.dsc_part.
+template <typename T, int DT>
+int run_intensity_bwd_big(const BwdP& p, long dsc_rows, hipStream_t st) {
+    constexpr int dh = 16 * DT;
+    const long jobs = (long)p.B * p.H;
+    const int JE = dh * p.E;
+    const int RS = big_row_splits(dh, p.E);
+    IntP ip{};
+    ip.hin = p.hin; ip.spans = p.spans; ip.pack = p.pack; ip.dz = p.dz_ws; ip.R = (long)p.B * p.H * p.T; ip.B = p.B; ip.T = p.T;
+    ip.E = p.E; ip.dh_out = p.dh_ws; ip.wpart = p.wpart; ip.dsc_part = p.dsc_part; ip.njobs = dsc_rows;
+    const long ntile = jobs * ((p.T + 15) / 16);
+    const size_t smem_r = (size_t)MarkChunk<T, DT, true>::BYTES * (big_double_buffer<T, DT>() ? 2 : 1);
+    auto kr = intensity_bwd_rows_big_kernel<T, DT>;
+    hipFuncSetAttribute((const void*)kr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r);
+    hipLaunchKernelGGL(kr, dim3(row_blocks(ntile, 8)), dim3(256), smem_r, st, ip);
+    EDGL_LAUNCH_CHECK();
+    constexpr int NC = WGroup<DT>::NJ * 16;
+    const size_t smem_w = (size_t)NC * (dh + 4) * sizeof(T) + (size_t)(3 * NC + (dh + 3) * NC) * sizeof(float);
+    auto kw = intensity_bwd_weights_big_kernel<T, DT>;
+    hipFuncSetAttribute((const void*)kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_w);
+    hipLaunchKernelGGL(kw, dim3(RS, (JE + NC - 1) / NC), dim3(256), smem_w, st, ip);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
 template <typename T, int DT, int NT>
 int bwd_big(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling, hipStream_t st) {
     constexpr int dh = 16 * DT, Tp = 16 * NT, LDT = Tp + 4;
@@ -507,24 +533,9 @@ int bwd_big(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling
         hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         EDGL_LAUNCH_CHECK();
     }
-    const int JE = dh * p.E, NPAR = (dh + 3) * JE, NPARX = NPAR + EP;
-    const int RS = big_row_splits(dh, p.E);
     {   // Y: dH rows, then weight-gradient partials
-        IntP ip{};
-        ip.hin = p.hin; ip.spans = p.spans; ip.pack = p.pack; ip.dz = p.dz_ws; ip.R = (long)p.B * p.H * p.T; ip.B = p.B; ip.T = p.T;
-        ip.E = p.E; ip.dh_out = p.dh_ws; ip.wpart = p.wpart; ip.dsc_part = p.dsc_part; ip.njobs = jobs;
-        const long ntile = jobs * ((p.T + 15) / 16);
-        const size_t smem_r = (size_t)MarkChunk<T, DT, true>::BYTES * (big_double_buffer<T, DT>() ? 2 : 1);
-        auto kr = intensity_bwd_rows_big_kernel<T, DT>;
-        hipFuncSetAttribute((const void*)kr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r);
-        hipLaunchKernelGGL(kr, dim3(row_blocks(ntile, 8)), dim3(256), smem_r, st, ip);
-        EDGL_LAUNCH_CHECK();
-        constexpr int NC = WGroup<DT>::NJ * 16;
-        const size_t smem_w = (size_t)NC * (dh + 4) * sizeof(T) + (size_t)(3 * NC + (dh + 3) * NC) * sizeof(float);
-        auto kw = intensity_bwd_weights_big_kernel<T, DT>;
-        hipFuncSetAttribute((const void*)kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_w);
-        hipLaunchKernelGGL(kw, dim3(RS, (JE + NC - 1) / NC), dim3(256), smem_w, st, ip);
-        EDGL_LAUNCH_CHECK();
+        const int rc = run_intensity_bwd_big<T, DT>(p, jobs, st);
+        if (rc) return rc;
     }
     {   // Z: sweep 2
         const size_t wave_bytes = (3 * (size_t)Tp * dh + (size_t)Tp * EP + (TR ? 0 : (size_t)dh * LDT)) * sizeof(T) + (size_t)Tp * sizeof(float);
@@ -552,15 +563,7 @@ int bwd_big(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling
         edgl_prof_end(EDGL_KERNEL_BIMAU_BWD_ALL, st);
         EDGL_LAUNCH_CHECK();
     }
-    if (db1 == dW1 + (dh + 1) * JE && dw == db1 + JE && dscaling == dw + JE)   // flat-arena layout: one reduction
-        return edgl_reduce_rows(p.wpart, RS, NPAR + p.E, NPARX, dW1, 0, st);
-    int rc = edgl_reduce_rows(p.wpart, RS, (dh + 1) * JE, NPARX, dW1, 0, st);
-    if (rc) return rc;
-    rc = edgl_reduce_rows(p.wpart + (dh + 1) * JE, RS, JE, NPARX, db1, 0, st);
-    if (rc) return rc;
-    rc = edgl_reduce_rows(p.wpart + (dh + 2) * JE, RS, JE, NPARX, dw, 0, st);
-    if (rc) return rc;
-    return edgl_reduce_rows(p.wpart + NPAR, RS, p.E, NPARX, dscaling, 0, st);
+    return reduce_wparts(p.wpart, big_row_splits(dh, p.E), dh, p.E, dW1, db1, dw, dscaling, st);
 }
 
 // Head dims 64 and 128: T <= 128 (8 key tiles) in bf16.  The per-(b, head) accumulators dK, dT_ of sweep 2 are DT * NT register
@@ -623,5 +626,27 @@ int big_fwd(const FwdP& p, int dtype, hipStream_t st) {
 }
 int big_bwd(const BwdP& p, char* ws, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st) {
     return dtype == EDGL_F32 ? bwd_dispatch<float>(p, ws, dW1, db1, dw, dsc, st) : bwd_dispatch<bf16>(p, ws, dW1, db1, dw, dsc, st);
+}
+// the row-wise stages on their own (key-streamed form, k_bimau_stream.hip)
+int intensity_fwd_rows(const FwdP& p, int dtype, hipStream_t st) {
+    const bool f = dtype == EDGL_F32;
+    switch (p.C / p.H) {
+        case 16: return f ? run_intensity_fwd<float, 1>(p, st) : run_intensity_fwd<bf16, 1>(p, st);
+        case 32: return f ? run_intensity_fwd<float, 2>(p, st) : run_intensity_fwd<bf16, 2>(p, st);
+        case 64: return f ? run_intensity_fwd<float, 4>(p, st) : run_intensity_fwd<bf16, 4>(p, st);
+        case 128: return f ? run_intensity_fwd<float, 8>(p, st) : run_intensity_fwd<bf16, 8>(p, st);
+    }
+    edgl_set_error("edgl_bimau_fwd: head dim %d not supported (16, 32, 64 or 128)", p.C / p.H);
+    return EDGL_ERR_SHAPE;
+}
+int intensity_bwd_big(const BwdP& p, long dsc_rows, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st) {
+    const bool f = dtype == EDGL_F32;
+    const int dh = p.C / p.H;
+    int rc;
+    if (dh == 64) rc = f ? run_intensity_bwd_big<float, 4>(p, dsc_rows, st) : run_intensity_bwd_big<bf16, 4>(p, dsc_rows, st);
+    else if (dh == 128) rc = f ? run_intensity_bwd_big<float, 8>(p, dsc_rows, st) : run_intensity_bwd_big<bf16, 8>(p, dsc_rows, st);
+    else { edgl_set_error("edgl_bimau_bwd: head dim %d has no streamed-weights intensity backward (64 or 128)", dh); return EDGL_ERR_SHAPE; }
+    if (rc) return rc;
+    return reduce_wparts(p.wpart, big_row_splits(dh, p.E), dh, p.E, dW1, db1, dw, dsc, st);
 }
 }  // namespace bimau

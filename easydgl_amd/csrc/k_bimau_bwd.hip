@@ -375,6 +375,27 @@ size_t intensity_bwd_lds(int dh, int E) {
     return pack_dims<T>(dh, E).bytes + ((size_t)((NACC + 3) & ~3) + 4 * (16 * KY_ECH + 16)) * sizeof(float);
 }
 
+// Y: the intensity MLP backward over all rows of p (wpart: KY_BLOCKS partial rows).  dsc_rows: rows of dscaling partials sweep 1
+// left in p.dsc_part.
+template <typename T, int DT>
+int launch_intensity_bwd(const BwdP& p, long dsc_rows, hipStream_t st) {
+    constexpr int dh = 16 * DT;
+    MlpP mp{p.hin, p.dz_ws, p.spans, p.pack, (long)p.B * p.H * p.T, p.B, p.T, p.E, p.dh_ws, p.wpart, p.dsc_part, dsc_rows, 0};
+    size_t smem_b = intensity_bwd_lds<T>(dh, p.E);
+    const size_t slab_b = (size_t)4 * intensity_bwd_nreg<T>(DT) * 64 * sizeof(float);
+    mp.slab_epi = slab_b <= std::max(smem_b, (size_t)52 * 1024);   // (three workgroups per CU stay resident up to 53 KB)
+    if (mp.slab_epi) smem_b = std::max(smem_b, slab_b);
+    EDGL_REQUIRE(smem_b <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_bimau_bwd: intensity kernel needs %zu B of LDS", smem_b);
+    EDGL_REQUIRE((long)p.B * p.H * p.T < (1l << 31) - 16, EDGL_ERR_SHAPE, "edgl_bimau_bwd: B*H*T = %ld rows exceed the 32-bit row index", (long)p.B * p.H * p.T);
+    // (a compile-time mark count — no guards around the mark blocks — lets the scheduler hoist the LDS operand reads of all eight
+    //  blocks: 168 registers no longer hold them, 25-37 spilled inside the tile loop, 81 -> 180 us.  Run-time E it is.)
+    auto kb = intensity_bwd_kernel<T, DT, 0>;
+    hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b);
+    hipLaunchKernelGGL(kb, dim3(KY_BLOCKS, KY_NY), dim3(256), smem_b, st, mp);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
 template <typename T, int DT, int NT>
 int launch_bwd(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling, hipStream_t st) {
     constexpr int dh = 16 * DT, Tp = 16 * NT, LDT = Tp + 4;
@@ -417,19 +438,8 @@ int launch_bwd(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscal
     }
     // ---- Y ----
     {
-        MlpP mp{p.hin, p.dz_ws, p.spans, p.pack, (long)p.B * p.H * p.T, p.B, p.T, p.E, p.dh_ws, p.wpart, p.dsc_part, jobs, 0};
-        size_t smem_b = intensity_bwd_lds<T>(dh, p.E);
-        const size_t slab_b = (size_t)4 * intensity_bwd_nreg<T>(DT) * 64 * sizeof(float);
-        mp.slab_epi = slab_b <= std::max(smem_b, (size_t)52 * 1024);   // (three workgroups per CU stay resident up to 53 KB)
-        if (mp.slab_epi) smem_b = std::max(smem_b, slab_b);
-        EDGL_REQUIRE(smem_b <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_bimau_bwd: intensity kernel needs %zu B of LDS", smem_b);
-        EDGL_REQUIRE((long)p.B * p.H * p.T < (1l << 31) - 16, EDGL_ERR_SHAPE, "edgl_bimau_bwd: B*H*T = %ld rows exceed the 32-bit row index", (long)p.B * p.H * p.T);
-        // (a compile-time mark count — no guards around the mark blocks — lets the scheduler hoist the LDS operand reads of all eight
-        //  blocks: 168 registers no longer hold them, 25-37 spilled inside the tile loop, 81 -> 180 us.  Run-time E it is.)
-        auto kb = intensity_bwd_kernel<T, DT, 0>;
-        hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b);
-        hipLaunchKernelGGL(kb, dim3(KY_BLOCKS, KY_NY), dim3(256), smem_b, st, mp);
-        EDGL_LAUNCH_CHECK();
+        const int rc = launch_intensity_bwd<T, DT>(p, jobs, st);
+        if (rc) return rc;
     }
     // ---- Z ----
     {
@@ -457,19 +467,7 @@ int launch_bwd(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscal
         edgl_prof_end(EDGL_KERNEL_BIMAU_BWD_ALL, st);
         EDGL_LAUNCH_CHECK();
     }
-    const int JE = dh * p.E, NPAR = (dh + 3) * JE, NPARX = NPAR + EP;
-    if (db1 == dW1 + (dh + 1) * JE && dw == db1 + JE && dscaling == dw + JE) {   // flat-arena layout: one reduction
-        return edgl_reduce_rows(p.wpart, KY_BLOCKS, NPAR + p.E, NPARX, dW1, 0, st);
-    }
-    int rc = edgl_reduce_rows(p.wpart, KY_BLOCKS, (dh + 1) * JE, NPARX, dW1, 0, st);
-    if (rc) return rc;
-    rc = edgl_reduce_rows(p.wpart + (dh + 1) * JE, KY_BLOCKS, JE, NPARX, db1, 0, st);
-    if (rc) return rc;
-    rc = edgl_reduce_rows(p.wpart + (dh + 2) * JE, KY_BLOCKS, JE, NPARX, dw, 0, st);
-    if (rc) return rc;
-    rc = edgl_reduce_rows(p.wpart + NPAR, KY_BLOCKS, p.E, NPARX, dscaling, 0, st);
-    if (rc) return rc;
-    return EDGL_OK;
+    return reduce_wparts(p.wpart, KY_BLOCKS, dh, p.E, dW1, db1, dw, dscaling, st);
 }
 
 template <typename T, int DT>
@@ -495,10 +493,28 @@ int dispatch_nt(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dsc,
 
 }  // namespace
 
-extern "C" long edgl_bimau_bwd_workspace(int B, int T, int C, int H, int E, int dtype) {
-    (void)dtype;
+namespace bimau {
+int intensity_bwd_small(const BwdP& p, long dsc_rows, float* dW1, float* db1, float* dw, float* dsc, int dtype, hipStream_t st) {
+    const bool f = dtype == EDGL_F32;
+    const int dh = p.C / p.H;
+    int rc;
+    if (dh == 16) rc = f ? launch_intensity_bwd<float, 1>(p, dsc_rows, st) : launch_intensity_bwd<bf16, 1>(p, dsc_rows, st);
+    else if (dh == 32) rc = f ? launch_intensity_bwd<float, 2>(p, dsc_rows, st) : launch_intensity_bwd<bf16, 2>(p, dsc_rows, st);
+    else { edgl_set_error("edgl_bimau_bwd: head dim %d has no weights-in-LDS intensity backward (16 or 32)", dh); return EDGL_ERR_SHAPE; }
+    if (rc) return rc;
+    return reduce_wparts(p.wpart, KY_BLOCKS, dh, p.E, dW1, db1, dw, dsc, st);
+}
+}  // namespace bimau
+
+// Workspace of the form that (T, C, H, dtype, flags) selects (edgl_bimau_form).  Without EDGL_MAU_STREAM a shape of the in-register
+// kernels gets exactly the in-register layout; the key-streamed form keeps one row of dscaling partials per job AND query tile.
+extern "C" long edgl_bimau_bwd_workspace_ex(int B, int T, int C, int H, int E, int dtype, int flags) {
     if (H <= 0 || C % H) return -1;
-    return (long)ws_layout(B, T, C, H, E).total;
+    const int form = bimau::bimau_form(T, C, H, dtype == EDGL_BF16 ? EDGL_BF16 : EDGL_F32, flags);
+    return (long)ws_layout_form(B, T, C, H, E, form).total;
+}
+extern "C" long edgl_bimau_bwd_workspace(int B, int T, int C, int H, int E, int dtype) {
+    return edgl_bimau_bwd_workspace_ex(B, T, C, H, E, dtype, 0);
 }
 
 // Largest mark count (<= 16) one launch of the fused unit takes at this head dim and dtype — what a caller with more mark types
@@ -558,6 +574,21 @@ static int bimau_bwd_impl(const void* qkvt, const int64_t* ids, const float* spa
     hipStream_t st = (hipStream_t)stream;
     const int dh = C / H;
     char* ws = (char*)workspace;
+    const int form = bimau::bimau_form(T, C, H, dtype, flags);
+    p.flags = flags & ~EDGL_MAU_STREAM;
+    if (form < 0) {
+        edgl_set_error("edgl_bimau_bwd: head dim %d with T=%d not supported (head dims 16, 32, 64 or 128; T <= %d)", dh, T, bimau::STREAM_MAX_T);
+        return EDGL_ERR_SHAPE;
+    }
+    if (form == 1) {   // the key-streamed kernels (k_bimau_stream.hip): every shape beyond the in-register bounds, or EDGL_MAU_STREAM
+        EDGL_REQUIRE(!tpp_desc, EDGL_ERR_SHAPE, "edgl_bimau_bwd_tpp: the fused TPP form does not exist on the key-streamed path (T=%d, T <= 128)", T);
+        const WsLayout wl = ws_layout_form(B, T, C, H, E, 1);
+        p.dz_ws = reinterpret_cast<float*>(ws + wl.dz); p.dh_ws = reinterpret_cast<float*>(ws + wl.dh);
+        p.rowdot_ws = reinterpret_cast<float*>(ws + wl.rowdot);
+        p.dsc_part = reinterpret_cast<float*>(ws + wl.dsc); p.wpart = reinterpret_cast<float*>(ws + wl.wpart);
+        const bimau::SavedLayoutStream ss = bimau::saved_layout_stream(B, T, C, H, dtype == EDGL_BF16 ? 2 : 4);
+        return bimau::stream_bwd(p, reinterpret_cast<const float*>((const char*)saved + ss.off_stats), dW1, db1, dw, dscaling, dtype, st);
+    }
     if (dtype == EDGL_F32) {
         if (dh == 16) return dispatch_nt<float, 1>(p, ws, dW1, db1, dw, dscaling, st);
         if (dh == 32) return dispatch_nt<float, 2>(p, ws, dW1, db1, dw, dscaling, st);

@@ -21,9 +21,19 @@ extern "C" long edgl_bimau_pack_bytes(int C, int H, int E, int dtype) {
     return (long)(dtype == EDGL_BF16 ? bimau::pack_dims<bf16>(dh, E).bytes : bimau::pack_dims<float>(dh, E).bytes);
 }
 
-extern "C" long edgl_bimau_saved_bytes(int B, int T, int C, int H, int dtype) {
+// 0: the in-register kernels take the shape, 1: the key-streamed kernels (k_bimau_stream.hip), negative: unsupported.  Host only.
+extern "C" int edgl_bimau_form(int T, int C, int H, int dtype, int flags) {
+    return bimau::bimau_form(T, C, H, dtype, flags);
+}
+// `saved` of the form that (T, C, H, dtype, flags) selects: the key-streamed form adds the row statistics (bimau_common.h)
+extern "C" long edgl_bimau_saved_bytes_ex(int B, int T, int C, int H, int dtype, int flags) {
     if (H <= 0 || C % H) return -1;
-    return (long)bimau::saved_layout(B, T, C, H, dtype == EDGL_BF16 ? 2 : 4).bytes;
+    const size_t es = dtype == EDGL_BF16 ? 2 : 4;
+    if (bimau::bimau_form(T, C, H, dtype == EDGL_BF16 ? EDGL_BF16 : EDGL_F32, flags) == 1) return (long)bimau::saved_layout_stream(B, T, C, H, es).bytes;
+    return (long)bimau::saved_layout(B, T, C, H, es).bytes;
+}
+extern "C" long edgl_bimau_saved_bytes(int B, int T, int C, int H, int dtype) {
+    return edgl_bimau_saved_bytes_ex(B, T, C, H, dtype, 0);
 }
 
 extern "C" int edgl_bimau_pack(const float* W1, const float* b1, const float* w, const float* scaling, int C, int H,
@@ -191,10 +201,34 @@ extern "C" int edgl_bimau_fwd_ord(const void* qkvt, const void* resid, int ld_re
     EDGL_REQUIRE(drop_rate == 0.f || rng_state, EDGL_ERR_NULL, "edgl_bimau_fwd: dropout without rng_state");
     EDGL_REQUIRE(ld_res % 4 == 0, EDGL_ERR_SHAPE, "edgl_bimau_fwd: ld_res must be a multiple of 4");
     EDGL_REQUIRE((double)B * H * T * T < 4294967296.0, EDGL_ERR_SHAPE, "edgl_bimau_fwd: H*B*T*T must be < 2^32");
+    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_bimau_fwd: bad dtype %d", dtype);
+    const int form = bimau::bimau_form(T, C, H, dtype, flags);
+    flags &= ~EDGL_MAU_STREAM;
     FwdP p{qkvt, resid, ld_res, ids, spans, marks, (const char*)pack, B, T, C, H, E, drop_rate, rng_state, stream_id,
            out, lam_out, nullptr, nullptr, nullptr, 4, flags & ~EDGL_MAU_NO_SKIP, dropbits, qk_scale, order, (flags & EDGL_MAU_NO_SKIP) ? 1 : 0};
     flags &= ~EDGL_MAU_NO_SKIP;
     hipStream_t st = (hipStream_t)stream;
+    if (form < 0) {
+        edgl_set_error("edgl_bimau_fwd: head dim %d with T=%d not supported (head dims 16, 32, 64 or 128; T <= %d)", C / H, T, bimau::STREAM_MAX_T);
+        return EDGL_ERR_SHAPE;
+    }
+    if (form == 1) {   // the key-streamed kernels (k_bimau_stream.hip): every shape beyond the in-register bounds, or EDGL_MAU_STREAM
+        if (zero_rows && hipMemsetAsync(zero_rows, 0, (size_t)H * B * T * E * sizeof(float), st) != hipSuccess) {
+            edgl_set_error("edgl_bimau_fwd: memset failed");
+            return EDGL_ERR_LAUNCH;
+        }
+        float* stats = nullptr;
+        if (saved) {   // H rows | z | row statistics
+            const bimau::SavedLayoutStream ss = bimau::saved_layout_stream(B, T, C, H, dtype == EDGL_BF16 ? 2 : 4);
+            p.hin_out = (char*)saved + ss.off_hin;
+            p.z_out = reinterpret_cast<float*>((char*)saved + ss.off_z);
+            stats = reinterpret_cast<float*>((char*)saved + ss.off_stats);
+        }
+        edgl_prof_begin(EDGL_KERNEL_BIMAU_FWD, st);
+        const int rc = bimau::stream_fwd(p, stats, dtype, st);
+        edgl_prof_end(EDGL_KERNEL_BIMAU_FWD, st);
+        return rc;
+    }
     if (C / H == 64 || C / H == 128) {   // three-launch form: lambda is written by the intensity kernel — plain memset there
         if (zero_rows && hipMemsetAsync(zero_rows, 0, (size_t)H * B * T * E * sizeof(float), st) != hipSuccess) {
             edgl_set_error("edgl_bimau_fwd: memset failed");

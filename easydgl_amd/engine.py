@@ -143,7 +143,9 @@ class TrainEngine:
         self.pre_t, self.so, self.st3 = e(B, T, C), e(B, T, C), e(B, 2, dtype=f32)
         # fused per-sample block tail (csrc/k_tail.hip): one launch for dense -> LN -> GELU-dense -> dense -> LN (-> head)
         # (the head of the fused tail and the fused TPP kernel hold the masked positions of a sample in LDS: M <= 256, T <= 1024 —
-        # beyond what the BiMAU kernels take (T <= 208), checked here so that a future relaxation fails at construction)
+        # the bound of the key-streamed BiMAU kernels too (edgl_bimau_form: T <= 208 ... 64 in registers, T <= 1024 streamed).  Beyond
+        # their own bounds the optional forms are simply not taken: fused TPP and stored keep bits T <= 128, fused tail T <= 112;
+        # the buffer sizes of `saved` and the backward workspace come from the size queries, which know the form)
         if m.ct_reg != 0.0 and (M > 256 or T > 1024):
             raise _lib.EdglError(f"TrainEngine: masklen {M} > 256 or T {T} > 1024 exceeds the fused TPP kernel (edgl_tpp_fwd_bwd_ex)")
         # (channel-padded models: the _ct forms take the LayerNorms' moments over the real channels)

@@ -66,6 +66,7 @@ class Drop:
 
 NO_DROP = Drop()
 MAU_CAUSAL, MAU_NO_DIAG, MAU_DIAG_ZERO = _lib.MAU_CAUSAL, _lib.MAU_NO_DIAG, _lib.MAU_DIAG_ZERO
+MAU_STREAM = _lib.MAU_STREAM   # host-side hint: the key-streamed kernels at a shape the in-register kernels also take
 
 
 def make_rng_state(device, seed: int = 9876) -> torch.Tensor:
@@ -309,9 +310,11 @@ class BiMAUFn(torch.autograd.Function):
         if resid.stride(-1) != 1 or resid.stride(0) != T * resid.stride(1):
             raise _lib.EdglError("BiMAU residual must be a row-strided view of a contiguous [B,T,*] tensor")
         need_grad = any(ctx.needs_input_grad)
-        # head dims >= 64 run as scores phase -> intensity kernel -> values phase and hand H rows / z through `saved`
-        need_saved = need_grad or (C // H) >= 64
-        saved = torch.empty(lib.edgl_bimau_saved_bytes(B, T, C, H, code), device=qkvt.device, dtype=torch.uint8) if need_saved else None
+        # head dims >= 64 and the key-streamed form (long T, or MAU_STREAM) run as scores phase -> intensity kernel -> values phase
+        # and hand H rows / z (/ the softmax statistics) through `saved`
+        form = lib.edgl_bimau_form(T, C, H, code, int(flags))
+        need_saved = need_grad or (C // H) >= 64 or form == 1
+        saved = torch.empty(max(lib.edgl_bimau_saved_bytes_ex(B, T, C, H, code, int(flags)), 0), device=qkvt.device, dtype=torch.uint8) if need_saved else None
         check(lib.edgl_bimau_fwd_db(_ptr(qkvt), resid.data_ptr(), resid.stride(1), _ptr(ids), _ptr(spans), _ptr(marks),
                                     _ptr(pack), B, T, C, H, E, float(drop.rate), drop.ptr(), drop.stream_id, None, float(qk_scale),
                                     _ptr(out), _ptr(lam), _ptr(saved), None, int(flags), code, _stream()), "edgl_bimau_fwd")
@@ -333,7 +336,7 @@ class BiMAUFn(torch.autograd.Function):
         both = torch.empty(n1 + n2 + n3 + n4, device=dev, dtype=torch.float32)
         dW1, db1 = both[:n1].view(s1), both[n1:n1 + n2].view(s2)
         dw, dsc = both[n1 + n2:n1 + n2 + n3].view(s3), both[n1 + n2 + n3:].view(s4)
-        ws = torch.empty(lib.edgl_bimau_bwd_workspace(B, T, C, H, E, code), device=dev, dtype=torch.uint8)
+        ws = torch.empty(lib.edgl_bimau_bwd_workspace_ex(B, T, C, H, E, code, flags), device=dev, dtype=torch.uint8)
         dl = d_lam.contiguous() if d_lam is not None else None
         check(lib.edgl_bimau_bwd_db(_ptr(qkvt), _ptr(ids), _ptr(spans), _ptr(marks), _ptr(pack), _ptr(d_out), _ptr(dl),
                                     _ptr(lam), _ptr(saved), B, T, C, H, E, float(drop.rate), drop.ptr(), drop.stream_id, None,

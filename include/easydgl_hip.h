@@ -203,7 +203,17 @@ int edgl_colsum(const void* X, int M, int N, int ld, float* out, int accumulate,
  * it with 1, :438-439); EDGL_MAU_DIAG_ZERO writes 0 there instead of 1 — for a unit with more than 16 mark types, run as
  * groups of <= 16 marks whose outputs are summed (G is linear in the marks: group 0 carries the diagonal 1 and the
  * residual, the later groups 0 and a zero residual).  The caller may fill the Q and K|V|T_ column blocks of qkvt from different inputs
- * (MAU: Q = dense(LN(x)), K,V,T_ = dense(x), temporal.py:352-355).  Supported: dh in {16,32}, E<=16, T<=128. */
+ * (MAU: Q = dense(LN(x)), K,V,T_ = dense(x), temporal.py:352-355).  Supported: dh in {16,32,64,128}, E<=16, T<=1024.
+ *
+ * Two kernel families serve the unit.  The in-register kernels keep the whole key row of a (sample, head) job in registers and
+ * take T <= 208 at head dim 16, T <= 208 (bf16) / 128 (f32) at head dim 32, T <= 128 / 112 at head dim 64 and T <= 128 / 64 at head
+ * dim 128.  Every other shape up to T = 1024 runs the key-streamed kernels (flash style: the keys are walked in tiles, the softmax
+ * statistics of every row are kept in `saved`), which compute the same function, take the same dropout decisions from the same
+ * (rng_state, stream_id) and need `saved` also for inference.  edgl_bimau_form tells which family a shape gets (0 in-register,
+ * 1 key-streamed, negative: unsupported; a host function, no GPU needed).  EDGL_MAU_STREAM is a host-side hint like
+ * EDGL_MAU_NO_SKIP: it forces the key-streamed family at a shape the in-register kernels also take; the forward, its backward and
+ * the size queries (the _ex forms below, which take the flags) must all see the same flag.  The key-streamed family has no fused TPP
+ * form and ignores dropbits, order and EDGL_MAU_NO_SKIP (results do not depend on them anywhere). */
 #define EDGL_MAU_CAUSAL 1
 #define EDGL_MAU_NO_DIAG 2
 #define EDGL_MAU_DIAG_ZERO 4
@@ -212,8 +222,12 @@ int edgl_colsum(const void* X, int M, int N, int ld, float* out, int accumulate,
  * have any — training batches of the reference's masker carry MASK tokens on padded positions, dataloader.py:187-191 — saves the
  * skip variant's per-tile scalar branch.  Results are identical either way. */
 #define EDGL_MAU_NO_SKIP 8
+#define EDGL_MAU_STREAM 16
+int edgl_bimau_form(int T, int C, int H, int dtype, int flags);
 long edgl_bimau_pack_bytes(int C, int H, int E, int dtype);
+/* bytes of `saved` for the family the shape gets without / with the hint flags (the _ex form with flags = 0 is the plain one) */
 long edgl_bimau_saved_bytes(int B, int T, int C, int H, int dtype);
+long edgl_bimau_saved_bytes_ex(int B, int T, int C, int H, int dtype, int flags);
 /* largest mark count (<= 16) one launch takes at this head dim / dtype (LDS of the intensity backward); -1: bad arguments */
 int edgl_bimau_mark_group(int C, int H, int dtype);
 int edgl_bimau_pack(const float* W1, const float* b1, const float* w, const float* scaling, int C, int H, int E,
@@ -270,6 +284,7 @@ int edgl_bimau_bwd_ord(const void* qkvt, const int64_t* ids, const float* spans,
  * `workspace` — edgl_bimau_bwd_workspace BYTES — are reduced in a fixed order).  The residual
  * gradient (d_out itself) is NOT added here — the caller routes it. */
 long edgl_bimau_bwd_workspace(int B, int T, int C, int H, int E, int dtype);
+long edgl_bimau_bwd_workspace_ex(int B, int T, int C, int H, int E, int dtype, int flags);   /* for the family that `flags` selects */
 int edgl_bimau_bwd(const void* qkvt, const int64_t* ids, const float* spans, const uint8_t* marks,
                    const void* pack, const void* d_out, const float* d_lam_ext, const float* lam,
                    const void* saved, int B, int T, int C, int H, int E, float drop_rate,
