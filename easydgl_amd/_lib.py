@@ -43,6 +43,10 @@ SIGNATURES = {
     "edgl_encode_bwd_add_ct": (I, [P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, I, P]),
     "edgl_encode_bwd_label_fused": (I, [I, I]),
     "edgl_encode_bwd_add_label": (I, [P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, P, P, P, P, I, P, I, P]),
+    "edgl_segsum_passes": (I, [I]),
+    "edgl_segsum_plan_bytes": (L, [I, I]),
+    "edgl_segsum_plan": (I, [P, I, P, I, I, I, P, P]),
+    "edgl_encode_bwd_add_det": (I, [P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, P, I, P]),
     "edgl_embed_pos_fwd": (I, [P, P, P, P, P, I, I, I, I, F, F, P, U32, P, P, P, I, P]),
     "edgl_embed_pos_bwd": (I, [P, P, I, I, I, I, F, P, U32, P, P, I, P]),
     "edgl_embed_pos_fwd_ct": (I, [P, P, P, P, P, I, I, I, I, F, F, P, U32, P, P, P, I, I, P]),
@@ -100,6 +104,7 @@ SIGNATURES = {
     "edgl_score_flash_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, I, P]),
     "edgl_score_flash_bwd_ex": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, P, P, I, I, P]),
     "edgl_score_flash_label_term": (I, [P, P, P, P, I, I, I, I, I, P, P, P, I, P]),
+    "edgl_score_flash_label_term_det": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, I, P]),
     "edgl_reduce_defer": (I, [I, P]),
     "edgl_reduce_flush": (I, [P]),
     "edgl_mask_topk": (I, [P, I, I, I, P, I, I, P, P, P]),

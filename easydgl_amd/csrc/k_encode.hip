@@ -578,12 +578,24 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
                            int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
                            float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, const void* lab_rows,
                            const int64_t* lab_ids, const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias,
-                           int dtype, void* stream);
+                           void* det_plan, int dtype, void* stream);
 extern "C" int edgl_encode_bwd_add_ct(const int64_t* ids, const uint8_t* marks, const void* dx0, const void* add1, const void* add2, int B,
                                       int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
                                       float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, int dtype, void* stream) {
     return encode_bwd_impl(ids, marks, dx0, add1, add2, B, T, C, E, I, drop_rate, rng_state, stream_id, d_item, d_pos, d_mark_emb, workspace,
-                           c_true, nullptr, nullptr, nullptr, nullptr, 0, nullptr, dtype, stream);
+                           c_true, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, dtype, stream);
+}
+// edgl_encode_bwd_add_ct with the item scatter as an ordered sum over a sorted plan (k_segsum.hip) instead of f32 atomics: the
+// position / mark stage and its reductions are the same launches, d_item is bitwise reproducible (coding.py:60-64).
+int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* dx0, const void* add1, const void* add2, float sq, float rate,
+                      const uint64_t* rng, uint32_t stream_id, float* d_item, void* plan, int dtype, hipStream_t st);
+extern "C" int edgl_encode_bwd_add_det(const int64_t* ids, const uint8_t* marks, const void* dx0, const void* add1, const void* add2, int B,
+                                       int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
+                                       float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, void* plan, int dtype,
+                                       void* stream) {
+    EDGL_REQUIRE(plan, EDGL_ERR_NULL, "edgl_encode_bwd_add_det: null plan buffer");
+    return encode_bwd_impl(ids, marks, dx0, add1, add2, B, T, C, E, I, drop_rate, rng_state, stream_id, d_item, d_pos, d_mark_emb, workspace,
+                           c_true, nullptr, nullptr, nullptr, nullptr, 0, nullptr, plan, dtype, stream);
 }
 // edgl_encode_bwd_add_ct that ALSO applies the one-hot term of the scoring gradient which edgl_score_flash_bwd_ex(defer_label_term = 1)
 // left out — d_item[label[r]] -= coef[r] rows[r], d_bias[label[r] - 1] -= coef[r] over the first min(R, nvalid) compacted rows
@@ -599,13 +611,13 @@ extern "C" int edgl_encode_bwd_add_label(const int64_t* ids, const uint8_t* mark
     EDGL_REQUIRE(edgl_encode_bwd_label_fused(C, dtype) && (((uintptr_t)lab_rows | (uintptr_t)dx0 | (uintptr_t)add1 | (uintptr_t)add2) & 7) == 0,
                  EDGL_ERR_SHAPE, "edgl_encode_bwd_add_label: needs bf16, C %% 128 == 0 (or 64) and 8-byte aligned operands (C=%d)", C);
     return encode_bwd_impl(ids, marks, dx0, add1, add2, B, T, C, E, I, drop_rate, rng_state, stream_id, d_item, d_pos, d_mark_emb, workspace,
-                           c_true, lab_rows, lab_ids, lab_coef, lab_nvalid, lab_R, d_bias, dtype, stream);
+                           c_true, lab_rows, lab_ids, lab_coef, lab_nvalid, lab_R, d_bias, nullptr, dtype, stream);
 }
 static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void* dx0, const void* add1, const void* add2, int B,
                            int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
                            float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, const void* lab_rows,
                            const int64_t* lab_ids, const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias,
-                           int dtype, void* stream) {
+                           void* det_plan, int dtype, void* stream) {
     EDGL_REQUIRE(c_true >= 0 && c_true <= C, EDGL_ERR_SHAPE, "edgl_encode_bwd: true width %d exceeds C=%d", c_true, C);
     EDGL_REQUIRE((add1 == nullptr) == (add2 == nullptr), EDGL_ERR_NULL, "edgl_encode_bwd_add: add1 / add2 go together");
     EDGL_REQUIRE(ids && marks && dx0 && d_item && d_pos && d_mark_emb && workspace, EDGL_ERR_NULL,
@@ -625,7 +637,10 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
     if (dtype == EDGL_F32) hipLaunchKernelGGL((encode_bwd_kernel<float>), grid, dim3(256), smem, st, p);
     else hipLaunchKernelGGL((encode_bwd_kernel<bf16>), grid, dim3(256), smem, st, p);
     EDGL_LAUNCH_CHECK();
-    {
+    if (det_plan) {      // deterministic mode: sorted plan + ordered sum, no atomics
+        const int rc = edgl_segsum_embed(ids, (long)B * T, C, I, dx0, add1, add2, p.sq, drop_rate, rng_state, stream_id, d_item, det_plan, dtype, st);
+        if (rc) return rc;
+    } else {
         const size_t smem_s = (size_t)srows * C * sizeof(float);
         EDGL_REQUIRE(smem_s <= 150 * 1024, EDGL_ERR_SHAPE, "edgl_encode_bwd: C=%d too large for the scatter stage", C);
         const unsigned nb = (unsigned)(((long)B * T + srows - 1) / srows);

@@ -2307,6 +2307,19 @@ extern "C" int edgl_score_flash_label_term(const void* rows, const int64_t* labe
     if (strip == 2) return edgl_stripw_label_scatter(rows, labels, coef, nvalid, R, C, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
     return edgl_strip_label_scatter(rows, labels, coef, nvalid, R, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
 }
+// edgl_score_flash_label_term as an ordered sum over a sorted plan (k_segsum.hip): no f32 atomics, one writer per table row, the
+// same no-op where the product pass already contains the one-hot term (EasyDGL.py:177-185).
+int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
+                      const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype, hipStream_t st);
+extern "C" int edgl_score_flash_label_term_det(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C,
+                                               int I, int i0, int i1, const int32_t* nvalid, float* d_table, float* d_bias, void* plan,
+                                               int dtype, void* stream) {
+    EDGL_REQUIRE(rows && labels && coef && d_table && d_bias && plan, EDGL_ERR_NULL, "edgl_score_flash_label_term_det: null pointer");
+    EDGL_REQUIRE(R > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1, EDGL_ERR_SHAPE, "edgl_score_flash_label_term_det: bad shape");
+    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_score_flash_label_term_det: bad dtype %d", dtype);
+    if (!use_strip(C, dtype == EDGL_BF16 ? 2 : 4)) return EDGL_OK;
+    return edgl_segsum_label(rows, labels, coef, gscale, R, C, I, i0, i1, nvalid, d_table, d_bias, plan, dtype, (hipStream_t)stream);
+}
 extern "C" int edgl_score_flash_bwd_ex(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                                        const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int i0,
                                        int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias,

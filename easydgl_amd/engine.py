@@ -49,7 +49,8 @@ class TrainEngine:
     place because only the strip passes leave the one-hot term of the table gradient to the embedding scatter (`_label_fused`)."""
     _SIDE_STREAMS = {}
 
-    def __init__(self, model, batch: int, use_graph: bool = True, process_group=None, fused_tail=None, flash_ce=None):
+    def __init__(self, model, batch: int, use_graph: bool = True, process_group=None, fused_tail=None, flash_ce=None,
+                 deterministic=None):
         # the environment switches (class docstring): read here, once, and nowhere else in the engine
         env = os.environ.get
         self.sw_flash_ce = env("EDGL_FLASH_CE", "1") != "0"
@@ -63,6 +64,12 @@ class TrainEngine:
         self.m = model
         self.B = batch
         self.use_graph = use_graph
+        # Deterministic mode (None: the model's attribute): the two f32-atomic scatters into the item table / output
+        # bias gradient — the embedding scatter and the one-hot term of the scoring gradient — run as ordered sums over sorted plans
+        # (csrc/k_segsum.hip) on the main stream, behind the slab reduction that assigns the two gradients.  The launch sequence
+        # is then ONE, eager or captured: no slab folding into the optimizer launch, no L2 term from the optimizer's sums, no lazy
+        # loss (step()), so a replayed graph and the eager step give the same bits.  The data-parallel all-reduce is outside the promise.
+        self.deterministic = bool(getattr(model, "deterministic", False)) if deterministic is None else bool(deterministic)
         self.group = process_group
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         m = model
@@ -178,7 +185,7 @@ class TrainEngine:
         # step, checkpoint, an autograd-path step) the term is recomputed from the arena.
         self.l2_nparts = int(lib.edgl_adam_l2_parts(m._arena.numel()))
         self.l2_parts = [torch.zeros(self.l2_nparts, device=dev, dtype=f32) for _ in range(2)] \
-            if (m.l2_reg != 0.0 and not use_graph) else None
+            if (m.l2_reg != 0.0 and not use_graph and not self.deterministic) else None
         self._l2p_cur, self._l2p_ready = 0, False
         # two side streams per DEVICE, shared by every engine of the process: the runtime multiplexes streams onto a handful of
         # hardware queues, and a process that builds engine after engine (bench.py's extra rows) otherwise ends up with its main
@@ -205,7 +212,7 @@ class TrainEngine:
         # the host swaps in behind it — no single-thread step_begin launch at the end of the step's chain.  step() only (a bare
         # _issue() leaves complete gradients in the arena), single process only (the all-reduce wants complete gradients), never with a
         # captured graph on the model (a graph bakes the counters' addresses in).  EDGL_ADAM_EX=0: the round-5 launches.
-        self.adam_ex = (not use_graph) and self.sw_adam_ex
+        self.adam_ex = (not use_graph) and self.sw_adam_ex and not self.deterministic
         self._rng_alt, self._adam_alt = torch.zeros_like(m._rng_state), torch.zeros_like(m._adam_state)
         self._slabs = None          # (table slabs ptr, bias slabs ptr, nslab) left by the scoring backward of the current step
         self._slab_info = None
@@ -232,6 +239,9 @@ class TrainEngine:
         self._dp = False
         # ---- backward temporaries -------------------------------------------------------------------------------
         self.d_rows = e(self.R, C)
+        # deterministic mode: the static plan buffers of the two ordered sums (embedding rows, label rows)
+        self.plan_emb = ops.segsum_plan_buffer(self.rows, I, dev) if self.deterministic else None
+        self.plan_lab = ops.segsum_plan_buffer(self.R, I, dev) if self.deterministic else None
         self.G1, self.G2, self.G3, self.G4 = e(B, T, C), e(B, T, C), e(B, T, C), e(B, T, C)
         self.G2c, self.G4c, self.G3c = e(B, T, 2 * C), e(B, T, 4 * C), e(B, T, 3 * C)
         # ---- workspaces -----------------------------------------------------------------------------------------------
@@ -589,7 +599,7 @@ class TrainEngine:
         if self.flash_ce:
             # d_rows: written by the forward call.  The one-hot term of the table / bias gradient (a scatter of the weighted rows:
             # f32 atomics that commute with the embedding scatter's) is deferred to the side stream at the end of the backward
-            defer = 1 if self.blk else 0
+            defer = 1 if (self.blk or self.deterministic) else 0
             if self._fold:
                 defer |= 4      # the slabs stay in the flash workspace: the optimizer launch sums them (no slab_reduce launch)
                 o_t, o_b, ns = self._slab_info
@@ -600,8 +610,15 @@ class TrainEngine:
                   "edgl_score_flash_bwd")
             # the one-hot term as extra blocks of the embedding scatter's launch at the end of the backward (no launch, no fork)
             self._label_fused = bool((defer & 1) and self.code == _lib.BF16 and C == 128 and lib.edgl_encode_bwd_label_fused(C, code)
-                                     and self.sw_score_strip)    # (only the strip passes leave the term out)
-            if (defer & 1) and not self._label_fused:
+                                     and self.sw_score_strip and not self.deterministic)    # (only the strip passes leave the term out)
+            if self.deterministic:
+                # the one-hot term as an ordered sum, here: behind the slab reduction that assigned the two gradients, in front of
+                # the embedding scatter's ordered sum at the end of the backward — one stream, one order (a no-op where the
+                # product pass already contains the term)
+                check(lib.edgl_score_flash_label_term_det(_ptr(self.hrows_c), _ptr(lab), _ptr(self.coef), None, R, C, I, 0, I,
+                                                          _ptr(self.nvalid), _ptr(tab.grad), _ptr(m.output_bias.grad),
+                                                          _ptr(self.plan_lab), code, st), "edgl_score_flash_label_term_det")
+            elif (defer & 1) and not self._label_fused:
                 self._pending_label = lambda s: check(lib.edgl_score_flash_label_term(
                     _ptr(self.hrows_c), _ptr(lab), _ptr(self.coef), None, R, C, I, 0, I, _ptr(self.nvalid), _ptr(tab.grad),
                     _ptr(m.output_bias.grad), code, s), "edgl_score_flash_label_term")
@@ -699,7 +716,12 @@ class TrainEngine:
                 dY = d_in   # first block: the embedding backward adds the two branches itself (one pass less over dX0)
         d0 = drop(hd, 1)
         add1, add2 = (self.G1, self.G2) if self.blk else (None, None)
-        if self._label_fused:
+        if self.deterministic:
+            check(lib.edgl_encode_bwd_add_det(_ptr(self.ids), _ptr(self.marks), _ptr(dY), _ptr(add1), _ptr(add2), B, T, C, E, I,
+                                              float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad), _ptr(m.pcoding.pembs.lookup_table.grad),
+                                              _ptr(m.mark_embs.lookup_table.grad), _ptr(self._ws(lib.edgl_encode_bwd_workspace(B, T, C))),
+                                              self.c_true, _ptr(self.plan_emb), code, st), "edgl_encode_bwd_add_det")
+        elif self._label_fused:
             check(lib.edgl_encode_bwd_add_label(_ptr(self.ids), _ptr(self.marks), _ptr(dY), _ptr(add1), _ptr(add2), B, T, C, E, I,
                                                 float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad),
                                                 _ptr(m.pcoding.pembs.lookup_table.grad), _ptr(m.mark_embs.lookup_table.grad),
@@ -916,7 +938,10 @@ class TrainEngine:
         if not self.use_graph:
             if distributed:
                 self._global_counts()
-            self._issue(lazy_loss=not distributed, fold_slabs=self.adam_ex and not distributed and not self.m._state_pinned)
+            # (deterministic mode: exactly the captured path's _issue() — the lazy form groups the deferred reductions into other
+            #  launches, and the reduction kernel's form, hence its summation order, is chosen per launch)
+            self._issue(lazy_loss=not distributed and not self.deterministic,
+                        fold_slabs=self.adam_ex and not distributed and not self.m._state_pinned)
             out = self.loss
             if distributed:
                 evs = self._ar_events      # bench.py: HIP events around the step's one collective (its EXPOSED time:

@@ -77,6 +77,8 @@ class EasyDGL(Sequential):
             raise ValueError(f"num_events must be in [2, {T.MAX_EVENTS}] (more than 16 run as mark groups: temporal.modulated_attention)")
         self.register_buffer("mark_lookup_table", torch.from_numpy(table.astype(np.uint8)), persistent=False)
         self.ct_reg = float(getattr(FLAGS, "ct_reg", 0.0) or 0.0)
+        # bitwise reproducible training: the item-table gradient as ordered sums instead of f32 atomics
+        self.deterministic = bool(getattr(FLAGS, "deterministic", False))
 
         gen = torch.Generator().manual_seed(self.seed)
         # A head dim the attention kernels do not tile (they take 16 / 32 / 64 / 128; the reference's own defaults are
@@ -267,7 +269,8 @@ class EasyDGL(Sequential):
         tab = self.item_embs.lookup_table
         return ops.EncodeFn.apply(tab, self.pcoding.pembs.lookup_table, self.mark_embs.lookup_table, self.compute(tab),
                                   ids, ts, self.mark_lookup_table, self.tcoding.scale, self.mask, self.time_scale,
-                                  self._drop(self.hidden_dropout_rate, 1, is_training), self.act_dtype, self.pad)
+                                  self._drop(self.hidden_dropout_rate, 1, is_training), self.act_dtype, self.pad,
+                                  self.deterministic)
 
     def encoder(self, features, is_training, gather_pos):
         """EasyDGL.py:70-146: returns (rows [B*Mg, C] at gather_pos, [lambda per block])."""
@@ -360,7 +363,8 @@ class EasyDGL(Sequential):
         """EasyDGL.py:153-188 with the fused scoring/CE path (no [B*M, I] tensor)."""
         rows, lams = self.encoder(features, True, self._gather_pos(features, True))
         tab = self.item_embs.lookup_table
-        loss = ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels.reshape(-1).contiguous())
+        loss = ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels.reshape(-1).contiguous(),
+                                   self.deterministic)
         if self.l2_reg != 0.0:                                                                     # :158
             for p in (self.item_embs.lookup_table, self.mark_embs.lookup_table, self.pcoding.pembs.lookup_table):
                 loss = loss + ops.L2Fn.apply(p, self.l2_reg)

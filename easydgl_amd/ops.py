@@ -128,6 +128,30 @@ def _splitk_for(m_out: int, n_out: int, kc: int) -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# deterministic item-table scatter (csrc/k_segsum.hip)
+# ------------------------------------------------------------------------------------------------
+def segsum_plan_buffer(n: int, I: int, device) -> torch.Tensor:
+    """Device buffer for one plan over n rows (sort scratch and the partial sums of the ordered sum included)."""
+    nbytes = int(lib.edgl_segsum_plan_bytes(int(n), int(I)))
+    if nbytes <= 0:
+        raise _lib.EdglError(f"segsum plan: bad shape n={n} I={I}")
+    return torch.empty((nbytes + 3) // 4, device=device, dtype=torch.int32)
+
+
+def segsum_plan(keys: torch.Tensor, I: int, nvalid: Optional[torch.Tensor] = None, i0: int = 0, i1: Optional[int] = None):
+    """The sorted plan of `keys` (int64 [n]) as views into its buffer: (perm [n], seg_key [n], seg_start [n + 1], nseg [1],
+    nkept [1]), all int32 on the device — perm[:nkept] are the kept rows by ascending key (ascending rows inside a key),
+    seg_key[:nseg] the distinct keys, seg_start[:nseg + 1] their first positions.  For tests and tools."""
+    keys = keys.reshape(-1).contiguous()
+    n = keys.numel()
+    buf = segsum_plan_buffer(n, I, keys.device)
+    check(lib.edgl_segsum_plan(_ptr(keys), n, _ptr(nvalid), int(I), int(i0), int(I if i1 is None else i1), _ptr(buf), _stream()),
+          "edgl_segsum_plan")
+    n4 = (n + 3) // 4 * 4
+    return buf[4:4 + n], buf[4 + n4:4 + n4 + n], buf[4 + 2 * n4:4 + 2 * n4 + n + 1], buf[0:1], buf[1:2]
+
+
+# ------------------------------------------------------------------------------------------------
 # K1 encode
 # ------------------------------------------------------------------------------------------------
 class EncodeFn(torch.autograd.Function):
@@ -136,8 +160,9 @@ class EncodeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, item_master, pos_tab, mark_emb, item_c, ids, ts, mark_table, tscale, mask_id, time_scale,
-                drop: Drop, act_dtype, pad=(0, 0)):
-        """pad = (dh_pad, dh_true) of a channel-padded model (model/base.py), (0, 0) otherwise."""
+                drop: Drop, act_dtype, pad=(0, 0), deterministic=False):
+        """pad = (dh_pad, dh_true) of a channel-padded model (model/base.py), (0, 0) otherwise.  deterministic: the backward adds
+        the item gradient as ordered sums over a sorted plan (edgl_encode_bwd_add_det) instead of f32 atomics."""
         B, T = ids.shape
         I, C = item_c.shape
         E = mark_table.shape[1]
@@ -150,6 +175,7 @@ class EncodeFn(torch.autograd.Function):
                                      _DT[act_dtype], _stream()), "edgl_encode_fwd")
         ctx.save_for_backward(ids, marks)
         ctx.c_true = (C // pad[0] * pad[1]) if pad[0] else 0
+        ctx.deterministic = bool(deterministic)
         ctx.meta = (B, T, C, E, I, drop, item_master.shape, pos_tab.shape, mark_emb.shape)
         ctx.mark_non_differentiable(spans, marks)
         return x0, spans, marks
@@ -163,10 +189,16 @@ class EncodeFn(torch.autograd.Function):
         d_pos = torch.zeros(pshape, device=dx0.device, dtype=torch.float32)
         d_mark = torch.empty(mshape, device=dx0.device, dtype=torch.float32)
         ws = torch.empty(lib.edgl_encode_bwd_workspace(B, T, C), device=dx0.device, dtype=torch.float32)
-        check(lib.edgl_encode_bwd_add_ct(_ptr(ids), _ptr(marks), _ptr(dx0), None, None, B, T, C, E, I, float(drop.rate), drop.ptr(),
-                                         drop.stream_id, _ptr(d_item), _ptr(d_pos), _ptr(d_mark), _ptr(ws), int(ctx.c_true),
-                                         _code(dx0), _stream()), "edgl_encode_bwd")
-        return (d_item, d_pos, d_mark) + (None,) * 10
+        if ctx.deterministic:
+            plan = segsum_plan_buffer(B * T, I, dx0.device)
+            check(lib.edgl_encode_bwd_add_det(_ptr(ids), _ptr(marks), _ptr(dx0), None, None, B, T, C, E, I, float(drop.rate), drop.ptr(),
+                                              drop.stream_id, _ptr(d_item), _ptr(d_pos), _ptr(d_mark), _ptr(ws), int(ctx.c_true),
+                                              _ptr(plan), _code(dx0), _stream()), "edgl_encode_bwd_add_det")
+        else:
+            check(lib.edgl_encode_bwd_add_ct(_ptr(ids), _ptr(marks), _ptr(dx0), None, None, B, T, C, E, I, float(drop.rate), drop.ptr(),
+                                             drop.stream_id, _ptr(d_item), _ptr(d_pos), _ptr(d_mark), _ptr(ws), int(ctx.c_true),
+                                             _code(dx0), _stream()), "edgl_encode_bwd")
+        return (d_item, d_pos, d_mark) + (None,) * 11
 
 
 class EmbedPosFn(torch.autograd.Function):
@@ -497,7 +529,10 @@ class ScoreCEFn(torch.autograd.Function):
     gives the row log-sum-exp also accumulates the row gradients, and the backward only finishes them."""
 
     @staticmethod
-    def forward(ctx, rows, table_master, out_bias, table_c, labels):
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, deterministic=False):
+        """deterministic: the one-hot term of the table / bias gradient is left out of the scoring backward
+        (edgl_score_flash_bwd_ex, defer_label_term = 1) and applied as ordered sums (edgl_score_flash_label_term_det)."""
+        ctx.deterministic = bool(deterministic)
         rows, labels, _perm, inv, nvalid = compact_rows(rows.contiguous(), labels.reshape(-1).contiguous())
         R, C = rows.shape
         I = table_c.shape[0]
@@ -530,12 +565,21 @@ class ScoreCEFn(torch.autograd.Function):
         d_rows = torch.empty_like(rows)
         d_table = torch.empty((I, C), device=dev, dtype=torch.float32)
         d_bias = torch.empty(I - 1, device=dev, dtype=torch.float32)
-        check(lib.edgl_score_flash_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(labels), _ptr(lse), _ptr(coef),
-                                       _ptr(g), R, C, I, 0, I, _ptr(nvalid), _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
-                                       _ptr(ws), _code(rows), _stream()), "edgl_score_flash_bwd")
+        if ctx.deterministic:
+            check(lib.edgl_score_flash_bwd_ex(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(labels), _ptr(lse), _ptr(coef),
+                                              _ptr(g), R, C, I, 0, I, _ptr(nvalid), _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
+                                              _ptr(ws), 1, _code(rows), _stream()), "edgl_score_flash_bwd")
+            plan = segsum_plan_buffer(R, I, dev)
+            check(lib.edgl_score_flash_label_term_det(_ptr(rows), _ptr(labels), _ptr(coef), _ptr(g), R, C, I, 0, I, _ptr(nvalid),
+                                                      _ptr(d_table), _ptr(d_bias), _ptr(plan), _code(rows), _stream()),
+                  "edgl_score_flash_label_term_det")
+        else:
+            check(lib.edgl_score_flash_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(labels), _ptr(lse), _ptr(coef),
+                                           _ptr(g), R, C, I, 0, I, _ptr(nvalid), _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
+                                           _ptr(ws), _code(rows), _stream()), "edgl_score_flash_bwd")
         check(lib.edgl_scatter_rows(_ptr(d_rows_c), _ptr(inv), R, C, _ptr(d_rows), _code(rows), _stream()),
               "edgl_scatter_rows")
-        return d_rows, d_table, d_bias, None, None
+        return d_rows, d_table, d_bias, None, None, None
 
 
 class ScoreLogitsFn(torch.autograd.Function):

@@ -61,6 +61,9 @@ def args(argv=None):
     p.add_argument("--patience", type=int, default=10)
     p.add_argument("--graph", action="store_true",
                    help="regressive models: replay the training step of full batches as one HIP graph (Sequential.graphed_train_step)")
+    p.add_argument("--deterministic", action="store_true",
+                   help="EasyDGL: bitwise reproducible training (main.py:157-168 pins TF_DETERMINISTIC_OPS): the item-table gradient "
+                        "as ordered sums instead of f32 atomics, in the engine and in train_step")
     a = p.parse_args(argv)
     return a
 
@@ -175,6 +178,9 @@ def run(FLAGS) -> Dict[str, float]:
     if getattr(FLAGS, "mark", None) and isinstance(FLAGS.mark, str):
         FLAGS.mark_table = F.load_mark_table(FLAGS.mark, FLAGS.num_items)
     FLAGS.compute_dtype = getattr(FLAGS, "dtype", "bf16")
+    if getattr(FLAGS, "deterministic", False) and FLAGS.model != "EasyDGL":
+        # the regressive models keep f32-atomic scatters (k_data.hip, k_tattn.hip): the promise must never silently not hold
+        raise ValueError(f"--deterministic covers --model EasyDGL only (got {FLAGS.model}): DESIGN 4.9")
     model = ranking(FLAGS)
     model.finalize(torch.device("cuda", torch.cuda.current_device()))
     bs = FLAGS.batch_size

@@ -137,6 +137,31 @@ int edgl_encode_bwd_add_label(const int64_t* ids, const uint8_t* marks, const vo
                               const int64_t* lab_ids, const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias,
                               int dtype, void* stream);
 
+/* ---- Deterministic item-table scatter (csrc/k_segsum.hip) — coding.py:60-64, EasyDGL.py:177-185 ---------------------
+ * The f32 atomics of the embedding scatter and of the one-hot term of the scoring gradient make the item-table gradient differ in
+ * its last bits from run to run.  The _det entry points below compute the same sums without atomics: a stable radix sort of the
+ * row indices by item id (the plan), then one ordered f32 sum per id, added to its table row with plain loads and stores (one writer
+ * per row per call).  The summation order is a function of the keys alone; two calls on the same inputs give the same bits.
+ *
+ * A plan is built in a caller-provided device buffer of edgl_segsum_plan_bytes bytes (16-byte aligned; sized for n rows at any
+ * C <= 512, scratch of the sort and of the sums included).  Its front, in 32-bit words with n4 = n rounded up to a multiple of 4:
+ *   [0] nseg   [1] kept rows   [4, 4 + n) perm   [4 + n4, ..) seg_key   [4 + 2 n4, ..) seg_start (nseg + 1 entries)
+ * keys int64 [n]; entries with key 0, entries at or behind min(n, *nvalid) (nvalid may be NULL) and keys outside [i0, i1) are
+ * dropped.  perm holds the kept row indices sorted by key, ascending rows inside one key; seg_key are the distinct keys in
+ * ascending order, seg_start[s] the first position of segment s in perm, seg_start[nseg] = kept rows.  The sort runs
+ * edgl_segsum_passes = ceil(bits(I - 1) / 8) passes of 8-bit digits.  No host read-back anywhere: every call can be captured in
+ * a HIP graph.  The two size queries are host functions (no GPU needed); they return -1 for bad arguments. */
+int edgl_segsum_passes(int I);
+long edgl_segsum_plan_bytes(int n, int I);
+int edgl_segsum_plan(const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, void* plan, void* stream);
+/* edgl_encode_bwd_add_ct with the item scatter through a plan over ids (built by the call in `plan`, edgl_segsum_plan_bytes of
+ * (B * T, I) bytes): the position / mark stage and its reductions are the same launches, d_item += the ordered sums.  The
+ * three-way sum dX0 + add1 + add2 is kept in f32.  C % 4 == 0, C <= 512. */
+int edgl_encode_bwd_add_det(const int64_t* ids, const uint8_t* marks, const void* dx0, const void* add1, const void* add2, int B,
+                            int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
+                            float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, void* plan, int dtype,
+                            void* stream);
+
 /* ---- K1b: CTSMA input encoding — CTSMA.py:48-58, coding.py:60-79 ----------------------------------
  * ids int64 [B,T] (tokens[:-1]), ts f32 [B,T+1] raw seconds.  x0 [B,T,2C] `dtype` =
  * dropout(concat(item_tab[ids] * sqrt(C) (row 0 reads as zeros), pos_tab[0..T))) (PositionCoding.__call__
@@ -492,6 +517,11 @@ int edgl_score_flash_bwd_ex(const void* rows, const void* table, const float* ou
                             int defer_label_term, int dtype, void* stream);
 int edgl_score_flash_label_term(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I,
                                 int i0, int i1, const int32_t* nvalid, float* d_table, float* d_bias, int dtype, void* stream);
+/* The same term without f32 atomics (deterministic mode): an ordered sum over a plan of the labels, built by the call in `plan`
+ * (edgl_segsum_plan_bytes of (R, I) bytes) — same contract, same no-op where the product pass already contains the one-hot term. */
+int edgl_score_flash_label_term_det(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C,
+                                    int I, int i0, int i1, const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype,
+                                    void* stream);
 
 /* ---- deferred partial reductions ------------------------------------------------------------------
  * The weight-gradient entry points (edgl_gemm_dw, edgl_add_layernorm_bwd, edgl_encode_bwd,
