@@ -107,6 +107,8 @@ SIGNATURES = {
     "edgl_score_flash_label_term_det": (I, [P, P, P, P, I, I, I, I, I, P, P, P, P, I, P]),
     "edgl_reduce_defer": (I, [I, P]),
     "edgl_reduce_flush": (I, [P]),
+    "edgl_reduce_partials": (I, [P, I, I, L, P, I, P]),
+    "edgl_reduce_ride": (I, [I]),
     "edgl_mask_topk": (I, [P, I, I, I, P, I, I, P, P, P]),
     "edgl_score_topk_fused_supported": (I, [I, I, I, I, I, I]),
     "edgl_score_topk_fused_workspace": (L, [I, I, I, I, I]),

@@ -4,6 +4,7 @@
 // C=128 row with contiguous 4/8-byte stores and one sincosf per pair.
 #include "edgl_common.h"
 #include "batch_prep.h"
+#include "red_batch.h"
 
 namespace {
 
@@ -170,6 +171,7 @@ struct EncBwdP {
     // embedding's: lab_blk0 = first such block (0: none)
     const void* lab_rows; const int64_t* lab_ids; const float* lab_coef; const int32_t* lab_nvalid; int lab_R; int lab_blk0;
     float* d_bias;
+    int red_blk0;         // first workgroup of the reduction list that rides in the MFMA scatter launch (RedBatch::blocks of them; 0: in front)
     float* d_mark_zero;   // [E*C]: cleared by block (0, 0) of the position / mark stage (only row 1 is ever written afterwards)   // rows per block of the scatter stage (<= SROWS; fewer when SROWS*C floats exceed the LDS)
 };
 
@@ -341,17 +343,26 @@ __device__ __forceinline__ uint2 enc_tr_read(const bf16* tile, int ld, int k0, i
 }
 // CT = channel tiles of one workgroup's slice (C = 16 CT channels starting at blockIdx.y * C of the p.C-wide rows: the 256 / 512-unit
 // recipes run as 2 / 4 slices of 128)
+// Third job of the launch (edgl_reduce_ride; gridDim.y == 1 only): the deferred partial reductions of the backward, rb.blocks
+// workgroups from p.red_blk0 on that run the body of reduce_rows_multi_vec_kernel and leave.  They read what earlier launches of the
+// stream wrote and write what later launches read: no ordering against the scatter's workgroups exists or is needed.
 template <int CT>
-__global__ __launch_bounds__(256) void encode_scatter_mfma_kernel(EncBwdP p) {
+__global__ __launch_bounds__(256) void encode_scatter_mfma_kernel(EncBwdP p, RedBatch rb) {
     constexpr int C = 16 * CT, LDG = C + 8, SR = SROWS;
     const int CF = p.C, coff = (int)blockIdx.y * C;      // full row width, first channel of this slice
     __shared__ __attribute__((aligned(16))) bf16 Gs[SR * LDG];   // masked gradient rows of the block
     __shared__ __attribute__((aligned(16))) int s_id[SR];
     __shared__ __attribute__((aligned(16))) int s_lead[SR];       // first row with the same id; -1: padding / past the end
+    if ((int)blockIdx.x >= p.red_blk0 && (int)blockIdx.x < p.red_blk0 + rb.blocks) {      // reduction job (block-uniform)
+        static_assert(sizeof(Gs) >= 32 * 9 * sizeof(float4), "the reduction's scratch lives in the row image");
+        reduce_rows_vec_block(rb, (int)blockIdx.x - p.red_blk0, reinterpret_cast<float4(*)[9]>(Gs));
+        return;
+    }
+    const int bx = (int)blockIdx.x - (p.red_blk0 == 0 ? rb.blocks : 0);      // workgroup index among the scatter's own
     // label job (block-uniform): rows = the compacted head rows, ids = their labels, every row scaled by its loss coefficient
-    const bool lab = p.lab_blk0 > 0 && (int)blockIdx.x >= p.lab_blk0;
+    const bool lab = p.lab_blk0 > 0 && bx >= p.lab_blk0;
     const long rows = lab ? (long)(p.lab_nvalid ? min(p.lab_R, p.lab_nvalid[0]) : p.lab_R) : (long)p.B * p.T;
-    const long r0 = (long)((int)blockIdx.x - (lab ? p.lab_blk0 : 0)) * SR;
+    const long r0 = (long)(bx - (lab ? p.lab_blk0 : 0)) * SR;
     if (lab && r0 >= rows) return;
     __shared__ float s_cf[SR], s_cb[SR];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, G = lane >> 4, g4 = G * 4, l15 = lane & 15;
@@ -629,7 +640,7 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
     int srows = SROWS;
     while (srows > 8 && (size_t)srows * C * sizeof(float) > 150 * 1024) srows >>= 1;   // C = 512: 64 rows per block
     EncBwdP p{ids, marks, dx0, B, T, C, E, I, drop_rate, rng_state, stream_id, d_item, part_pos, part_mk, ENC_NCHUNK, srows, add1, add2,
-              sqrtf((float)(c_true > 0 ? c_true : C)), lab_rows, lab_ids, lab_coef, lab_nvalid, lab_R, 0, d_bias, d_mark_emb};
+              sqrtf((float)(c_true > 0 ? c_true : C)), lab_rows, lab_ids, lab_coef, lab_nvalid, lab_R, 0, d_bias, 0, d_mark_emb};
     hipStream_t st = (hipStream_t)stream;
     const int rows_par = 256 / (C / 4);
     dim3 grid(T, ENC_NCHUNK);
@@ -637,6 +648,9 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
     if (dtype == EDGL_F32) hipLaunchKernelGGL((encode_bwd_kernel<float>), grid, dim3(256), smem, st, p);
     else hipLaunchKernelGGL((encode_bwd_kernel<bf16>), grid, dim3(256), smem, st, p);
     EDGL_LAUNCH_CHECK();
+    // the two reductions this call ends with (only row 1 of the mark-embedding table is ever indexed: EasyDGL.py:87-88)
+    const RedJob own[2] = {{part_pos, d_pos, (long)T * C, ENC_NCHUNK, T * C, 0}, {part_mk, E > 1 ? d_mark_emb + C : d_mark_emb, (long)C, ENC_NCHUNK * T, C, 0}};
+    bool rode = false;   // ... as workgroups of the MFMA scatter launch
     if (det_plan) {      // deterministic mode: sorted plan + ordered sum, no atomics
         const int rc = edgl_segsum_embed(ids, (long)B * T, C, I, dx0, add1, add2, p.sq, drop_rate, rng_state, stream_id, d_item, det_plan, dtype, st);
         if (rc) return rc;
@@ -647,8 +661,23 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
         if (dtype == EDGL_BF16 && (C % 128 == 0 || C == 64) && (((uintptr_t)dx0 | (uintptr_t)add1 | (uintptr_t)add2) & 7) == 0) {
             unsigned nbm = (unsigned)(((long)B * T + SROWS - 1) / SROWS);
             if (lab_rows) { p.lab_blk0 = (int)nbm; nbm += (unsigned)((lab_R + SROWS - 1) / SROWS); }    // label blocks behind the embedding's
-            if (C % 128 == 0) hipLaunchKernelGGL((encode_scatter_mfma_kernel<8>), dim3(nbm, C / 128), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((encode_scatter_mfma_kernel<4>), dim3(nbm), dim3(256), 0, st, p);
+            // the thread's queued reductions + the two of this call as further workgroups of the launch (edgl_reduce_ride): one
+            // slice of channels only — with gridDim.y > 1 every reduction workgroup would exist once per slice
+            RedBatch rb;
+            rb.n = rb.blocks = 0;
+            if (C <= 128) {
+                int first = 1;
+                const int nred = edgl_reduce_ride_take(own, E > 1 ? 2 : 1, d_item, d_item + (long)I * C, d_bias, d_bias ? d_bias + (I - 1) : d_bias,
+                                                       &rb, &first, st);
+                if (nred < 0) return nred;
+                if (nred > 0) {
+                    rode = true;
+                    p.red_blk0 = first ? 0 : (int)nbm;
+                    nbm += (unsigned)nred;
+                }
+            }
+            if (C % 128 == 0) hipLaunchKernelGGL((encode_scatter_mfma_kernel<8>), dim3(nbm, C / 128), dim3(256), 0, st, p, rb);
+            else hipLaunchKernelGGL((encode_scatter_mfma_kernel<4>), dim3(nbm), dim3(256), 0, st, p, rb);
         } else if (dtype == EDGL_F32) {
             hipFuncSetAttribute((const void*)encode_scatter_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s);
             hipLaunchKernelGGL((encode_scatter_kernel<float>), dim3(nb), dim3(256), smem_s, st, p);
@@ -658,10 +687,8 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
         }
         EDGL_LAUNCH_CHECK();
     }
-    int rc = edgl_reduce_rows(part_pos, ENC_NCHUNK, T * C, (long)T * C, d_pos, 0, st);
-    if (rc) return rc;
-    if (E > 1) {  // only row 1 of the mark-embedding table is ever indexed (EasyDGL.py:87-88)
-        rc = edgl_reduce_rows(part_mk, ENC_NCHUNK * T, C, C, d_mark_emb + C, 0, st);
+    for (int i = 0; i < (E > 1 ? 2 : 1) && !rode; ++i) {
+        const int rc = edgl_reduce_rows(own[i].part, own[i].P, own[i].N, own[i].ld, own[i].out, 0, st);
         if (rc) return rc;
     }
     return EDGL_OK;

@@ -7,6 +7,7 @@
 #include "edgl_common.h"
 #include "bimau_common.h"   // TppDesc / tpp_layout: slot data of the fused TPP form
 #include "batch_prep.h"     // slot data of a sample (also run inside the encoder's launch)
+#include "red_batch.h"      // job list of the deferred reductions (also run inside the embedding scatter's launch)
 
 namespace {
 thread_local char g_err[512] = "";
@@ -797,14 +798,14 @@ inline int grid_for(long n) { return (int)std::min<long>((n + 255) / 256, 4096);
 // the host and edgl_reduce_flush() runs all of them in ONE launch.  The caller must then keep every partial buffer
 // alive (distinct workspaces) until the flush.  Jobs that accumulate into `out` flush first and run immediately, so the
 // order of read-modify-write updates is preserved.
-constexpr int RED_MAX_JOBS = 24;
-constexpr int RED_COL_P = 32;      // jobs with at most this many partial rows run in the column form of the vector kernel
-struct RedJob { const float* part; float* out; long ld; int P, N, blk0; };
-struct RedBatch { RedJob j[RED_MAX_JOBS]; int n, blocks; };
 static inline int red_blocks_scalar(const RedJob& j) { return (j.N + 31) / 32; }
 static inline int red_blocks_vec(const RedJob& j) { return j.P <= RED_COL_P ? (j.N + 1023) / 1024 : (j.N + 31) / 32; }
+static inline bool red_job_vec(const RedJob& j) {
+    return (j.N & 3) == 0 && (j.ld & 3) == 0 && (((uintptr_t)j.part | (uintptr_t)j.out) & 15) == 0;
+}
 thread_local bool g_red_defer = false;
 thread_local RedBatch g_red_batch = {};
+thread_local int g_red_ride = 0;       // edgl_reduce_ride: 1 / 2 = the queue may leave with the embedding scatter's launch (in front of / behind its blocks)
 
 // 32 columns per workgroup.  Scalar form: one column per thread x RL partial-row lanes (RL = 8, or 32 when a list holds a deep job:
 // the 1616 partial rows of the mark-embedding gradient were a chain of 50 dependent loads per thread with 8 lanes).
@@ -846,64 +847,7 @@ __global__ __launch_bounds__(32 * RL) void reduce_rows_multi_kernel(RedBatch b) 
 
 __global__ __launch_bounds__(256) void reduce_rows_multi_vec_kernel(RedBatch b) {
     __shared__ float4 sm[32][9];
-    int ji = 0;
-    for (int i = 1; i < b.n; ++i)
-        if ((int)blockIdx.x >= b.j[i].blk0) ji = i;
-    const RedJob& jb = b.j[ji];
-    const int P = jb.P, N = jb.N;
-    const long ld = jb.ld;
-    if (P <= RED_COL_P) {
-        // few partial rows (the row splits of a weight-gradient GEMM: 2-24 slabs of up to 3 M elements): a thread owns one
-        // float4 column and adds its P values — 4 KB of consecutive bytes per row and workgroup, 32x fewer workgroups than the
-        // row-lane form, whose 32 lanes per column would mostly idle (the 512-unit recipe's lists took 213 us for 143 MB)
-        const int n = (((int)blockIdx.x - jb.blk0) * 256 + (int)threadIdx.x) * 4;
-        if (n >= N) return;
-        const float* base = jb.part + n;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        int p0 = 0;
-        for (; p0 + 8 <= P; p0 += 8) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(base + (long)(p0 + u) * ld);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
-        }
-        for (; p0 < P; ++p0) {
-            const float4 v = *reinterpret_cast<const float4*>(base + (long)p0 * ld);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        *reinterpret_cast<float4*>(jb.out + n) = acc;
-        return;
-    }
-    const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;          // float4 column group, row lane
-    const int n = ((int)blockIdx.x - jb.blk0) * 32 + 4 * tx;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (n < N) {
-        const float* base = jb.part + n;
-        int p = ty;
-        for (; p + 7 * 32 < P; p += 8 * 32) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(base + (long)(p + 32 * u) * ld);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
-        }
-        for (; p < P; p += 32) {
-            const float4 v = *reinterpret_cast<const float4*>(base + (long)p * ld);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-    }
-    sm[ty][tx] = acc;
-    __syncthreads();
-    if (ty < 4 && n < N) {       // 32 threads finish the 32 columns: thread (ty, tx) takes component ty of group tx
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const float4 v = sm[i][tx];
-            s += ty == 0 ? v.x : (ty == 1 ? v.y : (ty == 2 ? v.z : v.w));
-        }
-        jb.out[n + ty] = s;
-    }
+    reduce_rows_vec_block(b, (int)blockIdx.x, sm);      // (red_batch.h: the body is shared with the embedding scatter's launch)
 }
 
 int edgl_reduce_flush_impl(hipStream_t st) {
@@ -913,7 +857,7 @@ int edgl_reduce_flush_impl(hipStream_t st) {
     for (int i = 0; i < g_red_batch.n; ++i) {
         const RedJob& j = g_red_batch.j[i];
         maxp = std::max(maxp, j.P);
-        vec = vec && (j.N & 3) == 0 && (j.ld & 3) == 0 && (((uintptr_t)j.part | (uintptr_t)j.out) & 15) == 0;
+        vec = vec && red_job_vec(j);
     }
     int blocks = 0;      // first-block index of every job for the kernel form chosen
     for (int i = 0; i < g_red_batch.n; ++i) {
@@ -951,7 +895,56 @@ int edgl_reduce_rows(const float* part, int P, int N, long ld, float* out, int a
     return EDGL_OK;
 }
 
+// Hand-over of the queue to the embedding backward's MFMA scatter launch (k_encode.hip), which runs the jobs as extra workgroups:
+// `own` = the caller's d_pos / d_mark jobs, not yet queued; lo / hi = the two address ranges its atomics add into.  Returns the number
+// of reduction workgroups (*first_blocks: in front of the scatter's) with the list in *out and the queue empty, a negative error
+// code when the launch below failed, or 0 with everything as it was: riding not requested, not in deferred mode, a job outside the vector form (the form, and with it the order of the
+// additions, is chosen per list), or a job whose output lies inside a range — the flush assigns it BEHIND the scatter.  A list too
+// long for one batch with the caller's jobs is launched here, in the vector form it would have had anyway.
+int edgl_reduce_ride_take(const RedJob* own, int nown, const float* lo0, const float* hi0, const float* lo1, const float* hi1,
+                          RedBatch* out, int* first_blocks, hipStream_t st) {
+    if (!g_red_defer || !g_red_ride) return 0;
+    auto rides = [&](const RedJob& j) {
+        const float* o0 = j.out;
+        const float* o1 = j.out + j.N;
+        return red_job_vec(j) && !(o0 < hi0 && lo0 < o1) && !(o0 < hi1 && lo1 < o1);
+    };
+    for (int i = 0; i < g_red_batch.n; ++i)
+        if (!rides(g_red_batch.j[i])) return 0;
+    for (int i = 0; i < nown; ++i)
+        if (!rides(own[i])) return 0;
+    if (g_red_batch.n + nown > RED_MAX_JOBS) {
+        const int rc = edgl_reduce_flush_impl(st);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < nown; ++i) g_red_batch.j[g_red_batch.n++] = own[i];
+    int blocks = 0;
+    for (int i = 0; i < g_red_batch.n; ++i) {
+        g_red_batch.j[i].blk0 = blocks;
+        blocks += red_blocks_vec(g_red_batch.j[i]);
+    }
+    g_red_batch.blocks = blocks;
+    *out = g_red_batch;
+    *first_blocks = g_red_ride == 1;
+    g_red_batch.n = 0;
+    g_red_batch.blocks = 0;
+    return blocks;
+}
+
+extern "C" int edgl_reduce_ride(int on) {
+    EDGL_REQUIRE(on >= 0 && on <= 2, EDGL_ERR_SHAPE, "edgl_reduce_ride: on = %d (0: off, 1: in front of the scatter's workgroups, 2: behind)", on);
+    g_red_ride = on;
+    return EDGL_OK;
+}
+
+extern "C" int edgl_reduce_partials(const float* part, int P, int N, long ld, float* out, int accumulate, void* stream) {
+    EDGL_REQUIRE(part && out, EDGL_ERR_NULL, "edgl_reduce_partials: null pointer");
+    EDGL_REQUIRE(P > 0 && N > 0 && ld >= N, EDGL_ERR_SHAPE, "edgl_reduce_partials: bad shape P=%d N=%d ld=%ld", P, N, ld);
+    return edgl_reduce_rows(part, P, N, ld, out, accumulate, (hipStream_t)stream);
+}
+
 extern "C" int edgl_reduce_defer(int on, void* stream) {
+    if (on <= 0) g_red_ride = 0;      // (a riding request ends with the deferred mode it belongs to)
     if (on < 0) {   // abort: forget the queued jobs (their partial buffers may be gone) and leave deferred mode
         g_red_batch.n = 0;
         g_red_batch.blocks = 0;

@@ -44,6 +44,9 @@ class TrainEngine:
         EDGL_DEFER_LOSS=0        with sync_loss False the loss launches still run at the end of their own step's backward, not at
                                  the start of the next step
         EDGL_ADAM_EX=0           plain optimizer launch + slab reduction + step-counter launch instead of edgl_adam_apply_ex
+        EDGL_REDUCE_RIDE=0       the queued partial reductions of the backward as a launch of their own behind the embedding scatter
+                                 instead of extra workgroups of its launch (edgl_reduce_ride); 2: the workgroups behind the
+                                 scatter's instead of in front of them (the measured alternative, DESIGN rule 76)
 
     EDGL_SCORE_STRIP belongs to the library (csrc/k_score_strip.hip latches it once per process); the engine reads it at the same
     place because only the strip passes leave the one-hot term of the table gradient to the embedding scatter (`_label_fused`)."""
@@ -60,6 +63,8 @@ class TrainEngine:
         self.sw_ce_parts = env("EDGL_CE_PARTS", "1") != "0"
         self.sw_defer_loss = env("EDGL_DEFER_LOSS", "1") != "0"
         self.sw_adam_ex = env("EDGL_ADAM_EX", "1") != "0"
+        self.sw_reduce_ride = env("EDGL_REDUCE_RIDE", "1") != "0"
+        self.sw_reduce_ride_behind = env("EDGL_REDUCE_RIDE", "1") == "2"
         self.sw_score_strip = env("EDGL_SCORE_STRIP", "1") != "0"      # (the library's: csrc/k_score_strip.hip latches it per process)
         self.m = model
         self.B = batch
@@ -213,6 +218,12 @@ class TrainEngine:
         # _issue() leaves complete gradients in the arena), single process only (the all-reduce wants complete gradients), never with a
         # captured graph on the model (a graph bakes the counters' addresses in).  EDGL_ADAM_EX=0: the round-5 launches.
         self.adam_ex = (not use_graph) and self.sw_adam_ex and not self.deterministic
+        # The reductions still queued when the embedding backward is reached (edgl_reduce_defer) run as extra workgroups of its MFMA
+        # scatter launch: nothing in the list depends on the scatter or the other way round, and the launch that summed them sat
+        # alone between the scatter and the optimizer (DESIGN rule 76).  The library decides per call whether the list can ride
+        # (bf16, C = 64 / 128, every job in the vector form, no output inside the scatter's targets); what does not is flushed as
+        # before.  Deterministic mode keeps its launch sequence (the ordered sums are not this launch).
+        self.reduce_ride = self.sw_reduce_ride and not self.deterministic
         self._rng_alt, self._adam_alt = torch.zeros_like(m._rng_state), torch.zeros_like(m._adam_state)
         self._slabs = None          # (table slabs ptr, bias slabs ptr, nslab) left by the scoring backward of the current step
         self._slab_info = None
@@ -721,7 +732,10 @@ class TrainEngine:
                                               float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad), _ptr(m.pcoding.pembs.lookup_table.grad),
                                               _ptr(m.mark_embs.lookup_table.grad), _ptr(self._ws(lib.edgl_encode_bwd_workspace(B, T, C))),
                                               self.c_true, _ptr(self.plan_emb), code, st), "edgl_encode_bwd_add_det")
-        elif self._label_fused:
+            return
+        if self.reduce_ride:
+            check(lib.edgl_reduce_ride(2 if self.sw_reduce_ride_behind else 1), "edgl_reduce_ride")     # (holds until the deferred mode is left)
+        if self._label_fused:
             check(lib.edgl_encode_bwd_add_label(_ptr(self.ids), _ptr(self.marks), _ptr(dY), _ptr(add1), _ptr(add2), B, T, C, E, I,
                                                 float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad),
                                                 _ptr(m.pcoding.pembs.lookup_table.grad), _ptr(m.mark_embs.lookup_table.grad),

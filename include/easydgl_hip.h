@@ -534,6 +534,16 @@ int edgl_score_flash_label_term_det(const void* rows, const int64_t* labels, con
  * leaves deferred mode (a caller whose launch sequence failed half-way must not leave the thread deferred). */
 int edgl_reduce_defer(int on, void* stream);
 int edgl_reduce_flush(void* stream);
+/* The reduction of one set of partials by itself: out[n] (+)= sum over p < P of part[p * ld + n], fixed order — launched at once, or
+ * queued in deferred mode (accumulate = 0), exactly as the entry points above do with their own partials. */
+int edgl_reduce_partials(const float* part, int P, int N, long ld, float* out, int accumulate, void* stream);
+/* edgl_reduce_ride(1) (2: behind instead of in front of the scatter's workgroups), in deferred mode: the next edgl_encode_bwd* call
+ * of this thread that launches the MFMA scatter kernel (bf16, C = 64 / 128; not edgl_encode_bwd_add_det) takes the queued jobs,
+ * its own two included, into that launch as extra workgroups and leaves the queue empty — same sums, bit for bit, no reduction
+ * launch.  The jobs must not depend on the scatter: a list with a job outside the vector form (N, ld multiples of 4, 16-byte
+ * aligned pointers) or with an output inside d_item [I * C] / d_bias [I - 1] does not ride and stays queued for the flush.
+ * edgl_reduce_ride(0), or leaving deferred mode, withdraws the request. */
+int edgl_reduce_ride(int on);
 
 /* ---- K8: TPP likelihood regulariser — temporal.py:317-333 + EasyDGL.py:157-175 -----------------
  * lam f32 [H*B,T,E]; masked_pos int64 [B,M]; labels int64 [B,M]; ts_raw f32 [B,T] (raw seconds);
