@@ -24,29 +24,9 @@
 
 #include "edgl_common.h"
 #include "score_plan.h"
+#include "score_strip.h"
 #include "topk_select.h"
 #include "batch_prep.h"
-
-// csrc/k_score_strip.hip: one-wave-per-SIMD form of the two product passes (bf16, C = 128)
-bool edgl_strip_enabled();
-int edgl_strip_rows(const void* rows, const void* table, const float* out_bias, int R, int I, int i0, int i1, const int32_t* nvalid,
-                    float* slabs, float* part, int G, int slab16, hipStream_t st);
-int edgl_strip_table(const void* rows, const void* table, const float* out_bias, const float* coef, const float* row_lse, int R,
-                     int I, int i0, int i1, const int32_t* nvalid, float* slabs, float* bias_slabs, int nchunk, float* acc_table,
-                     float* acc_bias, hipStream_t st);
-// k_score_stripw.hip: the same passes at C = 256 (32 x vectors per wave, 128 per workgroup)
-bool edgl_stripw_enabled();
-bool edgl_stripw_supports(int C);
-long edgl_stripw_info_floats(long n);
-int edgl_stripw_rows(const void* rows, const void* table, const float* out_bias, int R, int C, int I, int i0, int i1,
-                     const int32_t* nvalid, float* slabs, float* part, int G, float* info_ws, hipStream_t st);
-int edgl_stripw_table(const void* rows, const void* table, const float* out_bias, const float* coef, const float* row_lse, int R,
-                      int C, int I, int i0, int i1, const int32_t* nvalid, float* slabs, float* bias_slabs, int nchunk, float* info_ws,
-                      hipStream_t st);
-int edgl_stripw_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int C, int i0,
-                              int i1, const float* gscale, float* d_table, float* d_bias, hipStream_t st);
-int edgl_strip_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int i0, int i1,
-                             const float* gscale, float* d_table, float* d_bias, hipStream_t st);
 
 namespace {
 
@@ -1936,7 +1916,7 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
                                             q.bias_slabs, q.nchunk, acc ? d_table : nullptr, acc ? d_bias : nullptr, st);
             if (rc) return rc;
             if (acc) {      // no slabs, no slab reduction
-                if (!p.defer_label) return edgl_strip_label_scatter(p.rows, p.labels, p.coef, p.nvalid, p.R, p.i0, p.i1, p.gscale, d_table, d_bias, st);
+                if (!p.defer_label) return edgl_strip_label_scatter(p.rows, p.labels, p.coef, p.nvalid, p.R, p.C, p.i0, p.i1, p.gscale, d_table, d_bias, st);
                 return EDGL_OK;
             }
         } else if (nw == 8) {
@@ -1958,8 +1938,7 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
                            q.nchunk, p.gscale);
         EDGL_LAUNCH_CHECK();
         if (strip && !p.defer_label) {   // the one-hot part of dl, which the strip product pass leaves out
-            const int rc = strip == 2 ? edgl_stripw_label_scatter(p.rows, p.labels, p.coef, p.nvalid, p.R, p.C, p.i0, p.i1, p.gscale, d_table, d_bias, st)
-                                      : edgl_strip_label_scatter(p.rows, p.labels, p.coef, p.nvalid, p.R, p.i0, p.i1, p.gscale, d_table, d_bias, st);
+            const int rc = edgl_strip_label_scatter(p.rows, p.labels, p.coef, p.nvalid, p.R, p.C, p.i0, p.i1, p.gscale, d_table, d_bias, st);
             if (rc) return rc;
         }
     }
@@ -2302,10 +2281,8 @@ extern "C" int edgl_score_flash_label_term(const void* rows, const int64_t* labe
                                            void* stream) {
     EDGL_REQUIRE(rows && labels && coef && d_table && d_bias, EDGL_ERR_NULL, "edgl_score_flash_label_term: null pointer");
     EDGL_REQUIRE(R > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1, EDGL_ERR_SHAPE, "edgl_score_flash_label_term: bad shape");
-    const int strip = use_strip(C, dtype == EDGL_BF16 ? 2 : 4);
-    if (!strip) return EDGL_OK;
-    if (strip == 2) return edgl_stripw_label_scatter(rows, labels, coef, nvalid, R, C, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
-    return edgl_strip_label_scatter(rows, labels, coef, nvalid, R, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
+    if (!use_strip(C, dtype == EDGL_BF16 ? 2 : 4)) return EDGL_OK;
+    return edgl_strip_label_scatter(rows, labels, coef, nvalid, R, C, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
 }
 // edgl_score_flash_label_term as an ordered sum over a sorted plan (k_segsum.hip): no f32 atomics, one writer per table row, the
 // same no-op where the product pass already contains the one-hot term (EasyDGL.py:177-185).

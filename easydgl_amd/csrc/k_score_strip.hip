@@ -1,13 +1,13 @@
 // K5 "strip" kernels: the two passes of the fused scoring / cross-entropy (EasyDGL.py:149-155,177-185) at the headline width
 // (bf16, C = 128) in the one-wave-per-SIMD form.
 //
-//   ROLE_YF (x = compacted rows, z = items): one sweep over an item chunk computes the logits D[z][x] = Z[z].X[x] + bias[z], a running
-//            row reference m (natural-log units, deferred: it only moves when a unit's maximum exceeds it by more than 8) and the
+//   ROLE_YF (x = compacted rows, z = items): one sweep over an item chunk computes the logits D[z][x] = Z[z].X[x] + bias[z], a row
+//            reference m (natural-log units, fixed per item chunk: the maximum of the chunk's first 32 logits, strip_mma.h) and the
 //            unnormalised row gradient  O[x] = sum_z exp(D[z][x] - m[x]) Z[z]  together with  l[x] = sum_z exp(D[z][x] - m[x]).
 //   ROLE_W  (x = items, z = rows): with the row log-sum-exp known,  P[z][x] = coef[z] softmax(z)[x] = exp(D - lse'[z]),
 //            lse' = lse - log coef;  O[x] = sum_z P[z][x] Z[z]  (d_table without the label term) and  sum_z P[z][x]  (d_bias
 //            without the label term).  The label term  -coef[z] onehot(label[z])  is a scatter of R_w rows and is applied by
-//            label_scatter_kernel after the slab reduction: no compare / select per logit in the product loop.
+//            label_scatter_kernel (k_score_stripw.hip) after the slab reduction: no compare / select per logit in the product loop.
 //
 // Geometry: a workgroup = 4 waves = one wave per SIMD, 512 registers each; a wave owns 64 x vectors whose fragments (64
 // registers) and whose [64 x 128] f32 accumulator (128 registers) never leave the register file; z streams through LDS in
@@ -21,16 +21,15 @@
 // LDS image of a tile: row z at byte z*512 + rot(z)*16, rot(z) = ((z&3)<<2) | ((z>>2)&3): both the row-fragment reads (32 rows
 // x 16 B per half wave group) and the transpose reads (4 rows x 64 B per half wave) are bank-conflict free, and every
 // address is one lane register + an immediate.
-#include <atomic>
 #include <cstdlib>
 
 #include "edgl_common.h"
 #include "score_plan.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef int v4i __attribute__((ext_vector_type(4)));
+#include "score_strip.h"
+#include "strip_mma.h"
 
 namespace strip {
+using namespace strip_mma;
 
 constexpr int NTHR = 256, XW = 64, XB = 256, ZT = 64, ZU = 32, C = 128;
 constexpr int ROWB = 512;                   // LDS bytes per z row
@@ -42,10 +41,6 @@ constexpr int NSLOT = 4;
 constexpr int OSTR = 132;                   // floats per staged output row (epilogue)
 constexpr int SMEM_LOOP = NSLOT * SLOTB, SMEM_EPI = 4 * XW * OSTR * 4;
 constexpr int SMEM = SMEM_LOOP > SMEM_EPI ? SMEM_LOOP : SMEM_EPI;
-constexpr float L2E = 1.4426950408889634f;
-constexpr float THR2 = 8.0f * L2E;          // deferral threshold of the row reference, log2 units
-
-enum { ROLE_YF = 0, ROLE_W = 1 };
 
 struct StripP {
     const bf16* rows; const bf16* table; const float* out_bias;
@@ -66,35 +61,7 @@ __device__ unsigned long long g_ph[48];
 #define PHT(i)
 #endif
 
-__device__ __forceinline__ int rot16(int z) { return (((z & 3) << 2) | ((z >> 2) & 3)) * 16; }
-
-#define SPIN() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {   // one v_cvt_pk_bf16_f32 (RNE)
-    typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }   // v_max3_f32
-
-__device__ __forceinline__ v4i lds_b128(const char* p) { return *reinterpret_cast<const v4i*>(p); }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-// B operand of a 32x32x16 MFMA contracting along the rows of the tile: two transpose reads (slots 0-3: rows +0..3, slots 4-7:
-// rows +8..11 of this lane half's row group — the order in which P is packed from the logit registers)
-__device__ __forceinline__ v4i lds_tr(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    const s4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-    const s4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p + 8 * ROWB + 32));
-    const uint2 a = __builtin_bit_cast(uint2, v0), b = __builtin_bit_cast(uint2, v1);
-    return v4i{(int)a.x, (int)a.y, (int)b.x, (int)b.y};
-}
-
-// Per-lane LDS offsets (bytes, relative to a unit's first row)
-struct LaneOff {
-    int zf;   // row-fragment read: row l&31, k-slot hi        (+ ks*32)
-    int tr;   // transpose read: row 4hi + (s>>2), columns 16*(G&1) + 4*(s&3)   (+ ks2*16*ROWB + ct*64)
-    int ci;   // C operand of the logit rows: info floats 4hi .. 4hi+3   (+ g*32)
-};
+// Per-lane LDS offsets relative to a unit's first row (tr: + ks2*16*ROWB + ct*64)
 __device__ __forceinline__ LaneOff lane_off(int lane) {
     LaneOff o;
     const int zr = lane & 31, hi = lane >> 5, G = lane >> 4, s = lane & 15;
@@ -172,10 +139,7 @@ struct Carry {            // operands fetched one iteration ahead: first three r
 };
 __device__ __forceinline__ void fetch_ci(f32x16& ci, const char* info, const LaneOff& lo) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const f32x4 t = lds_f4(info + lo.ci + g * 32);
-        ci[4 * g] = t[0]; ci[4 * g + 1] = t[1]; ci[4 * g + 2] = t[2]; ci[4 * g + 3] = t[3];
-    }
+    for (int g = 0; g < 4; ++g) fetch_ci_part(ci, info, lo, g);
 }
 __device__ __forceinline__ void fetch_carry(Carry& cy, const char* unit, const char* info, const LaneOff& lo) {
     cy.zf0 = lds_b128(unit + lo.zf);
@@ -184,33 +148,7 @@ __device__ __forceinline__ void fetch_carry(Carry& cy, const char* unit, const c
     fetch_ci(cy.ci, info, lo);
 }
 
-// The MFMAs and the per-logit VALU work are asm statements, for two reasons.
-// (1) Register FILES: with 512 registers per wave the compiler selects the AGPR form for every builtin MFMA and then moves each
-//     logit through v_accvgpr_read before the VALU can touch it (144 moves per 32 MFMAs in the first build of this kernel;
-//     -amdgpu-mfma-vgpr-form crashes hipcc 7.2 here).  Fixed here:  logits S in VGPRs (exponentiated in place), x fragments XF
-//     in AGPRs (only ever an MFMA B operand; loaded straight into them), output O in AGPRs (only touched by MFMAs until the
-//     epilogue), P and the Z fragments in VGPRs.
-// (2) Placement: one wave per SIMD issues one instruction per ~4 cycles, so a 32-cycle MFMA hides ~7 other instructions and only
-//     if they sit next to it.  IR passes otherwise sink the conversions to the end of the iteration and pack the row sums into
-//     v_pk_add_f32 (slow beside MFMAs).  asm volatile statements keep their program order.
-// Hazards (guide §5.7): the compiler neither sees nor pads an instruction inside asm.  Every consumer of an MFMA result here is
-// either the next MFMA of the same accumulator chain (no wait states) or more than a full slot group later; a v_exp result is
-// first read one slot later (no trans -> VALU forwarding hazard); the places that read MFMA results directly (prologue maxima,
-// epilogue) sit behind settle_s() / settle_o().
-#ifdef STRIP_SAFE
-#define MFMA_PAD "\n\ts_nop 15\n\ts_nop 15"
-#else
-#define MFMA_PAD ""
-#endif
-__device__ __forceinline__ void mfma_s0(f32x16& d, const v4i& a, const v4i& b, const f32x16& c) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" MFMA_PAD : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-}
-__device__ __forceinline__ void mfma_s(f32x16& d, const v4i& a, const v4i& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" MFMA_PAD : "+v"(d) : "v"(a), "a"(b));
-}
-__device__ __forceinline__ void mfma_o(f32x16& d, const v4i& a, const v4i& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" MFMA_PAD : "+a"(d) : "v"(a), "v"(b));
-}
+// The MFMA slots (slot<KIND>, slot_tail, mfma_s0 / mfma_s / mfma_o) and their hazard rules: strip_mma.h.
 // Wait states before compiler code reads MFMA results.  The results are operands of the statement: a reader cannot be scheduled
 // above it (a bare asm volatile orders against memory operations only — the first build read the prologue logits 4 instructions
 // after their MFMA).
@@ -218,57 +156,6 @@ __device__ __forceinline__ void settle_s(f32x16& s0, f32x16& s1) { asm volatile(
 __device__ __forceinline__ void settle_o(f32x16 (&O)[2][4]) {
     asm volatile("s_nop 15\n\ts_nop 15" : "+a"(O[0][0]), "+a"(O[0][1]), "+a"(O[0][2]), "+a"(O[0][3]), "+a"(O[1][0]), "+a"(O[1][1]),
                  "+a"(O[1][2]), "+a"(O[1][3]));
-}
-
-// One MFMA slot = ONE asm statement: the MFMA and the VALU work on logit e (0..15) of the x tile T being exponentiated; no
-// instruction depends on a result of the same slot (one wave per SIMD: a dependent pair costs the full VALU latency), and separate
-// statements would draw a compiler s_nop between them (an issue slot each).
-//   T[e]   <- exp2(T[e])                      T[e] already holds  logit * log2(e) + add  (written one slot earlier)
-//   T[e+1] <- T[e+1] * log2(e) + add          (e = 0 also scales itself first)
-//   row sum += T[e-1];  after every odd logit the pair before it is packed
-// slot_tail() finishes the tile (sum / pack of logits 14, 15).
-#define VALU_E0 "v_fma_f32 %[cur], %[cur], %[l2e], %[add]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_exp_f32 %[cur], %[cur]"
-#define VALU_ODD "v_exp_f32 %[cur], %[cur]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_add_f32 %[sum], %[sum], %[p1]"
-#define VALU_EVEN VALU_ODD "\n\tv_cvt_pk_bf16_f32 %[pk], %[p2], %[p1]"
-#define VALU_E15 "v_exp_f32 %[cur], %[cur]\n\tv_add_f32 %[sum], %[sum], %[p1]"
-#define MF_S0 "v_mfma_f32_32x32x16_bf16 %[d], %[a], %[b], %[c]\n\t"
-#define MF_S "v_mfma_f32_32x32x16_bf16 %[d], %[a], %[b], %[d]\n\t"
-// kind 0: S MFMA with C = ci (D early-clobber VGPR), 1: S MFMA accumulating (D VGPR, B AGPR), 2: O MFMA (D AGPR, B VGPR)
-template <int KIND>
-__device__ __forceinline__ void slot(f32x16& d, const v4i& a, const v4i& b, const f32x16& c, f32x16& T, int (&pk)[8], float& lsum,
-                                     float add, int e) {
-    float cur = T[e], nxt = T[e < 15 ? e + 1 : 15];
-    int r = 0;
-#define SLOT_ASM(MF, VA, DC, BC)                                                                                                  \
-    asm volatile(MF VA : [d] DC(d), [cur] "+v"(cur), [nxt] "+v"(nxt), [sum] "+v"(lsum), [pk] "=&v"(r)                          \
-                 : [a] "v"(a), [b] BC(b), [l2e] "s"(L2E), [add] "v"(add), [p1] "v"(T[e >= 1 ? e - 1 : 0]), [p2] "v"(T[e >= 2 ? e - 2 : 0]))
-#define SLOT_ASM_C(MF, VA, DC, BC)                                                                                                \
-    asm volatile(MF VA : [d] DC(d), [cur] "+v"(cur), [nxt] "+v"(nxt), [sum] "+v"(lsum), [pk] "=&v"(r)                          \
-                 : [a] "v"(a), [b] BC(b), [c] "v"(c), [l2e] "s"(L2E), [add] "v"(add), [p1] "v"(T[e >= 1 ? e - 1 : 0]),             \
-                   [p2] "v"(T[e >= 2 ? e - 2 : 0]))
-    if (KIND == 0) {
-        if (e == 0) SLOT_ASM_C(MF_S0, VALU_E0, "=&v", "a");
-        else SLOT_ASM_C(MF_S0, VALU_ODD, "=&v", "a");          // (kind 0 occupies slots 0 and 1 only)
-    } else if (KIND == 1) {
-        if (e == 15) SLOT_ASM(MF_S, VALU_E15, "+v", "a");
-        else if (e & 1) SLOT_ASM(MF_S, VALU_ODD, "+v", "a");
-        else SLOT_ASM(MF_S, VALU_EVEN, "+v", "a");
-    } else {
-        if (e == 0) SLOT_ASM(MF_S, VALU_E0, "+a", "v");
-        else if (e == 15) SLOT_ASM(MF_S, VALU_E15, "+a", "v");
-        else if (e & 1) SLOT_ASM(MF_S, VALU_ODD, "+a", "v");
-        else SLOT_ASM(MF_S, VALU_EVEN, "+a", "v");
-    }
-#undef SLOT_ASM_C
-#undef SLOT_ASM
-    T[e] = cur;
-    if (e < 15) T[e + 1] = nxt;
-    if (e >= 2 && (e & 1) == 0) pk[(e - 2) >> 1] = r;
-}
-__device__ __forceinline__ void slot_tail(f32x16& T, int (&pk)[8], float& lsum) {
-    int r;
-    asm volatile("v_add_f32 %0, %0, %2\n\tv_cvt_pk_bf16_f32 %1, %3, %2" : "+v"(lsum), "=&v"(r) : "v"(T[15]), "v"(T[14]));
-    pk[7] = r;
 }
 
 // One pipeline iteration u: S(u+1) -> Sn, P(u) <- exp of Sc, O += P(u-1) . Z(u-1).
@@ -295,7 +182,7 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[2][4], const v4i (&XF)[2][
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
         if (ks + 3 < 8) zf[(ks + 3) % 4] = lds_b128(s_unit + lo.zf + (ks + 3) * 32);
-        if (ks >= 5) tf[ks - 5] = lds_tr(o_unit + lo.tr + (ks - 5) * 64);     // (tile u-1: resident long before this iteration)
+        if (ks >= 5) tf[ks - 5] = lds_tr<ROWB>(o_unit + lo.tr + (ks - 5) * 64);     // (tile u-1: resident long before this iteration)
 #pragma unroll
         for (int xt = 0; xt < 2; ++xt) {
             // (kind 0: slot 0 starts the x tile: VALU_E0; slot 1 is an odd slot)
@@ -326,7 +213,7 @@ __device__ __forceinline__ void unit_iter(f32x16 (&O)[2][4], const v4i (&XF)[2][
 #pragma unroll
     for (int f = 0; f < 8; ++f) {          // f = ks2 * 4 + ct
         const int ks2 = f >> 2, ct = f & 3;
-        if (f + 3 < 8) tf[(f + 3) % 4] = lds_tr(o_unit + lo.tr + ((f + 3) >> 2) * 16 * ROWB + ((f + 3) & 3) * 64);
+        if (f + 3 < 8) tf[(f + 3) % 4] = lds_tr<ROWB>(o_unit + lo.tr + ((f + 3) >> 2) * 16 * ROWB + ((f + 3) & 3) * 64);
         if (f == 4) cy.zf0 = lds_b128(nx_unit + lo.zf);
         if (f == 5) { fetch_ci(cy.ci, nx_info, lo); cy.zf1 = lds_b128(nx_unit + lo.zf + 32); }
         if (f == 6) cy.zf2 = lds_b128(nx_unit + lo.zf + 64);
@@ -366,15 +253,6 @@ __device__ __forceinline__ void max_unit(float (&mx)[2], const v4i (&XF)[2][8], 
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx[xt] = fmaxf(mx[xt], S[xt][r]);
 }
-
-// Reference of the row exponentials (ROLE_YF).  A flash-style running maximum would have to rescale the [64 x 128] accumulator
-// whenever it moves — code that touches O outside an MFMA, which drags the accumulators through VGPRs in every iteration (128
-// v_accvgpr moves + spills in the first build).  Instead the reference of a row is FIXED per item chunk: the maximum of the
-// chunk's first 32 logits.  exp(logit - ref) then exceeds 1 for larger logits, which f32 (and bf16: same exponent range, relative
-// precision) absorbs up to 2^100; a row sum beyond that makes the WORKGROUP redo its chunk with the exact row maxima from an
-// S-only sweep (attempt 1: exp <= 1, cannot overflow).  The finish kernels merge chunks from (reference, sum) pairs and do not
-// care which reference a chunk used.
-constexpr float LSUM_LIMIT = 1.2676506e30f;   // 2^100
 
 struct Geo {     // per-wave geometry of a launch
     const bf16* Z;
@@ -523,7 +401,7 @@ __device__ __forceinline__ void main_pass(const StripP& p, const Geo& g, char* s
         const char* o_unit = smem + ((ntile2 - 1) & 3) * SLOTB + UNITB;
 #pragma unroll
         for (int f = 0; f < 8; ++f) {
-            const v4i tf = lds_tr(o_unit + lo.tr + (f >> 2) * 16 * ROWB + (f & 3) * 64);
+            const v4i tf = lds_tr<ROWB>(o_unit + lo.tr + (f >> 2) * 16 * ROWB + (f & 3) * 64);
 #pragma unroll
             for (int xt = 0; xt < 2; ++xt) mfma_o(O[xt][f & 3], Pb[xt][f >> 2], tf);
         }
@@ -705,56 +583,6 @@ __global__ __launch_bounds__(NTHR, 1) void strip_kernel(StripP p) {
     }
 }
 
-// d_table[label[r]] -= coef[r] rows[r];  d_bias[label[r] - 1] -= coef[r]   over the weighted rows (label != 0): the one-hot part of
-// dl = coef (p - onehot) (Appendix C) that the ROLE_W product pass leaves out.  A block = 32 rows x 128 channels: rows with equal
-// labels are summed in LDS first, in row order by one thread per channel (hot items would otherwise serialise their atomics and
-// the sums of a block are formed in a fixed order); the leaders' sums leave as f32 atomics.
-__global__ __launch_bounds__(128) void label_scatter_kernel(const bf16* rows, const int64_t* labels, const float* coef,
-                                                            const int32_t* nvalid, int R, int i0, int i1, const float* gscale,
-                                                            float* d_table, float* d_bias) {
-    constexpr int RB = 32;
-    __shared__ float acc[RB][C];
-    __shared__ float accb[RB];
-    __shared__ int lab_s[RB], lead_s[RB];
-    __shared__ float cf_s[RB];
-    const int Reff = nvalid ? min(R, nvalid[0]) : R;
-    const int r0 = blockIdx.x * RB, tid = threadIdx.x;
-    if (r0 >= Reff) return;
-    const float gs = gscale ? gscale[0] : 1.0f;
-    float xv[RB];      // every row value of this thread's channel in flight before the first use
-#pragma unroll
-    for (int j = 0; j < RB; ++j) xv[j] = (float)rows[(long)min(r0 + j, Reff - 1) * C + tid];
-    if (tid < RB) {
-        const int r = r0 + tid;
-        const int64_t lb = labels[min(r, Reff - 1)];
-        const float cf = coef[min(r, Reff - 1)];
-        const bool on = r < Reff && lb != 0 && lb >= i0 && lb < i1 && cf != 0.f;
-        lab_s[tid] = on ? (int)lb : -1;
-        cf_s[tid] = on ? cf * gs : 0.f;
-        accb[tid] = 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < RB; ++j) acc[j][tid] = 0.f;
-    __syncthreads();
-    if (tid < RB) {   // leader = first row of the block with the same label
-        int lead = tid;
-        const int lb = lab_s[tid];
-        for (int j = tid - 1; j >= 0; --j)
-            if (lab_s[j] == lb) lead = j;
-        lead_s[tid] = lead;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RB; ++j) acc[lead_s[j]][tid] += cf_s[j] * xv[j];     // column `tid` is private to this thread
-    if (tid == 0)
-        for (int j = 0; j < RB; ++j) accb[lead_s[j]] += cf_s[j];
-    __syncthreads();
-#pragma unroll 4
-    for (int j = 0; j < RB; ++j)
-        if (lab_s[j] >= 0 && lead_s[j] == j) atomicAdd(d_table + (long)lab_s[j] * C + tid, -acc[j][tid]);
-    if (tid < RB && lab_s[tid] >= 0 && lead_s[tid] == tid) atomicAdd(d_bias + lab_s[tid] - 1, -accb[tid]);
-}
-
 }  // namespace strip
 
 // ---- host side (called from k_score.hip) --------------------------------------------------------------------------------------
@@ -768,21 +596,6 @@ bool edgl_strip_enabled() {
     return on != 0;
 }
 
-// The dynamic-LDS attribute of a kernel is PER DEVICE: one flag per (kernel, device ordinal), set with an atomic so that two host
-// threads driving different GPUs neither skip nor race it (a process-wide bool left the second device without the attribute).
-static void strip_set_smem_attr(const void* kern, int which) {
-    static std::atomic<uint64_t> done[2];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {   // unknown ordinal: set it on every launch
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, strip::SMEM);
-        return;
-    }
-    const uint64_t bit = 1ull << dev;
-    if (done[which].load(std::memory_order_acquire) & bit) return;
-    hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, strip::SMEM);
-    done[which].fetch_or(bit, std::memory_order_release);
-}
-
 int edgl_strip_rows(const void* rows, const void* table, const float* out_bias, int R, int I, int i0, int i1, const int32_t* nvalid,
                     float* slabs, float* part, int G, int slab16, hipStream_t st) {
     strip::StripP p{};
@@ -790,7 +603,8 @@ int edgl_strip_rows(const void* rows, const void* table, const float* out_bias, 
     p.rows = (const bf16*)rows; p.table = (const bf16*)table; p.out_bias = out_bias; p.R = R; p.I = I; p.i0 = i0; p.i1 = i1;
     p.nvalid = nvalid; p.slabs = slabs; p.part = part; p.stamps = g_strip_stamps;
     auto k = strip::strip_kernel<strip::ROLE_YF>;
-    strip_set_smem_attr((const void*)k, 0);
+    static std::atomic<uint64_t> attr_done;
+    edgl_strip_set_smem_attr((const void*)k, strip::SMEM, attr_done);
     hipLaunchKernelGGL(k, dim3(G), dim3(strip::NTHR), strip::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -804,16 +618,9 @@ int edgl_strip_table(const void* rows, const void* table, const float* out_bias,
     p.rows = (const bf16*)rows; p.table = (const bf16*)table; p.out_bias = out_bias; p.R = R; p.I = I; p.i0 = i0; p.i1 = i1;
     p.nvalid = nvalid; p.coef = coef; p.row_lse = row_lse; p.slabs = slabs; p.bias_slabs = bias_slabs; p.stamps = g_strip_stamps;
     auto k = strip::strip_kernel<strip::ROLE_W>;
-    strip_set_smem_attr((const void*)k, 1);
+    static std::atomic<uint64_t> attr_done;
+    edgl_strip_set_smem_attr((const void*)k, strip::SMEM, attr_done);
     hipLaunchKernelGGL(k, dim3((i1 - i0 + strip::XB - 1) / strip::XB, nchunk), dim3(strip::NTHR), strip::SMEM, st, p);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-
-int edgl_strip_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int i0, int i1,
-                             const float* gscale, float* d_table, float* d_bias, hipStream_t st) {
-    hipLaunchKernelGGL(strip::label_scatter_kernel, dim3((R + 31) / 32), dim3(128), 0, st, (const bf16*)rows, labels, coef, nvalid, R,
-                       i0, i1, gscale, d_table, d_bias);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

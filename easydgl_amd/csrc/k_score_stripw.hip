@@ -25,16 +25,15 @@
 // Geometry: 4 waves = one per SIMD, 512 registers each; z streams through LDS in 32-row units, ring of SEVEN: the loads of unit
 // u+5 are issued in the second half of iteration u (behind the barrier: the slot of unit u-2 is free), unit u+2 must have
 // landed at iteration u's barrier (s_waitcnt vmcnt(8): the two younger units stay in flight) — three iterations ~ 3 us of cover.
-#include <atomic>
 #include <cstdlib>
 
 #include "edgl_common.h"
 #include "score_plan.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef int v4i __attribute__((ext_vector_type(4)));
+#include "score_strip.h"
+#include "strip_mma.h"
 
 namespace stripw {
+using namespace strip_mma;
 
 constexpr int NTHR = 256, XW = 32, XB = 128, ZU = 32, ZQ = 128;     // ZQ: chunk granularity of the planners
 constexpr int INFOB = 256;                 // one global_load_lds_dword: 64 floats (the unit's 32 + the next unit's, unused)
@@ -43,8 +42,6 @@ static_assert(AHEAD >= 3 && AHEAD <= 5, "ring of 5 .. 7 units");
 constexpr int CPAD = 512;                  // -inf entries behind the C-operand arrays (units past a chunk's end read them)
 constexpr int PF = 6, RING = 8;    // operand prefetch distance (MFMA slots) / ring size
 static_assert(PF >= 2 && PF < RING, "operand rings");
-constexpr float L2E = 1.4426950408889634f;
-constexpr float LSUM_LIMIT = 1.2676506e30f;   // 2^100
 
 template <int CW>
 struct W {
@@ -61,8 +58,6 @@ struct W {
     static_assert(KS == 16 && CT == 8 && 2 * CW * 2 == 1024, "the slot schedule and the one-KB blocks below are written for C = 256");
 };
 
-enum { ROLE_YF = 0, ROLE_W = 1 };
-
 struct StripP {
     const bf16* rows; const bf16* table; const float* out_bias;
     int R, I, i0, i1;
@@ -72,28 +67,8 @@ struct StripP {
     float* slabs; float* bias_slabs; float* part;
 };
 
-__device__ __forceinline__ int rot16(int z) { return (((z & 3) << 2) | ((z >> 2) & 3)) * 16; }
-#define SPIN() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __forceinline__ v4i lds_b128(const char* p) { return *reinterpret_cast<const v4i*>(p); }
-__device__ __forceinline__ f32x4 lds_f4(const char* p) { return *reinterpret_cast<const f32x4*>(p); }
-// B operand of a 32x32x16 MFMA contracting along the rows of the unit: two transpose reads (slots 0-3: rows +0..3, slots 4-7:
-// rows +8..11 of this lane half's row group — the order in which P is packed from the logit registers)
-template <int BLKB>
-__device__ __forceinline__ v4i lds_tr(const char* p) {
-    typedef __attribute__((ext_vector_type(4))) short s4;
-    const s4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)p);
-    const s4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(p + 8 * BLKB + 32));   // rows + 8: rot + 2
-    const uint2 a = __builtin_bit_cast(uint2, v0), b = __builtin_bit_cast(uint2, v1);
-    return v4i{(int)a.x, (int)a.y, (int)b.x, (int)b.y};
-}
-
-// Per-lane LDS offsets (bytes, relative to a unit's first block).  Row z of a unit: block z & 15, second half of it for z >= 16.
-struct LaneOff {
-    int zf;   // row-fragment read: row l&31, k-slot hi        (+ ks*32)
-    int tr;   // transpose read: row 4hi + (s>>2), columns 16*(G&1) + 4*(s&3)   (+ ks2*512 + ct*64; rows + 8: lds_tr)
-    int ci;   // C operand of the logit rows: info floats 4hi .. 4hi+3   (+ g*32)
-};
+// Per-lane LDS offsets relative to a unit's first block (tr: + ks2*512 + ct*64; rows + 8: lds_tr).  Row z of a unit: block z & 15,
+// second half of it for z >= 16.
 template <int BLKB>
 __device__ __forceinline__ LaneOff lane_off(int lane) {
     LaneOff o;
@@ -152,76 +127,11 @@ struct Dma {
 // load has issued since the unit waited for
 #define VM_WAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 
-__device__ __forceinline__ void fetch_ci_part(f32x16& ci, const char* info, const LaneOff& lo, int g) {
-    const f32x4 t = lds_f4(info + lo.ci + g * 32);
-    ci[4 * g] = t[0]; ci[4 * g + 1] = t[1]; ci[4 * g + 2] = t[2]; ci[4 * g + 3] = t[3];
-}
-
-// MFMAs and the per-logit VALU work as asm statements (register files and placement: see k_score_strip.hip).  Logits S in VGPRs
-// (exponentiated in place), x fragments XF and the output O in AGPRs, P and the Z fragments in VGPRs.  Every consumer of an MFMA
-// result is either the next MFMA of the same accumulator chain (no wait states) or more than a full slot group later; the places
-// that read MFMA results directly (prologue maxima, epilogue) sit behind settle_s() / settle_o().
-#ifdef STRIP_SAFE
-#define MFMA_PAD "\n\ts_nop 15\n\ts_nop 15"
-#else
-#define MFMA_PAD ""
-#endif
-__device__ __forceinline__ void mfma_s0(f32x16& d, const v4i& a, const v4i& b, const f32x16& c) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" MFMA_PAD : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-}
-__device__ __forceinline__ void mfma_s(f32x16& d, const v4i& a, const v4i& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" MFMA_PAD : "+v"(d) : "v"(a), "a"(b));
-}
-__device__ __forceinline__ void mfma_o(f32x16& d, const v4i& a, const v4i& b) {
-    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" MFMA_PAD : "+a"(d) : "v"(a), "v"(b));
-}
+// The MFMA slots (slot<KIND>, slot_tail, mfma_s0 / mfma_s / mfma_o) and their hazard rules: strip_mma.h.  Wait states before compiler
+// code reads MFMA results (the results are operands of the statement: a reader cannot be scheduled above it):
 __device__ __forceinline__ void settle_s(f32x16& s0) { asm volatile("s_nop 15\n\ts_nop 15" : "+v"(s0)); }
 __device__ __forceinline__ void settle_o(f32x16 (&O)[8]) {
     asm volatile("s_nop 15\n\ts_nop 15" : "+a"(O[0]), "+a"(O[1]), "+a"(O[2]), "+a"(O[3]), "+a"(O[4]), "+a"(O[5]), "+a"(O[6]), "+a"(O[7]));
-}
-
-// One S slot = ONE asm statement: the MFMA and the VALU work on logit e (0..15) of the unit being exponentiated (the stream of
-// strip::slot: T[e] <- exp2(T[e]); T[e+1] scaled; row sum += T[e-1]; after every odd logit the pair before it is packed).
-#define VALU_E0 "v_fma_f32 %[cur], %[cur], %[l2e], %[add]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_exp_f32 %[cur], %[cur]"
-#define VALU_ODD "v_exp_f32 %[cur], %[cur]\n\tv_fma_f32 %[nxt], %[nxt], %[l2e], %[add]\n\tv_add_f32 %[sum], %[sum], %[p1]"
-#define VALU_EVEN VALU_ODD "\n\tv_cvt_pk_bf16_f32 %[pk], %[p2], %[p1]"
-#define VALU_E15 "v_exp_f32 %[cur], %[cur]\n\tv_add_f32 %[sum], %[sum], %[p1]"
-#define MF_S0 "v_mfma_f32_32x32x16_bf16 %[d], %[a], %[b], %[c]\n\t"
-#define MF_S "v_mfma_f32_32x32x16_bf16 %[d], %[a], %[b], %[d]\n\t"
-// kind 0: S MFMA with C = ci (D early-clobber VGPR; logit 0), 1: S MFMA accumulating, 2: O MFMA (D AGPR, B VGPR)
-template <int KIND>
-__device__ __forceinline__ void slot(f32x16& d, const v4i& a, const v4i& b, const f32x16& c, f32x16& T, int (&pk)[8], float& lsum,
-                                     float add, int e) {
-    float cur = T[e], nxt = T[e < 15 ? e + 1 : 15];
-    int r = 0;
-#define SLOT_ASM(MF, VA, DC, BC)                                                                                               \
-    asm volatile(MF VA : [d] DC(d), [cur] "+v"(cur), [nxt] "+v"(nxt), [sum] "+v"(lsum), [pk] "=&v"(r)                          \
-                 : [a] "v"(a), [b] BC(b), [l2e] "s"(L2E), [add] "v"(add), [p1] "v"(T[e >= 1 ? e - 1 : 0]), [p2] "v"(T[e >= 2 ? e - 2 : 0]))
-#define SLOT_ASM_C(MF, VA, DC, BC)                                                                                             \
-    asm volatile(MF VA : [d] DC(d), [cur] "+v"(cur), [nxt] "+v"(nxt), [sum] "+v"(lsum), [pk] "=&v"(r)                          \
-                 : [a] "v"(a), [b] BC(b), [c] "v"(c), [l2e] "s"(L2E), [add] "v"(add), [p1] "v"(T[e >= 1 ? e - 1 : 0]),             \
-                   [p2] "v"(T[e >= 2 ? e - 2 : 0]))
-    if (KIND == 0) {
-        SLOT_ASM_C(MF_S0, VALU_E0, "=&v", "a");
-    } else if (KIND == 1) {
-        if (e == 15) SLOT_ASM(MF_S, VALU_E15, "+v", "a");
-        else if (e & 1) SLOT_ASM(MF_S, VALU_ODD, "+v", "a");
-        else SLOT_ASM(MF_S, VALU_EVEN, "+v", "a");
-    } else {
-        if (e == 15) SLOT_ASM(MF_S, VALU_E15, "+a", "v");
-        else if (e & 1) SLOT_ASM(MF_S, VALU_ODD, "+a", "v");
-        else SLOT_ASM(MF_S, VALU_EVEN, "+a", "v");
-    }
-#undef SLOT_ASM_C
-#undef SLOT_ASM
-    T[e] = cur;
-    if (e < 15) T[e + 1] = nxt;
-    if (e >= 2 && (e & 1) == 0) pk[(e - 2) >> 1] = r;
-}
-__device__ __forceinline__ void slot_tail(f32x16& T, int (&pk)[8], float& lsum) {
-    int r;
-    asm volatile("v_add_f32 %0, %0, %2\n\tv_cvt_pk_bf16_f32 %1, %3, %2" : "+v"(lsum), "=&v"(r) : "v"(T[15]), "v"(T[14]));
-    pk[7] = r;
 }
 
 struct Carry {            // operands of the next iteration's first PF S slots and the C rows of its logits, fetched in the O half
@@ -875,9 +785,10 @@ __global__ __launch_bounds__(NTHR, 1) void stripw5_kernel(StripP p) {
     }
 }
 
-// d_table[label[r]] -= coef[r] rows[r];  d_bias[label[r] - 1] -= coef[r]   over the weighted rows: the one-hot part of
-// dl = coef (p - onehot) that the ROLE_W product pass leaves out (strip::label_scatter_kernel at any width: a block = RB rows x CW
-// channels, equal labels summed in LDS first in row order by one thread per channel, the leaders' sums leave as f32 atomics).
+// d_table[label[r]] -= coef[r] rows[r];  d_bias[label[r] - 1] -= coef[r]   over the weighted rows (label != 0): the one-hot part of
+// dl = coef (p - onehot) (Appendix C) that the ROLE_W product pass of every width leaves out — C = 128 (strip::strip_kernel) included.
+// A block = RB rows x CW channels: rows with equal labels are summed in LDS first, in row order by one thread per channel (hot items
+// would otherwise serialise their atomics and the sums of a block are formed in a fixed order); the leaders' sums leave as f32 atomics.
 template <int CW, int RB>
 __global__ __launch_bounds__(CW) void label_scatter_kernel(const bf16* rows, const int64_t* labels, const float* coef,
                                                            const int32_t* nvalid, int R, int i0, int i1, const float* gscale,
@@ -890,7 +801,7 @@ __global__ __launch_bounds__(CW) void label_scatter_kernel(const bf16* rows, con
     const int r0 = blockIdx.x * RB, tid = threadIdx.x;
     if (r0 >= Reff) return;
     const float gs = gscale ? gscale[0] : 1.0f;
-    float xv[RB];
+    float xv[RB];      // every row value of this thread's channel in flight before the first use
 #pragma unroll
     for (int j = 0; j < RB; ++j) xv[j] = (float)rows[(long)min(r0 + j, Reff - 1) * CW + tid];
     if (tid < RB) {
@@ -954,20 +865,6 @@ bool edgl_stripw_supports(int C) {      // 256: stripw_kernel; 512: stripw5_kern
     return C == 256 || (C == 512 && on512 != 0);
 }
 
-// the dynamic-LDS attribute of a kernel is per device (see k_score_strip.hip)
-static void stripw_set_smem_attr(const void* kern, int which, int bytes) {
-    static std::atomic<uint64_t> done[4];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        return;
-    }
-    const uint64_t bit = 1ull << dev;
-    if (done[which].load(std::memory_order_acquire) & bit) return;
-    hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done[which].fetch_or(bit, std::memory_order_release);
-}
-
 // floats of scratch a pass needs for its C operands (edgl_stripw_rows: n = i1 - i0; edgl_stripw_table: n = R)
 long edgl_stripw_info_floats(long n) { return n + stripw::CPAD; }
 
@@ -982,13 +879,15 @@ int edgl_stripw_rows(const void* rows, const void* table, const float* out_bias,
     p.nvalid = nvalid; p.slabs = slabs; p.part = part; p.cinfo = info_ws; p.ncinfo = n;
     if (C == 512) {
         auto k5 = stripw::stripw5_kernel<stripw::ROLE_YF>;
-        stripw_set_smem_attr((const void*)k5, 2, stripw::C5::SMEM);
+        static std::atomic<uint64_t> attr_done5;
+        edgl_strip_set_smem_attr((const void*)k5, stripw::C5::SMEM, attr_done5);
         hipLaunchKernelGGL(k5, dim3(2 * G), dim3(stripw::NTHR), stripw::C5::SMEM, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
     }
     auto k = stripw::stripw_kernel<stripw::ROLE_YF, 256>;
-    stripw_set_smem_attr((const void*)k, 0, stripw::W<256>::SMEM);
+    static std::atomic<uint64_t> attr_done;
+    edgl_strip_set_smem_attr((const void*)k, stripw::W<256>::SMEM, attr_done);
     hipLaunchKernelGGL(k, dim3(G), dim3(stripw::NTHR), stripw::W<256>::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -1006,27 +905,30 @@ int edgl_stripw_table(const void* rows, const void* table, const float* out_bias
     p.nvalid = nvalid; p.slabs = slabs; p.bias_slabs = bias_slabs; p.cinfo = info_ws; p.ncinfo = n;
     if (C == 512) {
         auto k5 = stripw::stripw5_kernel<stripw::ROLE_W>;
-        stripw_set_smem_attr((const void*)k5, 3, stripw::C5::SMEM);
+        static std::atomic<uint64_t> attr_done5;
+        edgl_strip_set_smem_attr((const void*)k5, stripw::C5::SMEM, attr_done5);
         hipLaunchKernelGGL(k5, dim3((i1 - i0 + stripw::XB - 1) / stripw::XB, nchunk, 2), dim3(stripw::NTHR), stripw::C5::SMEM, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
     }
     auto k = stripw::stripw_kernel<stripw::ROLE_W, 256>;
-    stripw_set_smem_attr((const void*)k, 1, stripw::W<256>::SMEM);
+    static std::atomic<uint64_t> attr_done;
+    edgl_strip_set_smem_attr((const void*)k, stripw::W<256>::SMEM, attr_done);
     hipLaunchKernelGGL(k, dim3((i1 - i0 + stripw::XB - 1) / stripw::XB, nchunk), dim3(stripw::NTHR), stripw::W<256>::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
 
-int edgl_stripw_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int C, int i0,
-                              int i1, const float* gscale, float* d_table, float* d_bias, hipStream_t st) {
-    EDGL_REQUIRE(edgl_stripw_supports(C), EDGL_ERR_SHAPE, "edgl_stripw_label_scatter: C=%d unsupported", C);
-    if (C == 512)
-        hipLaunchKernelGGL((stripw::label_scatter_kernel<512, 16>), dim3((R + 15) / 16), dim3(512), 0, st, (const bf16*)rows, labels, coef,
-                           nvalid, R, i0, i1, gscale, d_table, d_bias);
-    else
-        hipLaunchKernelGGL((stripw::label_scatter_kernel<256, 32>), dim3((R + 31) / 32), dim3(256), 0, st, (const bf16*)rows, labels, coef,
-                           nvalid, R, i0, i1, gscale, d_table, d_bias);
+int edgl_strip_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int C, int i0,
+                             int i1, const float* gscale, float* d_table, float* d_bias, hipStream_t st) {
+    EDGL_REQUIRE(C == 128 || edgl_stripw_supports(C), EDGL_ERR_SHAPE, "edgl_strip_label_scatter: C=%d unsupported", C);
+#define EDGL_LABEL_SCATTER(CW, RB)                                                                                                    \
+    hipLaunchKernelGGL((stripw::label_scatter_kernel<CW, RB>), dim3((R + RB - 1) / RB), dim3(CW), 0, st, (const bf16*)rows, labels, coef, \
+                       nvalid, R, i0, i1, gscale, d_table, d_bias)
+    if (C == 512) EDGL_LABEL_SCATTER(512, 16);
+    else if (C == 256) EDGL_LABEL_SCATTER(256, 32);
+    else EDGL_LABEL_SCATTER(128, 32);
+#undef EDGL_LABEL_SCATTER
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

@@ -118,6 +118,19 @@ def test_graft_entry_build():
     assert os.path.exists(os.path.join(ROOT, "easydgl_amd", "libeasydgl_hip.so"))
 
 
+def test_every_csrc_header_is_a_build_input():
+    """build.HEADERS feeds the content digest of every object: a header missing from it means stale objects after an edit."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_edgl_build_hdrs", os.path.join(ROOT, "easydgl_amd", "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    on_disk = {f for f in os.listdir(b.CSRC) if f.endswith(".h")}
+    assert on_disk, "no headers found"
+    assert on_disk <= set(b.HEADERS), sorted(on_disk - set(b.HEADERS))
+    for h in b.HEADERS:
+        assert os.path.exists(os.path.join(b.CSRC, h)), h
+
+
 def test_bench_flop_model_matches_the_survey_numbers():
     """179.9 MFLOP per sequence forward at the headline configuration (M = 20), 108.2 at M = 6; x3 for fwd+bwd."""
     import importlib.util

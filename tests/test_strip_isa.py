@@ -15,24 +15,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
-@pytest.fixture(scope="module")
-def strip_asm():
+def _device_asm(unit):
+    """Builds csrc/<unit>.hip with the flags of build.py and yields the path of its gfx950 assembly."""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not available")
-    sys.path.insert(0, os.path.join(ROOT, "easydgl_amd"))
     import importlib.util
-    spec = importlib.util.spec_from_file_location("_edgl_build", os.path.join(ROOT, "easydgl_amd", "build.py"))
+    spec = importlib.util.spec_from_file_location("_edgl_build_" + unit, os.path.join(ROOT, "easydgl_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    d = tempfile.mkdtemp(prefix="strip_isa_")
-    flags = b.FLAGS + b.EXTRA_FLAGS["k_score_strip.hip"]
-    src = os.path.join(ROOT, "easydgl_amd", "csrc", "k_score_strip.hip")
-    r = subprocess.run([HIPCC] + flags + ["-save-temps=obj", "-c", src, "-o", os.path.join(d, "strip.o")], capture_output=True, text=True, cwd=d)
+    d = tempfile.mkdtemp(prefix=unit + "_isa_")
+    flags = b.FLAGS + b.EXTRA_FLAGS[unit + ".hip"]
+    src = os.path.join(ROOT, "easydgl_amd", "csrc", unit + ".hip")
+    r = subprocess.run([HIPCC] + flags + ["-save-temps=obj", "-c", src, "-o", os.path.join(d, unit + ".o")], capture_output=True, text=True, cwd=d)
     assert r.returncode == 0, r.stderr[-3000:]
-    path = os.path.join(d, "k_score_strip-hip-amdgcn-amd-amdhsa-gfx950.s")
+    path = os.path.join(d, unit + "-hip-amdgcn-amd-amdhsa-gfx950.s")
     assert os.path.exists(path)
     yield path
     shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture(scope="module")
+def strip_asm():
+    yield from _device_asm("k_score_strip")
 
 
 @pytest.mark.parametrize("kernel", ["strip_kernelILi0", "strip_kernelILi1", "fallback_exact"])
@@ -66,21 +70,7 @@ def test_hot_loops_are_free_of_spills_and_accumulator_moves(strip_asm, kernel):
 # ---- compiler-visible global loads (every vmcnt in it is placed by hand)
 @pytest.fixture(scope="module")
 def stripw_asm():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_edgl_build_w", os.path.join(ROOT, "easydgl_amd", "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    d = tempfile.mkdtemp(prefix="stripw_isa_")
-    flags = b.FLAGS + b.EXTRA_FLAGS["k_score_stripw.hip"]
-    src = os.path.join(ROOT, "easydgl_amd", "csrc", "k_score_stripw.hip")
-    r = subprocess.run([HIPCC] + flags + ["-save-temps=obj", "-c", src, "-o", os.path.join(d, "stripw.o")], capture_output=True, text=True, cwd=d)
-    assert r.returncode == 0, r.stderr[-3000:]
-    path = os.path.join(d, "k_score_stripw-hip-amdgcn-amd-amdhsa-gfx950.s")
-    assert os.path.exists(path)
-    yield path
-    shutil.rmtree(d, ignore_errors=True)
+    yield from _device_asm("k_score_stripw")
 
 
 @pytest.mark.parametrize("kernel", ["stripw_kernelILi0", "stripw_kernelILi1", "fallback_exactILi256", "stripw5_kernelILi0", "stripw5_kernelILi1", "fallback_exact5"])
