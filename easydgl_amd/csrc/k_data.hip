@@ -9,28 +9,40 @@ namespace {
 // M DISTINCT positions in [1, T) per row, uniformly at random (any M-subset equally likely, in random order — the
 // semantics of np.random.choice(T-1, M, replace=False) + 1): every position gets a counter-based 32-bit key from
 // (seed, step, stream, row, position); the M positions with the smallest (key, position) are taken, rank = output slot.
-__global__ __launch_bounds__(256) void mask_random_kernel(const int64_t* tokens, int T, int M, int64_t mask_id,
-                                                          const uint64_t* rng, uint32_t stream_id, int64_t* masked,
-                                                          int64_t* mpos, int64_t* labels) {
-    extern __shared__ uint32_t keys[];   // [T] (entry 0 unused: position 0 is never drawn, ignore_head = 1)
-    const int b = blockIdx.x;
-    const int64_t* row = tokens + (long)b * T;
-    const DropKey dk = make_dropkey(rng, stream_id, 0.f);
+// The key and the rank are these two functions and nothing else: mask_random_kernel and the resident-split loader
+// (loader_batch_kernel) both call them, so a batch row gets the same draws from either.
+// keys: LDS [T] (entry 0 unused: position 0 is never drawn, ignore_head = 1); called by the whole workgroup, ends in a barrier.
+__device__ __forceinline__ void mask_keys_fill(uint32_t* keys, const DropKey& dk, int b, int T) {
     for (int t = threadIdx.x; t < T; t += blockDim.x) {
         uint32_t h = ((uint32_t)(b * T + t) ^ dk.k0) * 0x9E3779B1u + dk.k1;
         h ^= h >> 15; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
         keys[t] = h;
     }
     __syncthreads();
+}
+// rank of position t (>= 1) among the positions [1, T) by (key, position): t is drawn iff rank < M, into output slot `rank`
+__device__ __forceinline__ int mask_rank(const uint32_t* keys, int t, int T) {
+    const uint32_t k = keys[t];
+    int rank = 0;
+    for (int j = 1; j < T; ++j) {
+        const uint32_t kj = keys[j];
+        rank += (kj < k) || (kj == k && j < t);
+    }
+    return rank;
+}
+
+__global__ __launch_bounds__(256) void mask_random_kernel(const int64_t* tokens, int T, int M, int64_t mask_id,
+                                                          const uint64_t* rng, uint32_t stream_id, int64_t* masked,
+                                                          int64_t* mpos, int64_t* labels) {
+    extern __shared__ uint32_t keys[];   // [T]
+    const int b = blockIdx.x;
+    const int64_t* row = tokens + (long)b * T;
+    const DropKey dk = make_dropkey(rng, stream_id, 0.f);
+    mask_keys_fill(keys, dk, b, T);
     for (int t = threadIdx.x; t < T; t += blockDim.x) {
         int64_t tok = row[t];
         if (t >= 1) {
-            const uint32_t k = keys[t];
-            int rank = 0;
-            for (int j = 1; j < T; ++j) {
-                const uint32_t kj = keys[j];
-                rank += (kj < k) || (kj == k && j < t);
-            }
+            const int rank = mask_rank(keys, t, T);
             if (rank < M) {
                 mpos[(long)b * M + rank] = t;
                 labels[(long)b * M + rank] = tok;
@@ -39,6 +51,67 @@ __global__ __launch_bounds__(256) void mask_random_kernel(const int64_t* tokens,
         }
         masked[(long)b * T + t] = tok;
     }
+}
+
+// ---- Resident training split -> batch.  tokens int64 [N,T] / times f32 [N,T] stay on the device for the whole run;
+//      one workgroup assembles output row b from source row perm[cursor + b] (perm NULL: cursor + b) in one of four forms:
+//      MASK_RANDOM (mask_random_kernel's draws for batch row b), MASK_LAST (mask_last_kernel), REG_TRAIN / REG_EVAL
+//      (train.regressive_batch).  state = uint64 {seed, step, cursor, reserved}: the first two words ARE the masker's rng_state.
+//      Everything that changes from batch to batch is READ from `state`, so the launch is the same in every replay of a captured
+//      graph; loader_advance_kernel moves step / cursor in a launch of its own behind it (other workgroups of the batch launch
+//      still read them).  A source position outside [0, N) — the host cannot see a device cursor — or a permutation entry outside
+//      [0, N) gives an EMPTY row: ids 0, times 0, labels 0, and (MASK_RANDOM) the M drawn positions, which are valid by themselves.
+struct LoaderP {
+    const int64_t* tokens; const float* times; const int32_t* perm; long N; int T, M, mode; int64_t mask_id;
+    const uint64_t* state; uint32_t stream_id; int64_t* seqs_i; float* seqs_t; int64_t* mpos; int64_t* labels;
+};
+__global__ __launch_bounds__(256) void loader_batch_kernel(LoaderP p) {
+    extern __shared__ uint32_t keys[];   // [T] (MASK_RANDOM only)
+    const int b = blockIdx.x, T = p.T, M = p.M;
+    const uint64_t cursor = p.state[2];
+    long src = -1;
+    if (cursor < (uint64_t)p.N && cursor + (uint64_t)b < (uint64_t)p.N) {
+        const long pos = (long)cursor + b;
+        src = p.perm ? (long)p.perm[pos] : pos;
+        if (src < 0 || src >= p.N) src = -1;
+    }
+    const int64_t* row = src >= 0 ? p.tokens + src * T : nullptr;
+    const float* trow = src >= 0 ? p.times + src * T : nullptr;
+    for (int t = threadIdx.x; t < T; t += blockDim.x) p.seqs_t[(long)b * T + t] = trow ? trow[t] : 0.f;
+    if (p.mode == EDGL_LOADER_MASK_RANDOM) {
+        const DropKey dk = make_dropkey(p.state, p.stream_id, 0.f);
+        mask_keys_fill(keys, dk, b, T);
+        for (int t = threadIdx.x; t < T; t += blockDim.x) {
+            int64_t tok = row ? row[t] : 0;
+            if (t >= 1) {
+                const int rank = mask_rank(keys, t, T);
+                if (rank < M) {
+                    p.mpos[(long)b * M + rank] = t;
+                    p.labels[(long)b * M + rank] = tok;
+                    if (row) tok = p.mask_id;
+                }
+            }
+            p.seqs_i[(long)b * T + t] = tok;
+        }
+    } else if (p.mode == EDGL_LOADER_MASK_LAST) {
+        for (int t = threadIdx.x; t < T; t += blockDim.x) {
+            const int64_t tok = row ? row[t] : 0;
+            p.labels[(long)b * T + t] = tok;
+            p.seqs_i[(long)b * T + t] = (row && t == T - 1) ? p.mask_id : tok;
+        }
+    } else {   // REG_TRAIN / REG_EVAL: seqs_i = tokens[:-1]; labels = tokens[1:] (training) or the whole record (evaluation)
+        const bool train = p.mode == EDGL_LOADER_REG_TRAIN;
+        for (int t = threadIdx.x; t < T; t += blockDim.x) {
+            const int64_t tok = row ? row[t] : 0;
+            if (t < T - 1) p.seqs_i[(long)b * (T - 1) + t] = tok;
+            if (!train) p.labels[(long)b * T + t] = tok;
+            else if (t >= 1) p.labels[(long)b * (T - 1) + t - 1] = tok;
+        }
+    }
+}
+__global__ void loader_advance_kernel(uint64_t* state, int count) {
+    state[1] += 1;
+    state[2] += (uint64_t)count;
 }
 
 __global__ void mask_last_kernel(const int64_t* tokens, long n, int T, int64_t mask_id, int64_t* masked) {
@@ -235,6 +308,35 @@ extern "C" int edgl_mask_last(const int64_t* tokens, int B, int T, int64_t mask_
     const long n = (long)B * T;
     hipLaunchKernelGGL(mask_last_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 2048)), dim3(256), 0,
                        (hipStream_t)stream, tokens, n, T, mask_id, masked_tokens);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
+extern "C" int edgl_loader_state_words(void) { return 4; }
+
+extern "C" int edgl_loader_batch(const int64_t* tokens, const float* times, const int32_t* perm, long N, int T, int count, int mode,
+                                 int M, int64_t mask_id, const uint64_t* state, uint32_t stream_id, int64_t* seqs_i, float* seqs_t,
+                                 int64_t* masked_pos, int64_t* labels, void* stream) {
+    EDGL_REQUIRE(mode >= EDGL_LOADER_MASK_RANDOM && mode <= EDGL_LOADER_REG_EVAL, EDGL_ERR_SHAPE, "edgl_loader_batch: unknown mode %d", mode);
+    EDGL_REQUIRE(tokens && times && state && seqs_i && seqs_t && labels, EDGL_ERR_NULL, "edgl_loader_batch: null pointer");
+    EDGL_REQUIRE(mode != EDGL_LOADER_MASK_RANDOM || masked_pos, EDGL_ERR_NULL, "edgl_loader_batch: null pointer (masked_pos)");
+    EDGL_REQUIRE(N >= 1 && N <= 0x7fffffffL, EDGL_ERR_SHAPE, "edgl_loader_batch: bad split size N=%ld", N);
+    EDGL_REQUIRE(T >= 2, EDGL_ERR_SHAPE, "edgl_loader_batch: need T >= 2 (T=%d)", T);
+    EDGL_REQUIRE(count >= 1, EDGL_ERR_SHAPE, "edgl_loader_batch: need count >= 1 (count=%d)", count);
+    EDGL_REQUIRE(mode != EDGL_LOADER_MASK_RANDOM || (M >= 1 && M <= T - 1), EDGL_ERR_SHAPE,
+                 "edgl_loader_batch: need 1 <= masklen <= T-1 (T=%d masklen=%d)", T, M);
+    EDGL_REQUIRE((size_t)T * sizeof(uint32_t) <= 64 * 1024, EDGL_ERR_SHAPE, "edgl_loader_batch: T=%d too long", T);
+    LoaderP p{tokens, times, perm, N, T, M, mode, mask_id, state, stream_id, seqs_i, seqs_t, masked_pos, labels};
+    const size_t smem = mode == EDGL_LOADER_MASK_RANDOM ? (size_t)T * sizeof(uint32_t) : 0;
+    hipLaunchKernelGGL(loader_batch_kernel, dim3(count), dim3(256), smem, (hipStream_t)stream, p);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
+extern "C" int edgl_loader_advance(uint64_t* state, int count, void* stream) {
+    EDGL_REQUIRE(state, EDGL_ERR_NULL, "edgl_loader_advance: null pointer");
+    EDGL_REQUIRE(count >= 1, EDGL_ERR_SHAPE, "edgl_loader_advance: need count >= 1 (count=%d)", count);
+    hipLaunchKernelGGL(loader_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, state, count);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

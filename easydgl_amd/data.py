@@ -61,6 +61,144 @@ def device_mask_last(tokens: torch.Tensor, timestamps: torch.Tensor, mask_id: in
     return {"seqs_i": masked, "seqs_t": timestamps}, tokens
 
 
+LOADER_MODES = {"mask_random": 0, "mask_last": 1, "regressive_train": 2, "regressive_eval": 3}   # EDGL_LOADER_* of the header
+
+
+class DeviceSplit:
+    """A whole split (train / valid / test) resident in device memory: tokens int64 [N, T], times float32 [N, T], uploaded ONCE.
+    The Netflix recipe's training split is ~180 MB; `nbytes(ids, ts)` is what the upload takes."""
+
+    def __init__(self, ids, ts, device="cuda"):
+        ids, ts = np.ascontiguousarray(ids, dtype=np.int64), np.ascontiguousarray(ts, dtype=np.float32)
+        if ids.ndim != 2 or ids.shape != ts.shape or ids.shape[0] < 1 or ids.shape[1] < 2:
+            raise ValueError(f"DeviceSplit: ids / ts must be [N >= 1, T >= 2] arrays of one shape (got {ids.shape} / {ts.shape})")
+        if ids.shape[0] > 2 ** 31 - 1:
+            raise ValueError("DeviceSplit: the permutation is int32: at most 2^31 - 1 sequences")
+        self.tokens = torch.as_tensor(ids).to(device)
+        self.times = torch.as_tensor(ts).to(device)
+        self.N, self.T = int(ids.shape[0]), int(ids.shape[1])
+
+    @staticmethod
+    def nbytes(ids, ts) -> int:
+        return int(np.prod(ids.shape)) * 8 + int(np.prod(ts.shape)) * 4
+
+    def __len__(self):
+        return self.N
+
+
+class DeviceLoader:
+    """Batches of a DeviceSplit, assembled by ONE kernel launch each (edgl_loader_batch) + a one-thread launch that advances the
+    device-side (step, cursor) pair (edgl_loader_advance) — no host indexing, no host-to-device copy per batch.
+
+    mode: "mask_random" (EasyDGL training: the draws of `device_mask_random` for the same (seed, step, stream_id), batch row by
+    batch row), "mask_last" (EasyDGL evaluation), "regressive_train" / "regressive_eval" (`train.regressive_batch`).
+    The host draws the epoch's order (`set_epoch(rng.permutation(N))`): batch k of the epoch holds rows perm[k*B : (k+1)*B], as on
+    the host path.  The mask step counter runs on across epochs; `set_epoch` resets the cursor only.
+    `full_batches` / `remainder` / `len()`: N // B, N % B and the steps of an epoch (the remainder batch counts as a step)."""
+
+    def __init__(self, split: DeviceSplit, batch: int, mode: str = "mask_random", mask_id: int = 0, masklen: int = 0, seed: int = 0,
+                 stream_id: int = 0x4d41534b):
+        if mode not in LOADER_MODES:
+            raise ValueError(f"DeviceLoader: unknown mode {mode!r} (one of {sorted(LOADER_MODES)})")
+        if batch < 1:
+            raise ValueError("DeviceLoader: batch must be >= 1")
+        if mode == "mask_random" and not (1 <= masklen <= split.T - 1):
+            raise ValueError("masklen must be in [1, seqslen - 1]")
+        self.split, self.batch, self.mode, self.code = split, int(batch), mode, LOADER_MODES[mode]
+        self.mask_id, self.masklen, self.stream_id = int(mask_id), int(masklen) if mode == "mask_random" else 0, int(stream_id)
+        self.full_batches, self.remainder = divmod(split.N, self.batch)
+        dev = split.tokens.device
+        # { seed, step, cursor, reserved }: words 0..1 are the masker's rng_state (include/easydgl_hip.h)
+        self.state = torch.tensor([int(seed), 0, 0, 0], dtype=torch.int64, device=dev)
+        self.perm = None        # int32 [N] on the device once an order was set (None: identity, the kernel's NULL)
+        self._pos = 0           # host mirror of the cursor: how many rows of the epoch were handed out (sizes next()'s batch)
+
+    def __len__(self):
+        return self.full_batches + (1 if self.remainder else 0)
+
+    def remaining(self) -> int:
+        """Rows of the epoch not handed out yet (host mirror of the device cursor)."""
+        return max(self.split.N - self._pos, 0)
+
+    def pin_order(self) -> None:
+        """Give the order a device buffer of its own now (identity if none was set): a captured graph keeps its address."""
+        if self.perm is None:
+            self.perm = torch.arange(self.split.N, dtype=torch.int32, device=self.split.tokens.device)
+
+    def set_epoch(self, perm=None) -> None:
+        """Start an epoch: one small upload of the host-drawn order (None: identity) and a cursor reset."""
+        N = self.split.N
+        if perm is None:
+            if self.perm is not None:
+                self.perm.copy_(torch.arange(N, dtype=torch.int32, device=self.perm.device))
+        else:
+            perm = np.asarray(perm)
+            if perm.shape != (N,):
+                raise ValueError(f"DeviceLoader.set_epoch: the order must have {N} entries (got shape {perm.shape})")
+            host = torch.as_tensor(perm.astype(np.int32))
+            if self.perm is None:
+                self.perm = host.to(self.split.tokens.device)
+            else:
+                self.perm.copy_(host)
+        self.state[2:3].zero_()
+        self._pos = 0
+
+    def _shapes(self, count: int):
+        T, M = self.split.T, self.masklen
+        if self.mode == "mask_random":
+            return (count, T), (count, M), (count, M)
+        if self.mode == "mask_last":
+            return (count, T), None, (count, T)
+        return (count, T - 1), None, ((count, T - 1) if self.mode == "regressive_train" else (count, T))
+
+    def write_into(self, seqs_i, seqs_t, mpos, labels, count: int = None) -> None:
+        """Batch at the device cursor into the caller's buffers (row-major, at least `count` rows; default: a full batch), then the
+        advance — two launches on the current stream, both capturable.  Rows past the end of the split come out empty."""
+        from . import ops
+        from ._lib import check, lib
+        count = self.batch if count is None else int(count)
+        si, mp, lb = self._shapes(count)
+        for t, shape, dt, nm in ((seqs_i, si, torch.int64, "seqs_i"), (seqs_t, (count, self.split.T), torch.float32, "seqs_t"),
+                                 (mpos, mp, torch.int64, "masked_positions"), (labels, lb, torch.int64, "labels")):
+            if shape is None:
+                continue
+            if t is None or t.dtype != dt or t.dim() != 2 or t.shape[0] < shape[0] or t.shape[1] != shape[1]:
+                raise ValueError(f"DeviceLoader.write_into: {nm} must be a {dt} tensor of at least {shape}")
+        sp, st = self.split, ops._stream()
+        check(lib.edgl_loader_batch(ops._ptr(sp.tokens), ops._ptr(sp.times), ops._ptr(self.perm), sp.N, sp.T, count, self.code,
+                                    self.masklen, self.mask_id, ops._ptr(self.state), self.stream_id, ops._ptr(seqs_i), ops._ptr(seqs_t),
+                                    ops._ptr(mpos) if mp is not None else None, ops._ptr(labels), st), "edgl_loader_batch")
+        check(lib.edgl_loader_advance(ops._ptr(self.state), count, st), "edgl_loader_advance")
+        if not torch.cuda.is_current_stream_capturing():
+            self._pos += count
+
+    def note_replay(self) -> None:
+        """A captured pair of launches (a full batch) ran once more: keep the host mirror of the cursor in step."""
+        self._pos += self.batch
+
+    def next(self):
+        """The next batch as FRESH tensors: (features, labels) as `device_mask_random` / `device_mask_last` /
+        `train.regressive_batch` return them — a full batch, or what is left of the epoch (the remainder batch)."""
+        count = min(self.batch, self.remaining())
+        if count < 1:
+            raise StopIteration("DeviceLoader.next: the epoch is exhausted (set_epoch starts the next one)")
+        si, mp, lb = self._shapes(count)
+        dev = self.split.tokens.device
+        seqs_i = torch.empty(si, device=dev, dtype=torch.int64)
+        seqs_t = torch.empty((count, self.split.T), device=dev, dtype=torch.float32)
+        mpos = torch.empty(mp, device=dev, dtype=torch.int64) if mp is not None else None
+        labels = torch.empty(lb, device=dev, dtype=torch.int64)
+        self.write_into(seqs_i, seqs_t, mpos, labels, count)
+        feats = {"seqs_i": seqs_i, "seqs_t": seqs_t}
+        if mpos is not None:
+            feats["masked_positions"] = mpos
+        return feats, labels
+
+    def cursor(self) -> int:
+        """The device cursor (a synchronising read: tests and diagnostics)."""
+        return int(self.state[2])
+
+
 def synthetic_batch(num_items: int, seqslen: int, batch: int, seed: int = 9876, min_len: int = 5, ids: str = "zipf"):
     """SURVEY.md §8d synthetic sequences: row length ~ U{min_len..T}, left zero padding, Zipf(1.1) item ids
     clipped to [1, num_items-1], float32 timestamps 9.5e8 + cumsum(Exp(mean 3 days)).  T = seqslen + 1.

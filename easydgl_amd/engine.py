@@ -77,6 +77,11 @@ class TrainEngine:
         self.deterministic = bool(getattr(model, "deterministic", False)) if deterministic is None else bool(deterministic)
         self.group = process_group
         self.graph: Optional[torch.cuda.CUDAGraph] = None
+        # resident-split loader (attach_loader): step() without arguments draws the next batch of the epoch into the
+        # static batch buffers by the loader's two launches at the top of _issue()
+        self.loader = None
+        self._feed = False            # this _issue() starts with the loader's launches (set by step() only)
+        self._graph_feeds = False     # the captured sequence holds them
         m = model
         dev = m._arena.device
         self.dev = dev
@@ -328,6 +333,10 @@ class TrainEngine:
         # (fold_slabs: step() lets the optimizer launch sum the scoring gradient's slabs — see __init__)
         self._fold = bool(fold_slabs) and self._slab_info is not None and bool(self.blk) and not self._dp
         self._slabs = None
+        if self._feed:
+            # the batch of this step, straight into the static buffers: main stream, where load_batch's four copies stand on the host
+            # path — every side stream waits for the main stream in _issue_side_chain before it reads ids / ts / mpos / labels
+            self.loader.write_into(self.ids, self.ts, self.mpos, self.labels)
         if not self._fold:
             m._table_grad_zero = None      # (this issue's slab reduction ASSIGNS the table / bias gradient)
         drop = lambda rate, sid: ops.Drop(rate, m._rng_state, sid) if rate > 0 else ops.NO_DROP  # noqa: E731
@@ -895,6 +904,28 @@ class TrainEngine:
                 raise _lib.EdglError(f"TrainEngine.bind_batch: {nm} must be a contiguous {tuple(ref.shape)} {ref.dtype} tensor on {ref.device}")
         self.ids, self.ts, self.mpos, self.labels = new
 
+    def attach_loader(self, loader) -> None:
+        """Feed the engine from a data.DeviceLoader in "mask_random" mode over a resident split: step() WITHOUT arguments then
+        draws batch k of the epoch on the device (two launches in front of the step's own; with use_graph=True they are captured
+        with it, and an epoch is n replays with no host data work).  The caller runs exactly `loader.full_batches` such steps per
+        epoch (the capture's warm-up step is a real step and consumes a batch); the remainder batch goes through `loader.next()`
+        and the autograd path.  step(features, labels) keeps working on an eager engine.  Single process only."""
+        if self.group is not None:
+            raise _lib.EdglError("TrainEngine.attach_loader: a loader cannot be combined with a process_group — sharding the "
+                                 "resident split over data-parallel ranks is not implemented")
+        if self.graph is not None:
+            raise _lib.EdglError("TrainEngine.attach_loader: the step is already captured; attach the loader before the first step()")
+        if getattr(loader, "mode", None) != "mask_random":
+            raise _lib.EdglError("TrainEngine.attach_loader: the engine trains on masked batches: the loader's mode must be 'mask_random'")
+        if (loader.batch, loader.split.T, loader.masklen) != (self.B, self.T, self.M):
+            raise _lib.EdglError(f"TrainEngine.attach_loader: loader (batch {loader.batch}, T {loader.split.T}, masklen {loader.masklen}) "
+                                 f"does not match the engine (batch {self.B}, T {self.T}, masklen {self.M})")
+        if loader.split.tokens.device != self.ids.device:
+            raise _lib.EdglError(f"TrainEngine.attach_loader: the split lives on {loader.split.tokens.device}, the engine on {self.ids.device}")
+        if self.use_graph:
+            loader.pin_order()      # (the captured launch keeps the address of the order: set_epoch copies into this buffer from now on)
+        self.loader = loader
+
     def _global_counts(self) -> None:
         """Data parallel: the two normalisers of the loss that are sums over the BATCH — the number of weighted rows
         (EasyDGL.py:183-185) and the number of next-event marks of the TPP term (temporal.py:331-333) — are all-reduced before the
@@ -945,10 +976,24 @@ class TrainEngine:
         is the loss of that concatenated batch, the same number on every rank (_dp_allreduce); `self.loss` stays this rank's
         share + L2 as its kernels wrote it."""
         if features is not None:
+            if self._graph_feeds:
+                raise _lib.EdglError("TrainEngine.step: the captured step draws its batch from the attached loader; it takes no batch")
             self.load_batch(features, labels)
         distributed = torch.distributed.is_available() and torch.distributed.is_initialized() and \
             torch.distributed.get_world_size(self.group) > 1
         self._dp = distributed
+        feed = self.loader is not None and features is None
+        if feed and distributed:
+            raise _lib.EdglError("TrainEngine.step: the attached loader is single-process (no data-parallel sharding of the split)")
+        if feed != self._graph_feeds and self.graph is not None:
+            raise _lib.EdglError("TrainEngine.step: the loader was attached after the step was captured")
+        try:
+            self._feed = feed
+            return self._step(distributed)
+        finally:
+            self._feed = False
+
+    def _step(self, distributed: bool) -> torch.Tensor:
         if not self.use_graph:
             if distributed:
                 self._global_counts()
@@ -991,6 +1036,7 @@ class TrainEngine:
             assert self.m._state_ahead
             self.m._state_pinned = True      # (the captured launches keep the counters' addresses: no engine swaps them from here on)
             self.graph = torch.cuda.CUDAGraph()
+            self._graph_feeds = self._feed
             with torch.cuda.graph(self.graph):
                 self._issue()
                 if not distributed:
@@ -1005,6 +1051,8 @@ class TrainEngine:
         if not self.m._state_ahead:   # somebody settled the counters (a checkpoint, an autograd-path step)
             self._advance_state(_stream())
         self.graph.replay()
+        if self._graph_feeds:
+            self.loader.note_replay()
         self.m._state_ahead = not self._distributed       # the captured optimizer ends with the next step's counters
         if self._distributed:
             out = self._dp_allreduce()

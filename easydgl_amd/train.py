@@ -10,7 +10,9 @@ Same flags as ``main.py:22-75`` for everything these paths read (``--train/--val
 kernel per batch), then validation and test passes with the last position masked, model selection on validation H@100,
 patience 10, stop on a NaN loss, best checkpoint kept.  Differences, stated: records are shuffled with a full
 permutation per epoch (the reference: file-order shuffle + a 64-record buffer, ``dataloader.py:222-236``); full batches
-run through the static ``TrainEngine`` and the remainder batch through ``model.train_step``.
+run through the static ``TrainEngine`` and the remainder batch through ``model.train_step``.  ``--device_data`` keeps the
+three splits in device memory and assembles the same batches there (``data.DeviceLoader``); with ``--graph`` the
+EasyDGL step is then replayed as one HIP graph.
 
 ``python -m easydgl_amd.train --model EasyDGL --train 'data/train*.tfrec' --valid data/validation.tfrec
 --test data/test.tfrec --num_items 17770 --mark data/mark.pkl ...`` (``.npz`` files from ``formats.convert`` work too).
@@ -60,7 +62,11 @@ def args(argv=None):
     p.add_argument("--seed", type=int, default=9876)   # main.py:156-159
     p.add_argument("--patience", type=int, default=10)
     p.add_argument("--graph", action="store_true",
-                   help="regressive models: replay the training step of full batches as one HIP graph (Sequential.graphed_train_step)")
+                   help="regressive models: replay the training step of full batches as one HIP graph (Sequential.graphed_train_step); "
+                        "with --device_data also EasyDGL: the engine's step is captured together with the on-device batch loader")
+    p.add_argument("--device_data", action="store_true",
+                   help="keep the train / valid / test splits in device memory and assemble every batch there (data.DeviceLoader): no "
+                        "host indexing and no host-to-device copy per step; refused when the splits do not fit in free device memory")
     p.add_argument("--deterministic", action="store_true",
                    help="EasyDGL: bitwise reproducible training (main.py:157-168 pins TF_DETERMINISTIC_OPS): the item-table gradient "
                         "as ordered sums instead of f32 atomics, in the engine and in train_step")
@@ -143,12 +149,19 @@ def regressive_batch(tok, tim, is_training: bool):
     return {"seqs_i": tok[:, :-1].contiguous(), "seqs_t": tim}, (tok[:, 1:].contiguous() if is_training else tok)
 
 
-def evaluate(model, ids, ts, batch_size: int, mask_seen: bool) -> Dict[str, float]:
+def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
-    prefix (regressive models), streaming means."""
+    prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
+    (--device_data) — the batches are then assembled on the device, in file order."""
     import torch
     from . import data as D
     model.reset_metrics()
+    if loader is not None:
+        loader.set_epoch(None)
+        for _ in range(len(loader)):
+            feats, labels = loader.next()
+            model.eval_step(feats, labels, mask_seen=mask_seen)
+        return model.metrics()
     n = ids.shape[0]
     masked = hasattr(model, "mask")
     for lo in range(0, n, batch_size):
@@ -189,7 +202,26 @@ def run(FLAGS) -> Dict[str, float]:
         for name, (ii, tt) in (("train", (tr_i, tr_t)), ("valid", (vl_i, vl_t)), ("test", (te_i, te_t))):
             if np.any((np.diff(tt, axis=1) < 0) & (ii[:, :-1] != 0)):
                 raise ValueError(f"{name}: timestamps decrease inside a sequence; TGAT needs time-sorted records")
-    engine = TrainEngine(model, bs, use_graph=False) if (masked and len(tr_i) >= bs) else None
+    device_data = bool(getattr(FLAGS, "device_data", False))
+    # --device_data --graph: the batch no longer arrives from the host, so the EasyDGL step can be replayed as one graph
+    engine_graph = device_data and bool(getattr(FLAGS, "graph", False))
+    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs) else None
+    loader = vl_loader = te_loader = None
+    if device_data:
+        need = sum(D.DeviceSplit.nbytes(ii, tt) + 4 * len(ii) for ii, tt in ((tr_i, tr_t), (vl_i, vl_t), (te_i, te_t)))
+        free = torch.cuda.mem_get_info()[0]
+        if need > free:
+            raise RuntimeError(f"--device_data: the splits need {need} bytes of device memory, {free} bytes are free; "
+                               "run without --device_data (batches from the host)")
+        mask_id = int(model.mask) if masked else 0
+        loader = D.DeviceLoader(D.DeviceSplit(tr_i, tr_t), bs, "mask_random" if masked else "regressive_train", mask_id,
+                                FLAGS.masklen if masked else 0, FLAGS.seed)
+        emode = "mask_last" if masked else "regressive_eval"
+        vl_loader = D.DeviceLoader(D.DeviceSplit(vl_i, vl_t), bs, emode, mask_id)
+        te_loader = D.DeviceLoader(D.DeviceSplit(te_i, te_t), bs, emode, mask_id)
+        logging.info("   splits resident on the device: %d bytes", need)
+        if engine is not None:
+            engine.attach_loader(loader)
     if engine is not None:
         # the loss is read every 10 batches (NaN test) and once per epoch: the engine leaves its loss launches off the step
         # (they ride with the next step) and adds the step losses up on the device — the mode bench.py times
@@ -210,15 +242,22 @@ def run(FLAGS) -> Dict[str, float]:
         if engine is not None:
             engine.join_loss()
             engine.loss_sum.zero_()
+        if loader is not None:
+            loader.set_epoch(order)      # the one upload of the epoch: same order, hence the same batches and mask draws as below
         for lo in range(0, len(order), bs):
             idx = order[lo:lo + bs]
-            tok = torch.as_tensor(tr_i[idx]).cuda()
-            tim = torch.as_tensor(tr_t[idx]).cuda()
-            if masked:
-                feats, labels = D.device_mask_random(tok, tim, model.mask, FLAGS.masklen, mask_state)
-                mask_state[1] += 1
+            if loader is not None:
+                # full EasyDGL batches: the attached loader writes the engine's buffers inside engine.step(); everything else
+                # (remainder batch, regressive models) takes fresh tensors from the same device cursor
+                feats, labels = (None, None) if (engine is not None and len(idx) == bs) else loader.next()
             else:
-                feats, labels = regressive_batch(tok, tim, True)
+                tok = torch.as_tensor(tr_i[idx]).cuda()
+                tim = torch.as_tensor(tr_t[idx]).cuda()
+                if masked:
+                    feats, labels = D.device_mask_random(tok, tim, model.mask, FLAGS.masklen, mask_state)
+                    mask_state[1] += 1
+                else:
+                    feats, labels = regressive_batch(tok, tim, True)
             if engine is not None and len(idx) == bs:
                 engine.step(feats, labels)
                 loss = None      # (added to engine.loss_sum by the engine's own loss launches)
@@ -248,9 +287,9 @@ def run(FLAGS) -> Dict[str, float]:
             break
         if epoch % FLAGS.eval_per_steps:
             continue
-        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen)
+        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader)
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
-        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen)
+        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader)
         if stopper.step(running_loss, vl["H100"], vl, te):
             break
     return stopper.summary()

@@ -76,6 +76,28 @@ int edgl_mask_random(const int64_t* tokens, int B, int T, int M, int64_t mask_id
                      void* stream);
 int edgl_mask_last(const int64_t* tokens, int B, int T, int64_t mask_id, int64_t* masked_tokens, void* stream);
 
+/* ---- K0b: batches from a split that lives on the device ---------------------------
+ * tokens int64 [N,T] / times f32 [N,T]: a whole split, uploaded once.  perm int32 [N] or NULL (identity): the epoch's order.
+ * state: device uint64[edgl_loader_state_words()] = { seed, step, cursor, reserved } — words 0..1 are the rng_state of
+ * edgl_mask_random.  edgl_loader_batch writes `count` rows (one workgroup each); output row b takes source row
+ * perm[cursor + b].  cursor and step are READ FROM THE DEVICE, never passed by value: the same launch serves every replay of a
+ * captured graph.  edgl_loader_advance (one thread: step += 1, cursor += count) follows it in stream order; the batch launch
+ * never advances them itself (its other workgroups still read them).
+ *   EDGL_LOADER_MASK_RANDOM  seqs_i [count,T], seqs_t [count,T], masked_pos [count,M], labels [count,M] — bit for bit what
+ *                            edgl_mask_random(tokens[perm[cursor..]], ..., state, stream_id) gives: the draws of BATCH row b
+ *   EDGL_LOADER_MASK_LAST    seqs_i [count,T] with position T-1 := mask_id, seqs_t, labels [count,T] = the record (masked_pos unused)
+ *   EDGL_LOADER_REG_TRAIN    seqs_i [count,T-1] = tokens[:, :-1], seqs_t [count,T], labels [count,T-1] = tokens[:, 1:]
+ *   EDGL_LOADER_REG_EVAL     seqs_i [count,T-1] = tokens[:, :-1], seqs_t [count,T], labels [count,T] = the record
+ * A row whose source position cursor + b is >= N (or whose permutation entry is outside [0,N)) comes out EMPTY: ids 0, times 0,
+ * labels 0, masked_pos the M distinct drawn positions in [1,T) — the host cannot check a device-side cursor, the kernel does.
+ * Refused before any launch: null pointers, T < 2, masklen < 1 or > T-1 (MASK_RANDOM), count < 1, N < 1, an unknown mode. */
+enum { EDGL_LOADER_MASK_RANDOM = 0, EDGL_LOADER_MASK_LAST = 1, EDGL_LOADER_REG_TRAIN = 2, EDGL_LOADER_REG_EVAL = 3 };
+int edgl_loader_state_words(void);
+int edgl_loader_batch(const int64_t* tokens, const float* times, const int32_t* perm, long N, int T, int count, int mode,
+                      int M, int64_t mask_id, const uint64_t* state, uint32_t stream_id, int64_t* seqs_i, float* seqs_t,
+                      int64_t* masked_pos, int64_t* labels, void* stream);
+int edgl_loader_advance(uint64_t* state, int count, void* stream);
+
 /* ---- K1: input encoding — EasyDGL.py:70-95, coding.py:60-64,76-79,137-149 ---------------------
  * x0[b,t,:]   = [ item_tab[id]*sqrt(C) + sincos(ts/time_scale) | pos_tab[t] | nmarks*mark_emb[1] ]
  *               followed by hidden dropout (EasyDGL.py:92);
