@@ -13,6 +13,7 @@
 // LayerNorm reads them, two-pass moments, the same dropout element indices), so both paths produce the same tensors.
 // bf16, C in {64, 128}, T <= 112.
 #include "edgl_common.h"
+#include <mutex>      // std::once_flag
 
 #ifdef EDGL_PHASE_TIMING
 __device__ unsigned long long g_phase_cycles[16];   // see edgl_common.h (PH_MARK); read back with edgl_debug_phase_cycles_tail
@@ -525,13 +526,17 @@ __device__ __forceinline__ void tile_dx(const WFrags<NKB>& wf, const bf16* Gs, i
 
 // LayerNorm backward on registers: z = LN input sum, dy = upstream gradient; returns d(sum) in dz and writes the
 // per-sample (dbeta | dgamma) partials of this wave's channels
-template <int CT>
-__device__ __forceinline__ void ln_bwd_regs(const float (&z)[MAXRT][4], const float (&dy)[MAXRT][4], float mean, float rstd,
+// (ln_bwd_part: the partials of lane l15 == 0 are returned in dga / dbe instead of stored — the two-per-CU kernel stores them with
+// the store batch that ends its phase, so that no load of the phase waits behind them)
+template <int CT, bool STORE>
+__device__ __forceinline__ void ln_bwd_part(const float (&z)[MAXRT][4], const float (&dy)[MAXRT][4], float mean, float rstd,
                                             const float (&gv)[4], int nrt, int T, int lane, int nl, float* red, float* part_b,
-                                            float (&dz)[MAXRT][4], const ChanPad& cp) {
+                                            float (&dz)[MAXRT][4], const ChanPad& cp, float (&dga)[4], float (&dbe)[4]) {
     const int l15 = lane & 15;
     const float n = (float)T * cp.ctrue;      // (gamma is 0 on padded channels: they add nothing to s1 / s2)
-    float s1 = 0.f, s2 = 0.f, dga[4] = {0.f, 0.f, 0.f, 0.f}, dbe[4] = {0.f, 0.f, 0.f, 0.f};
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dga[r] = dbe[r] = 0.f;
 #pragma unroll
     for (int rt = 0; rt < MAXRT; ++rt)
         if (rt < nrt && rt * 16 + l15 < T) {
@@ -548,7 +553,7 @@ __device__ __forceinline__ void ln_bwd_regs(const float (&z)[MAXRT][4], const fl
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) { dga[r] += __shfl_xor(dga[r], o, 64); dbe[r] += __shfl_xor(dbe[r], o, 64); }
     }
-    if (l15 == 0) {
+    if (STORE && l15 == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { part_b[nl + r] = dbe[r]; part_b[16 * CT + nl + r] = dga[r]; }
     }
@@ -558,7 +563,15 @@ __device__ __forceinline__ void ln_bwd_regs(const float (&z)[MAXRT][4], const fl
         for (int r = 0; r < 4; ++r) {
             const float xh = (z[rt][r] - mean) * rstd;
             dz[rt][r] = cp.rm[r] * (rstd * (dy[rt][r] * gv[r] - m1 - xh * m2));      // nothing flows into a padded channel
+            if (!STORE && r == 3) __builtin_amdgcn_sched_barrier(0);      // (two-per-CU form: one row tile at a time, 128 registers)
         }
+}
+template <int CT>
+__device__ __forceinline__ void ln_bwd_regs(const float (&z)[MAXRT][4], const float (&dy)[MAXRT][4], float mean, float rstd,
+                                            const float (&gv)[4], int nrt, int T, int lane, int nl, float* red, float* part_b,
+                                            float (&dz)[MAXRT][4], const ChanPad& cp) {
+    float dga[4], dbe[4];
+    ln_bwd_part<CT, true>(z, dy, mean, rstd, gv, nrt, T, lane, nl, red, part_b, dz, cp, dga, dbe);
 }
 
 template <int CT, int NRT>
@@ -880,7 +893,8 @@ __global__ __launch_bounds__(64 * CT) void tail_bwd_kernel(TailBwdP p) {
 //   * <= 128 registers (4 waves per SIMD): no operand is prefetched a whole segment ahead — the other workgroup of the CU is
 //     what runs while a load is in flight —, the LayerNorm inputs of the backward come straight from global memory in the
 //     accumulator layout (8 bytes per lane and row tile) instead of through LDS images held in registers one phase ahead.
-// Same arithmetic, in the same order, as the kernels above: the outputs are bit-identical (tests/test_gpu_tail2.py).
+// Same arithmetic, in the same order, as the kernels above: the outputs are bit-identical (tests/test_gpu_tail2.py,
+// tests/test_gpu_tail_bwd2.py).
 // =========================================================================================================================
 namespace t2 {
 constexpr int C = 128, NTHR = 512, NKB = 4, TMAX = 101;
@@ -899,15 +913,24 @@ struct Lane {
     int quad;           // byte offset of this lane's 4 channels in row l15 of an image (+ rt * 4096)
     int squad;          // the same in the f32 staging image (+ rt * 8192)
 };
-__device__ __forceinline__ Lane make_lane() {
+__device__ __forceinline__ Lane make_lane(int tid) {
     Lane L;
-    L.lane = threadIdx.x & 63; L.wave = threadIdx.x >> 6; L.q = L.lane >> 4; L.l15 = L.lane & 15; L.nl = L.wave * 16 + L.q * 4;
+    L.lane = tid & 63; L.wave = tid >> 6; L.q = L.lane >> 4; L.l15 = L.lane & 15; L.nl = L.wave * 16 + L.q * 4;
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) L.frag[kb] = L.l15 * 256 + (((kb * 4 + L.q) ^ L.l15) << 4);
     L.quad = L.l15 * 256 + (((L.wave * 2 + (L.q >> 1)) ^ L.l15) << 4) + ((L.q & 1) << 3);
     L.squad = L.l15 * 512 + (((L.wave * 4 + L.q) ^ L.l15) << 4);
     return L;
 }
+__device__ __forceinline__ Lane make_lane() { return make_lane(threadIdx.x); }
+// The same, rebuilt from an opaque copy of the thread index: the backward keeps no operand offset alive from one segment to the next
+// (held for the whole kernel they went to scratch, and a reload from scratch waits on vmcnt like any load — behind the stores)
+__device__ __forceinline__ int fresh_tid() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+__device__ __forceinline__ Lane fresh_lane() { return make_lane(fresh_tid()); }
 __device__ __forceinline__ int vec_off(int row, int cv) { return row * 256 + ((cv ^ (row & 15)) << 4); }
 
 // acc[rt] += W^T[16 output channels][128 k] . X[rows of tile rt][k] over a swizzled image.  Rows >= T of the last tile(s) read
@@ -1186,6 +1209,365 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     }
 }
 
+// ---- backward on half a CU ---------------------------------------------------------------------------------------------------------
+// This lane's quads (4 channels, one row per row tile: the accumulator layout) of a global [T, 128] tensor, 8 bytes per lane and row
+// tile; rows past the sequence repeat row T - 1 (nothing consumes them: every sum and every store is guarded by row < T).
+struct Quads { uint2 q[MAXRT]; };
+template <int NRT>
+__device__ __forceinline__ Quads load_quads(const bf16* src, int ld, int T) {
+    Quads a;
+    // uniform base + 32-bit lane offset (one address register per load, not two), rebuilt by every call: held, the clamped offsets of
+    // all row tiles are seven registers per row stride
+    const Lane L = fresh_lane();
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt)
+        a.q[rt] = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(src) + (uint32_t)((min(rt * 16 + L.l15, T - 1) * ld + L.nl) * 2));
+#pragma unroll
+    for (int rt = NRT; rt < MAXRT; ++rt) a.q[rt] = make_uint2(0u, 0u);
+    return a;
+}
+__device__ __forceinline__ void quad_f32(const uint2& q, float (&v)[4]) {
+    Frag4<bf16> f;
+    *reinterpret_cast<uint2*>(&f) = q;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = to_f32(f.v[r]);
+}
+// byte offset of this lane's 4 channels in row `row` of an image (any row: the gathered rows of the head)
+__device__ __forceinline__ int quad_off(int row, const Lane& L) {
+    return row * 256 + (((L.wave * 2 + (L.q >> 1)) ^ (row & 15)) << 4) + ((L.q & 1) << 3);
+}
+// per-sample (dbeta | dgamma) partials of this wave's channels (ln_bwd_part<8, false>)
+__device__ __forceinline__ void store_part(float* part_b, const Lane& L, const float (&dga)[4], const float (&dbe)[4]) {
+    if (L.l15 == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { part_b[L.nl + r] = dbe[r]; part_b[C + L.nl + r] = dga[r]; }
+    }
+}
+
+// copy_out with the thread's offsets rebuilt by every call (uniform base + 32-bit lane offset)
+__device__ __forceinline__ void copy_out_b(bf16* dst, int ld, const char* img, int T) {
+    const int nv = T * 16, tid = fresh_tid();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int v = tid + i * NTHR, row = v >> 4, cv = v & 15;
+        if (v < nv) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + (uint32_t)((row * ld + cv * 8) * 2)) = *reinterpret_cast<const uint4*>(img + vec_off(row, cv));
+    }
+}
+
+constexpr int OFF_GAM = SMEM_BWD, SMEM_BWD_ALL = 81920;      // g1 | g2 | g3 behind the chain tables; the launch asks for half a CU:
+static_assert(OFF_GAM + 3 * C * 4 <= SMEM_BWD_ALL, "gamma table");
+// a product reads whole row tiles: over image R the rows >= T of the last tile lie in the tables behind it (read only; every consumer
+// of those rows is guarded) — they must stay inside the allocation
+static_assert(2 * IMG + MAXRT * 4096 <= SMEM_BWD_ALL && 2 * IMG + MAXRT * 4096 <= SMEM_FWD, "operand reads of rows >= T leave the workgroup's LDS");
+
+// The chain of tail_bwd_kernel with three images and <= 128 registers (the register plan of the block comment above).
+//   images: head  P = gathered row gradients [M] (rows >= 101 run into Q, which is free then), R = d_pre_t
+//           LN2'  P = d_a1 (residual part; bf16 exactly: it was rounded through the activation dtype anyway), Q = d_o
+//           hidden layer  R = d_pre_f half (product operand and copy-out source)
+//           LN1'  Q = d_ao, R = d_res1, P = d_att
+//   LayerNorm inputs (so, o / a1, ao / x_in), gelu' factors (pre_t, pre_f halves) and d_y_in arrive as quads straight from global
+//   memory: no image, no barrier, 14 registers per tensor.
+//   Load order: every quad set and every weight-fragment set is requested at the END of the segment in front of its use — behind the
+//   epilogue that frees the registers and behind the segment's store batch (copy_out) — and waited for where it is used.  Nothing
+//   is requested a whole segment ahead: a fragment set held across a LayerNorm (z + dy + the sums: 66 registers) spilled, and a
+//   reload from scratch waits on vmcnt like any load.  Requesting the loads IN FRONT of the store batch and pinning their wait
+//   there (rule 62, worth 5 us in the forward) was built and measured: 79.2 us against 77.5 us for this order at 512 samples, no
+//   difference at 256 (profiles/tail_bwd2_ab.txt) — with a second workgroup on the CU the wait behind the stores is hidden, and
+//   the pinned wait only delays the stores.  Not kept.  What stays of that rule costs nothing: the per-sample LayerNorm partials
+//   (256 floats per LayerNorm) leave with the store batch, not from inside the LayerNorm, and the saved moments are read in the
+//   prologue (behind a store a uniform load is a vector load like any other).
+//   The epilogue loops end every row tile with a scheduling fence ("one row tile at a time"): left alone, the scheduler interleaves
+//   the seven tiles of a loop for latency's sake — the dropout hashes and conversions of all of them at once, ~80 registers — and
+//   at four waves per SIMD the other waves are what hides that latency.
+template <int NRT>
+__global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* const P = smem; char* const Q = smem + IMG; char* const R = smem + 2 * IMG;
+    float* red = reinterpret_cast<float*>(smem + OFF_RED);
+    int* rowmap = reinterpret_cast<int*>(smem + OFF_ROWMAP);      // [T] head of the chain of gathered rows naming position t
+    int* nextj = reinterpret_cast<int*>(smem + OFF_NEXTJ);        // [M]
+    int* mpos_s = reinterpret_cast<int*>(smem + OFF_MPOS);        // [M] masked positions of this sample
+    float* gam = reinterpret_cast<float*>(smem + OFF_GAM);
+    const int b = blockIdx.x, T = p.T;
+    const Lane L = make_lane();
+    const int n0 = L.wave * 16, nl = L.nl, l15 = L.l15;
+    const long row0 = (long)b * T;
+    // the padded-channel mask is rebuilt in front of each LayerNorm (opaque copy of nl): held for the whole kernel it went to scratch, and
+    // a reload from scratch waits on vmcnt — behind the stores
+    auto make_cpad = [&]() { int n = nl; asm volatile("" : "+v"(n)); return chan_pad<8>(n, p.dhp, p.dht); };
+    const uint64_t idx0 = (uint64_t)((row0 + l15) * C + nl);       // dropout element index of this lane's quad in row tile 0 (+ rt * 16 * C)
+    PHB_DECL
+    if ((int)threadIdx.x < C) {
+        const int c = threadIdx.x;
+        const float* g3_or = p.head ? p.g3 : p.g1;
+        const float x0 = p.g1[c], x1 = p.g2[c], x2 = g3_or[c];
+        gam[c] = x0; gam[C + c] = x1; gam[2 * C + c] = x2;
+    }
+    DropKey dk1 = make_dropkey(p.rng, p.sid1, p.rate), dk2 = make_dropkey(p.rng, p.sid2, p.rate);     // wave-uniform: scalar registers,
+    dk1.scale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(dk1.scale)));                // the scale (a division) too
+    dk2.scale = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(dk2.scale)));
+    // the moments the forward saved, read in front of the first store (scalar registers): behind one, a uniform load is a vector load
+    // like any other and its wait would stand behind the store batch of the segment before
+    auto uni = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
+    const float* st3_or = p.head ? p.st3 : p.st1;
+    const float mean1 = uni(p.st1[2 * b]), rstd1 = uni(p.st1[2 * b + 1]), mean2 = uni(p.st2[2 * b]), rstd2 = uni(p.st2[2 * b + 1]),
+                mean3 = uni(st3_or[2 * b]), rstd3 = uni(st3_or[2 * b + 1]);
+    float z[MAXRT][4], dy[MAXRT][4], dz[MAXRT][4], dga[4], dbe[4];
+    f32x4 acc[MAXRT];
+    WFrags<NKB> wf;
+    Quads qa, qb;
+
+    if (p.head) {
+        // ---- LN3' on the gathered rows, GELU' -> d_pre_t (EasyDGL.py:136-146 backward) ------------------------------------
+        // the M <= 112 gathered row gradients of this sample -> image P rows [0, M) (compacted-away rows as zeros); their row indices
+        // are fetched first, so that the second hop travels with the so quads
+        int gsrc[4];
+        if (p.rowmap) {      // (uniform branch; straight-line loads inside)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) gsrc[i] = p.rowmap[(long)b * p.M + min((int)(threadIdx.x + i * NTHR) >> 4, p.M - 1)];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) gsrc[i] = b * p.M + min((int)(threadIdx.x + i * NTHR) >> 4, p.M - 1);
+        }
+        const int my_pos = (int)p.mpos[(long)b * p.M + min((int)threadIdx.x, p.M - 1)];      // M <= 112 <= threads
+        qa = load_quads<NRT>(p.so + row0 * C, C, T);
+        qb = load_quads<NRT>(p.pre_t + row0 * C, C, T);
+        {
+            uint4 g[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[i] = *reinterpret_cast<const uint4*>(p.d_rows + (long)max(gsrc[i], 0) * C + (threadIdx.x & 15) * 8);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int j = (int)(threadIdx.x + i * NTHR) >> 4;
+                if (j < p.M) *reinterpret_cast<uint4*>(P + vec_off(j, threadIdx.x & 15)) = gsrc[i] >= 0 ? g[i] : make_uint4(0, 0, 0, 0);
+            }
+        }
+        if ((int)threadIdx.x < p.M) mpos_s[threadIdx.x] = my_pos;
+        if ((int)threadIdx.x < MAXRT * 16) rowmap[threadIdx.x] = -1;
+        lds_barrier();
+        // chains of the gathered rows naming one position, in ascending j (the order the unfused kernel sums in): row j links to
+        // the next larger j' with the same position; the smallest j of a position is its head
+        if ((int)threadIdx.x < p.M) {
+            const int j = threadIdx.x, t = mpos_s[j];
+            int nxt = -1;
+            bool first = true;
+#pragma unroll 8
+            for (int k = 0; k < p.M; ++k) {
+                const bool same = mpos_s[k] == t;
+                nxt = (same && k > j && nxt < 0) ? k : nxt;
+                first = first && !(same && k < j);
+            }
+            nextj[j] = nxt;
+            if (first) rowmap[t] = j;
+        }
+        lds_barrier();
+        // first link of every row tile's chain as straight-line code; longer chains — repeated positions — in the loop below
+        int jn[MAXRT];
+        {
+            int jh[MAXRT];
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+                const int row = rt * 16 + l15;
+                quad_f32(qa.q[rt], z[rt]);
+                jh[rt] = row < T ? rowmap[row] : -1;
+                __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+            }
+#pragma unroll
+            for (int rt = 0; rt < NRT; ++rt) {
+                jn[rt] = nextj[max(jh[rt], 0)];
+                ld_bf4(reinterpret_cast<const bf16*>(P + quad_off(max(jh[rt], 0), L)), dy[rt]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dy[rt][r] = jh[rt] >= 0 ? dy[rt][r] : 0.f;
+                jn[rt] = jh[rt] >= 0 ? jn[rt] : -1;
+                __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+            }
+        }
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt)
+            for (int j = jn[rt]; j >= 0; j = nextj[j]) {
+                float v[4];
+                ld_bf4(reinterpret_cast<const bf16*>(P + quad_off(j, L)), v);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dy[rt][r] += v[r];
+            }
+        PHB_MARK(0);   // head inputs, gathered row gradients
+        {
+            const float4 gg = *reinterpret_cast<const float4*>(gam + 2 * C + nl);
+            const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
+            ln_bwd_part<8, false>(z, dy, mean3, rstd3, gv, NRT, T, L.lane, nl, red, nullptr, dz, make_cpad(), dga, dbe);
+        }
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) {
+            float dg[4];
+            quad_f32(qb.q[rt], dg);
+            const float v[4] = {dz[rt][0] * dg[0], dz[rt][1] * dg[1], dz[rt][2] * dg[2], dz[rt][3] * dg[3]};
+            if (rt * 16 + l15 < T) st_bf4(reinterpret_cast<bf16*>(R + L.quad + rt * 4096), v);
+            __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+        }
+        lds_barrier();
+        store_part(p.part3 + (long)b * 2 * C, L, dga, dbe);
+        copy_out_b(p.d_pre_t + row0 * C, C, R, T);
+        // the product's fragments and the next phase's inputs (behind the store batch: see the kernel's header comment)
+        EDGL_PIN();
+        wf = load_wfrags<NKB>(p.Wt + (long)n0 * C, C, L.lane);
+        qa = load_quads<NRT>(p.o + row0 * C, C, T);
+        qb = load_quads<NRT>(p.a1 + row0 * C, C, T);
+        // ---- d_y = d_pre_t . Wt^T ----------------------------------------------------------------------------------------------
+        zero_acc<NRT>(acc);
+        gemm<NRT>(wf, R, fresh_lane(), acc);
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dy[rt][r] = rbf(acc[rt][r]);
+        PHB_MARK(1);   // LN3', gelu', dX(Wt)
+    } else {
+        qa = load_quads<NRT>(p.d_y_in + row0 * C, C, T);
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) quad_f32(qa.q[rt], dy[rt]);
+        qa = load_quads<NRT>(p.o + row0 * C, C, T);
+        qb = load_quads<NRT>(p.a1 + row0 * C, C, T);
+        lds_barrier();      // (the gamma table)
+        touch_regs(qa); touch_regs(qb);      // as on the head's side: no wait of the code below is left to be merged with its stores in flight
+    }
+    // ---- LN2': z2 = drop(o) + a1 ; d_o = drop(d_z2) ; d_a1 (residual part) = d_z2 (EasyDGL.py:126-128 backward) -----------------
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        float ov[4], av[4];
+        quad_f32(qa.q[rt], ov);
+        quad_f32(qb.q[rt], av);
+        drop_apply4(dk2, idx0 + (uint64_t)(rt * 16 * C), ov);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[rt][r] = ov[r] + av[r];
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    PHB_MARK(2);   // o, a1 -> z2
+    {
+        const float4 gg = *reinterpret_cast<const float4*>(gam + C + nl);
+        const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
+        ln_bwd_part<8, false>(z, dy, mean2, rstd2, gv, NRT, T, L.lane, nl, red, nullptr, dz, make_cpad(), dga, dbe);
+    }
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        float v[4], w[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w[r] = rbf(dz[rt][r]);      // gradient w.r.t. a1: the residual branch now, + d_pre_f . Wi^T below
+            v[r] = dz[rt][r];
+        }
+        drop_apply4(dk2, idx0 + (uint64_t)(rt * 16 * C), v);
+        if (rt * 16 + l15 < T) {
+            st_bf4(reinterpret_cast<bf16*>(P + L.quad + rt * 4096), w);
+            st_bf4(reinterpret_cast<bf16*>(Q + L.quad + rt * 4096), v);
+        }
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    lds_barrier();
+    store_part(p.part2 + (long)b * 2 * C, L, dga, dbe);
+    copy_out_b(p.d_o + row0 * C, C, Q, T);
+    EDGL_PIN();
+    qa = load_quads<NRT>(p.pre_f + row0 * 2 * C, 2 * C, T);        // gelu'(pre_f), first half
+    wf = load_wfrags<NKB>(p.Wout + (long)n0 * C, C, L.lane);
+    WFrags<NKB> wi = load_wfrags<NKB>(p.Wi + (long)n0 * 2 * C, 2 * C, L.lane);
+    PHB_MARK(3);   // LN2', d_o
+    // ---- d_pre_f = (d_o . Wout^T) * gelu'(pre_f), two halves of the 2C hidden channels; d_a1 += d_pre_f . Wi^T -------------------
+    f32x4 acc6[MAXRT];
+    zero_acc<NRT>(acc6);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // product and epilogue row tile by row tile: all seven accumulator tiles beside acc6 (56 registers) do not fit
+        const Lane F = fresh_lane();
+#pragma unroll
+        for (int rt = 0; rt < NRT; ++rt) {
+            f32x4 a = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < NKB; ++kb) a = mma_kblock(wf.w[kb], *reinterpret_cast<const Vec16<bf16>*>(Q + F.frag[kb] + rt * 4096), a);
+            float dg[4];
+            quad_f32(qa.q[rt], dg);
+            const float v[4] = {a[0] * dg[0], a[1] * dg[1], a[2] * dg[2], a[3] * dg[3]};
+            if (rt * 16 + l15 < T) st_bf4(reinterpret_cast<bf16*>(R + L.quad + rt * 4096), v);
+            if (rt & 1) __builtin_amdgcn_sched_barrier(0);      // two row tiles in flight
+        }
+        if (h == 1) {      // (not earlier: beside the first half's second product there was no room for a third fragment set)
+            EDGL_PIN();
+            wi = load_wfrags<NKB>(p.Wi + (long)n0 * 2 * C + C, 2 * C, L.lane);
+        }
+        lds_barrier();
+        copy_out_b(p.d_pre_f + row0 * 2 * C + h * C, 2 * C, R, T);
+        // (the accumulator tiles of the product above are dead: room for the operands of what follows this half)
+        EDGL_PIN();
+        if (h == 0) {
+            qa = load_quads<NRT>(p.pre_f + row0 * 2 * C + C, 2 * C, T);
+            wf = load_wfrags<NKB>(p.Wout + (long)(C + n0) * C, C, L.lane);
+        } else {
+            qa = load_quads<NRT>(p.ao + row0 * C, C, T);
+            qb = load_quads<NRT>(p.xin + row0 * p.ld_x, p.ld_x, T);
+        }
+        gemm<NRT>(wi, R, fresh_lane(), acc6);
+        lds_barrier();      // every wave is past its reads of this half's d_pre_f image
+    }
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        float da[4];
+        ld_bf4(reinterpret_cast<const bf16*>(P + L.quad + rt * 4096), da);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dy[rt][r] = rbf(acc6[rt][r] + da[r]);
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    PHB_MARK(4);   // the two halves of the hidden layer
+    // ---- LN1': z1 = drop(ao) + x_in ; d_ao = drop(d_z1) ; d_res1 = d_z1 (EasyDGL.py:113-116 backward) ------------------------------
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        float ov[4], xv[4];
+        quad_f32(qa.q[rt], ov);
+        quad_f32(qb.q[rt], xv);
+        drop_apply4(dk1, idx0 + (uint64_t)(rt * 16 * C), ov);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) z[rt][r] = ov[r] + xv[r];
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    PHB_MARK(5);   // ao, x_in -> z1
+    {
+        const float4 gg = *reinterpret_cast<const float4*>(gam + nl);
+        const float gv[4] = {gg.x, gg.y, gg.z, gg.w};
+        ln_bwd_part<8, false>(z, dy, mean1, rstd1, gv, NRT, T, L.lane, nl, red, nullptr, dz, make_cpad(), dga, dbe);
+    }
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        float v[4], w[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w[r] = dz[rt][r];
+            v[r] = dz[rt][r];
+        }
+        drop_apply4(dk1, idx0 + (uint64_t)(rt * 16 * C), v);
+        if (rt * 16 + l15 < T) {
+            st_bf4(reinterpret_cast<bf16*>(Q + L.quad + rt * 4096), v);
+            st_bf4(reinterpret_cast<bf16*>(R + L.quad + rt * 4096), w);
+        }
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    lds_barrier();
+    store_part(p.part1 + (long)b * 2 * C, L, dga, dbe);
+    copy_out_b(p.d_ao + row0 * C, C, Q, T);
+    copy_out_b(p.d_res1 + row0 * C, C, R, T);
+    EDGL_PIN();
+    wf = load_wfrags<NKB>(p.Wo + (long)n0 * C, C, L.lane);
+    PHB_MARK(6);   // LN1', d_ao, d_res1
+    // ---- d_att = d_ao . Wo^T -> P (d_a1 is consumed, by the lanes that now overwrite it) --------------------------------------------
+    zero_acc<NRT>(acc);
+    gemm<NRT>(wf, Q, fresh_lane(), acc);
+#pragma unroll
+    for (int rt = 0; rt < NRT; ++rt) {
+        const float v[4] = {acc[rt][0], acc[rt][1], acc[rt][2], acc[rt][3]};
+        if (rt * 16 + l15 < T) st_bf4(reinterpret_cast<bf16*>(P + L.quad + rt * 4096), v);
+        __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
+    }
+    lds_barrier();
+    copy_out_b(p.d_att + row0 * C, C, P, T);
+    PHB_MARK(7);   // dX(Wo), d_att
+    PHB_FLUSH();
+}
+
 }  // namespace t2
 
 // dst[n][k] = src[k][n]  (tf.layers.dense kernels are [in, out]; the MFMA A operand wants k contiguous)
@@ -1215,6 +1597,33 @@ extern "C" int edgl_tail_variant(int variant) {
     const int prev = tail2_enabled() ? 1 : 0;
     if (variant >= 0) g_tail2 = variant ? 1 : 0;
     return prev;
+}
+
+// The dynamic-LDS limit of every tail kernel, raised once per device (a once-flag each), not on every launch
+static bool tail_lds_attrs() {
+    constexpr int MAXDEV = 64;
+    static std::once_flag once[MAXDEV];
+    static bool ok[MAXDEV] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return false;
+    std::call_once(once[dev], [dev] {
+        bool good = true;
+        auto set = [&](const void* f, size_t bytes) { good = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess && good; };
+        set((const void*)tail_fwd_kernel<8, 2>, TailGeom<8>::SMEM_FWD); set((const void*)tail_fwd_kernel<8, 4>, TailGeom<8>::SMEM_FWD);
+        set((const void*)tail_fwd_kernel<8, MAXRT>, TailGeom<8>::SMEM_FWD);
+        set((const void*)tail_fwd_kernel<4, 2>, TailGeom<4>::SMEM_FWD); set((const void*)tail_fwd_kernel<4, 4>, TailGeom<4>::SMEM_FWD);
+        set((const void*)tail_fwd_kernel<4, MAXRT>, TailGeom<4>::SMEM_FWD);
+        set((const void*)tail_bwd_kernel<8, 2>, TailGeom<8>::SMEM_BWD); set((const void*)tail_bwd_kernel<8, 4>, TailGeom<8>::SMEM_BWD);
+        set((const void*)tail_bwd_kernel<8, MAXRT>, TailGeom<8>::SMEM_BWD);
+        set((const void*)tail_bwd_kernel<4, 2>, TailGeom<4>::SMEM_BWD); set((const void*)tail_bwd_kernel<4, 4>, TailGeom<4>::SMEM_BWD);
+        set((const void*)tail_bwd_kernel<4, MAXRT>, TailGeom<4>::SMEM_BWD);
+        set((const void*)t2::tail2_fwd_kernel<2>, t2::SMEM_FWD); set((const void*)t2::tail2_fwd_kernel<4>, t2::SMEM_FWD);
+        set((const void*)t2::tail2_fwd_kernel<MAXRT>, t2::SMEM_FWD);
+        set((const void*)t2::tail2_bwd_kernel<2>, t2::SMEM_BWD_ALL); set((const void*)t2::tail2_bwd_kernel<4>, t2::SMEM_BWD_ALL);
+        set((const void*)t2::tail2_bwd_kernel<MAXRT>, t2::SMEM_BWD_ALL);
+        ok[dev] = good;
+    });
+    return ok[dev];      // (a failed set is reported by every launch, not retried)
 }
 
 extern "C" long edgl_tail_pack_elems(int C) { return 6L * C * C; }
@@ -1255,7 +1664,7 @@ extern "C" int edgl_tail_fwd_ct(const void* att, const void* xin, int ld_x, cons
     const int nrt = (T + 15) / 16;
     if (tail2_enabled() && C == 128 && T <= t2::TMAX) {      // two workgroups per CU (see namespace t2)
         auto k2 = nrt <= 2 ? t2::tail2_fwd_kernel<2> : nrt <= 4 ? t2::tail2_fwd_kernel<4> : t2::tail2_fwd_kernel<MAXRT>;
-        hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, t2::SMEM_FWD);
+        EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_fwd (two per CU): hipFuncSetAttribute failed on this device");
         hipLaunchKernelGGL(k2, dim3(B), dim3(t2::NTHR), t2::SMEM_FWD, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
@@ -1263,7 +1672,7 @@ extern "C" int edgl_tail_fwd_ct(const void* att, const void* xin, int ld_x, cons
     auto k = C == 128 ? (nrt <= 2 ? tail_fwd_kernel<8, 2> : nrt <= 4 ? tail_fwd_kernel<8, 4> : tail_fwd_kernel<8, MAXRT>)
                       : (nrt <= 2 ? tail_fwd_kernel<4, 2> : nrt <= 4 ? tail_fwd_kernel<4, 4> : tail_fwd_kernel<4, MAXRT>);
     const size_t smem = C == 128 ? TailGeom<8>::SMEM_FWD : TailGeom<4>::SMEM_FWD;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_fwd (one per CU): hipFuncSetAttribute failed on this device");
     hipLaunchKernelGGL(k, dim3(B), dim3(C == 128 ? 512 : 256), smem, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -1302,11 +1711,17 @@ extern "C" int edgl_tail_bwd_ct(const void* xin, int ld_x, const void* ao, const
                (bf16*)d_pre_t, (bf16*)d_o, (bf16*)d_pre_f, (bf16*)d_ao, (bf16*)d_res1, (bf16*)d_att, part1, part2, part3, dh_pad, dh_true};
     hipStream_t st = (hipStream_t)stream;
     const int nrt = (T + 15) / 16;
-    auto k = C == 128 ? (nrt <= 2 ? tail_bwd_kernel<8, 2> : nrt <= 4 ? tail_bwd_kernel<8, 4> : tail_bwd_kernel<8, MAXRT>)
-                      : (nrt <= 2 ? tail_bwd_kernel<4, 2> : nrt <= 4 ? tail_bwd_kernel<4, 4> : tail_bwd_kernel<4, MAXRT>);
-    const size_t smem = C == 128 ? TailGeom<8>::SMEM_BWD : TailGeom<4>::SMEM_BWD;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k, dim3(B), dim3(C == 128 ? 512 : 256), smem, st, p);
+    EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_bwd: hipFuncSetAttribute failed on this device");
+    // two workgroups per CU (see namespace t2); the unstaged head path (M > 112) keeps the one-per-CU kernel
+    if (tail2_enabled() && C == 128 && T <= t2::TMAX && (!head || M <= MAXRT * 16)) {
+        auto k2 = nrt <= 2 ? t2::tail2_bwd_kernel<2> : nrt <= 4 ? t2::tail2_bwd_kernel<4> : t2::tail2_bwd_kernel<MAXRT>;
+        hipLaunchKernelGGL(k2, dim3(B), dim3(t2::NTHR), t2::SMEM_BWD_ALL, st, p);
+    } else {
+        auto k = C == 128 ? (nrt <= 2 ? tail_bwd_kernel<8, 2> : nrt <= 4 ? tail_bwd_kernel<8, 4> : tail_bwd_kernel<8, MAXRT>)
+                          : (nrt <= 2 ? tail_bwd_kernel<4, 2> : nrt <= 4 ? tail_bwd_kernel<4, 4> : tail_bwd_kernel<4, MAXRT>);
+        const size_t smem = C == 128 ? TailGeom<8>::SMEM_BWD : TailGeom<4>::SMEM_BWD;
+        hipLaunchKernelGGL(k, dim3(B), dim3(C == 128 ? 512 : 256), smem, st, p);
+    }
     EDGL_LAUNCH_CHECK();
     // (dbeta | dgamma) per sample -> parameter gradients, fixed order (deferred-reduction aware)
     auto red2 = [&](float* part, float* dg, float* db) -> int {
