@@ -116,6 +116,14 @@ SIGNATURES = {
     "edgl_score_topk_fused_supported": (I, [I, I, I, I, I, I]),
     "edgl_score_topk_fused_workspace": (L, [I, I, I, I, I]),
     "edgl_score_topk_fused": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, I, P]),
+    "edgl_score_rank_supported": (I, [I, I, I, I, I]),
+    "edgl_score_rank_workspace": (L, [I, I, I, I]),
+    "edgl_score_rank_slices": (I, [I, I, I, I]),
+    "edgl_score_label_value": (I, [P, P, P, P, I, P, I, I, I, P, I, P]),
+    "edgl_score_rank_fused": (I, [P, P, P, P, I, P, P, I, I, I, I, I, P, P, I, P]),
+    "edgl_label_value_tile": (I, [P, I, I, I, P, I, P, P, P]),
+    "edgl_rank_count_tile": (I, [P, I, I, I, P, I, P, P, P, P]),
+    "edgl_rank_metrics_from_rank": (I, [P, I, P, I, P, P]),
     "edgl_topk_merge": (I, [P, P, I, I, I, P, P, P]),
     "edgl_rank_metrics": (I, [P, I, I, P, P, P]),
     "edgl_tpp_workspace": (I, []),

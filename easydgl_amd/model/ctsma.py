@@ -181,6 +181,13 @@ class CTSMA(Sequential):
         logits = self.forward(features, False)
         return ops.mask_topk(logits, 0, features["seqs_i"] if mask_seen else None, K)
 
+    @torch.no_grad()
+    def eval_rank(self, features, labels, mask_seen=True):
+        """int32 [B]: the label's place in the (logit desc, item id asc) order of the unseen catalogue (Base.py:150-201), counted on the
+        materialised logits — no top-K list, the logits are left as they are."""
+        logits = self.forward(features, False)
+        return ops.rank_from_logits(logits, 0, features["seqs_i"] if mask_seen else None, EasyDGL._last_labels(labels))
+
     eval_step = EasyDGL.eval_step
 
     # ---- interop with the reference's variable naming (tests / checkpoints converted from TF) ------------------------

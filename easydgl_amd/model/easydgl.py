@@ -418,19 +418,70 @@ class EasyDGL(Sequential):
             return ops.topk_merge(torch.stack(vals), torch.stack(idxs))
         return parallel.sharded_topk(local_topk, ops.topk_merge, self.num_items, K, group)
 
-    def reset_metrics(self):
-        self._metrics = torch.zeros(6, device=self._arena.device, dtype=torch.float32)
-        self._metric_count = 0
+    @staticmethod
+    def _last_labels(labels):
+        return (labels[:, -1] if labels.dim() == 2 else labels).contiguous()
 
     @torch.no_grad()
-    def eval_step(self, features, labels, mask_seen=True):
+    def eval_rank(self, features, labels, mask_seen=True):
+        """int32 [B]: the place of each sequence's true next item in the (logit desc, item id asc) order of the unseen catalogue
+        (Base.py:150-201) by one counting sweep — no top-K list (ops.score_label_rank)."""
+        rows, _ = self.encoder(features, False, self._gather_pos(features, False))
+        tab = self.item_embs.lookup_table
+        return ops.score_label_rank(rows, self.compute(tab), self.output_bias, features["seqs_i"] if mask_seen else None,
+                                    self._last_labels(labels), 0, self.num_items)
+
+    @torch.no_grad()
+    def eval_rank_sharded(self, features, labels, mask_seen=True, group=None, world=None, rank=None):
+        """eval_rank with the item table row-sharded: this rank counts over its parallel.shard_bounds range and ONE all-reduce (SUM)
+        of the int32 [B] counts gives the ranks — no candidate lists, no merge; an empty shard contributes zeros.  `world` emulates
+        the shards in one process (tests), as eval_topk_sharded does."""
+        from .. import parallel
+        rows, _ = self.encoder(features, False, self._gather_pos(features, False))
+        tab_c = self.compute(self.item_embs.lookup_table)
+        seen = features["seqs_i"] if mask_seen else None
+        lab = self._last_labels(labels)
+
+        def count_local(i0, i1):
+            return ops.score_label_rank(rows, tab_c, self.output_bias, seen, lab, i0, i1)
+
+        if world is not None:   # in-process emulation of `world` shards
+            return sum(count_local(*parallel.shard_bounds(self.num_items, world, r)) for r in range(world))
+        return parallel.sharded_rank(count_local, self.num_items, group)
+
+    def reset_metrics(self, ks=None):
+        """`ks`: the cut-offs of the by-rank metrics (eval_step(by_rank=True)); default (10, 50, 100), at most 8."""
+        dev = self._arena.device
+        self._metrics = torch.zeros(6, device=dev, dtype=torch.float32)
+        self._metric_count = 0
+        self._rank_ks = tuple(int(k) for k in (ks or (10, 50, 100)))
+        if not 1 <= len(self._rank_ks) <= 8:
+            raise ValueError(f"reset_metrics: 1 to 8 cut-offs (got {self._rank_ks})")
+        self._rank_ks_dev = torch.tensor(self._rank_ks, device=dev, dtype=torch.int32)
+        self._rank_sums = torch.zeros(2 * len(self._rank_ks) + 1, device=dev, dtype=torch.float32)
+        self._rank_count = 0
+
+    @torch.no_grad()
+    def eval_step(self, features, labels, mask_seen=True, by_rank=False):
         if self._metrics is None:
             self.reset_metrics()
-        _, idx = self.eval_topk(features, mask_seen)
-        ops.rank_metrics(idx, labels[:, -1].contiguous(), self._metrics)
+        if by_rank:
+            if self._metric_count != self._rank_count:
+                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
+            ops.rank_metrics_from_rank(self.eval_rank(features, labels, mask_seen), self._rank_ks_dev, self._rank_sums)
+            self._rank_count += labels.shape[0]
+        else:
+            if self._rank_count:
+                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
+            _, idx = self.eval_topk(features, mask_seen)
+            ops.rank_metrics(idx, labels[:, -1].contiguous(), self._metrics)
         self._metric_count += labels.shape[0]
 
     def metrics(self) -> Dict[str, float]:
+        if getattr(self, "_rank_count", 0):     # by-rank steps: H / N at the chosen cut-offs and the mean reciprocal rank
+            vals = (self._rank_sums / self._rank_count).tolist()
+            names = [f"H{k}" for k in self._rank_ks] + [f"N{k}" for k in self._rank_ks] + ["MRR"]
+            return dict(zip(names, vals))
         vals = (self._metrics / max(1, self._metric_count)).tolist()
         return dict(zip(("H10", "H50", "H100", "N10", "N50", "N100"), vals))
 

@@ -815,6 +815,120 @@ def rank_metrics(topk_idx: torch.Tensor, label: torch.Tensor, metrics: torch.Ten
     check(lib.edgl_rank_metrics(_ptr(topk_idx), R, K, _ptr(label), _ptr(metrics), _stream()), "edgl_rank_metrics")
 
 
+# ---- K6r: evaluation by label rank (csrc/k_eval_rank.hip) — Base.py:150-201 without a top-K list ---------------------------------
+RANK_FUSED_ITEMS = 262144    # items per call of edgl_score_rank_fused
+
+
+def _aligned_seen(seen, who):
+    """The sweeps read a row's seen ids as 16-byte pairs of int64 at a row stride of T."""
+    if seen is None:
+        return None
+    if seen.dtype != torch.int64:
+        raise _lib.EdglError(f"{who}: seen ids must be int64 (got {seen.dtype})")
+    seen = seen.contiguous()
+    return seen.clone() if seen.data_ptr() % 16 != 0 else seen
+
+
+def _rank_labels(labels, R, who):
+    if labels.dtype != torch.int64 or labels.shape != (R,):
+        raise _lib.EdglError(f"{who}: labels must be int64 [{R}] (got {labels.dtype} {tuple(labels.shape)})")
+    return labels.contiguous()
+
+
+def score_label_rank(rows, table_c, out_bias, seen, labels, i0=0, i1=None):
+    """int32 [R]: for every row the number of items j != y of [i0, i1) that come before its label y = labels[r] in the (logit desc,
+    item id asc) order of the catalogue with the row's seen ids at -inf (Base.py:150-201).  Over the whole catalogue that is the
+    label's rank: its index in score_topk's list whenever it is < K.  Counts over disjoint ranges add.
+    bf16 at C in {64, 128, 256}: the fused form — the label values by the sweep's own MFMA chain, then one counting sweep per range
+    of <= RANK_FUSED_ITEMS items, no logits in HBM.  Anything else: logits tiles bounded by EVAL_TILE_BYTES, scored by
+    edgl_score_lse_fwd (ONE kernel for every chunk: the label's value and its duplicates elsewhere in the catalogue must be the
+    same bits) — pass A takes each label's value from the chunk that holds it, pass B counts; a catalogue of one chunk is scored once."""
+    R, C = rows.shape
+    I = table_c.shape[0]
+    i1 = I if i1 is None else i1
+    _ptr(rows)                                               # (GPU tensors only: refused before anything else)
+    dev, code, st = rows.device, _code(rows), _stream()
+    labels = _rank_labels(labels, R, "score_label_rank")
+    count = torch.zeros(R, device=dev, dtype=torch.int32)
+    if i1 <= i0:                                            # (an empty table shard)
+        return count
+    T = 0 if seen is None else seen.shape[1]
+    label_val = torch.empty(R, device=dev, dtype=torch.float32)
+    if i0 % 8 == 0 and lib.edgl_score_rank_supported(R, C, min(i1 - i0, RANK_FUSED_ITEMS), T, code):
+        seen = _aligned_seen(seen, "score_label_rank")
+        check(lib.edgl_score_label_value(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(seen), T, _ptr(labels), R, C, I,
+                                         _ptr(label_val), code, st), "edgl_score_label_value")
+        for lo in range(i0, i1, RANK_FUSED_ITEMS):
+            check(lib.edgl_score_rank_fused(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(seen), T, _ptr(labels), _ptr(label_val),
+                                            R, C, I, lo, min(i1, lo + RANK_FUSED_ITEMS), _ptr(count), None, code, st),      # (workspace: 0 bytes)
+                  "edgl_score_rank_fused")
+        return count
+    if seen is not None:
+        seen = seen.contiguous()
+    chunk = max(8, (EVAL_TILE_BYTES // (4 * R)) // 8 * 8)
+
+    def chunks(lo, hi):
+        return [(a, min(hi, a + chunk)) for a in range(lo, hi, chunk)]
+
+    logits = torch.empty((R, min(chunk, I)), device=dev, dtype=torch.float32)
+    ws = torch.empty(2 * R * lib.edgl_score_chunks(R, min(chunk, I)), device=dev, dtype=torch.float32)
+
+    def score(lo, hi):     # logits [R, hi - lo], row stride hi - lo
+        check(lib.edgl_score_lse_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), None, R, C, I, lo, hi, None, None, None,
+                                     _ptr(logits), _ptr(ws), code, st), "edgl_score_lse_fwd")
+
+    def value(lo, hi):
+        check(lib.edgl_label_value_tile(_ptr(logits), R, hi - lo, lo, _ptr(seen), T, _ptr(labels), _ptr(label_val), st),
+              "edgl_label_value_tile")
+
+    def add(lo, hi):
+        check(lib.edgl_rank_count_tile(_ptr(logits), R, hi - lo, lo, _ptr(seen), T, _ptr(labels), _ptr(label_val), _ptr(count), st),
+              "edgl_rank_count_tile")
+
+    whole = chunks(0, I)             # pass A walks the whole catalogue: a label may lie outside [i0, i1) (table shards)
+    if len(whole) == 1:
+        score(0, I)
+        value(0, I)
+        if (i0, i1) != (0, I):
+            score(i0, i1)
+        add(i0, i1)
+        return count
+    for lo, hi in whole:
+        score(lo, hi)
+        value(lo, hi)
+    for lo, hi in chunks(i0, i1):
+        score(lo, hi)
+        add(lo, hi)
+    return count
+
+
+def rank_from_logits(logits: torch.Tensor, i0: int, seen: Optional[torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
+    """score_label_rank for materialised f32 logits [B, n] of the items [i0, i0 + n) (the regressive models): every label must lie
+    in that range.  The logits are not modified."""
+    R, n = logits.shape
+    _ptr(logits)                                             # (GPU tensors only: refused before anything else)
+    if logits.dtype != torch.float32:
+        raise _lib.EdglError(f"rank_from_logits: f32 logits (got {logits.dtype})")
+    labels = _rank_labels(labels, R, "rank_from_logits")
+    seen = None if seen is None else seen.contiguous()
+    T = 0 if seen is None else seen.shape[1]
+    st = _stream()
+    label_val = torch.full((R,), float("inf"), device=logits.device, dtype=torch.float32)
+    count = torch.zeros(R, device=logits.device, dtype=torch.int32)
+    check(lib.edgl_label_value_tile(_ptr(logits), R, n, i0, _ptr(seen), T, _ptr(labels), _ptr(label_val), st), "edgl_label_value_tile")
+    check(lib.edgl_rank_count_tile(_ptr(logits), R, n, i0, _ptr(seen), T, _ptr(labels), _ptr(label_val), _ptr(count), st),
+          "edgl_rank_count_tile")
+    return count
+
+
+def rank_metrics_from_rank(rank: torch.Tensor, ks: torch.Tensor, sums: torch.Tensor) -> None:
+    """sums f32 [2 nk + 1] += (H@k.., N@k.., MRR) of the int32 ranks; ks int32 [nk <= 8] on the device."""
+    if rank.dtype != torch.int32 or ks.dtype != torch.int32 or sums.dtype != torch.float32 or sums.numel() != 2 * ks.numel() + 1:
+        raise _lib.EdglError("rank_metrics_from_rank: rank int32 [R], ks int32 [nk], sums f32 [2 nk + 1]")
+    check(lib.edgl_rank_metrics_from_rank(_ptr(rank), rank.shape[0], _ptr(ks), ks.numel(), _ptr(sums), _stream()),
+          "edgl_rank_metrics_from_rank")
+
+
 def adam_step(param, grad, m, v, lr, state, l2, seg, shadow, beta1=0.9, beta2=0.999, eps=1e-8):
     check(lib.edgl_adam_step(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), param.numel(), float(lr), beta1, beta2, eps,
                              _ptr(state), float(l2), _ptr(seg), 0 if seg is None else seg.numel() // 2, _ptr(shadow),

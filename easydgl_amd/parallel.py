@@ -4,6 +4,8 @@
   shard, masks seen items, keeps its local top-K with GLOBAL item ids, then ONE all-gather moves a packed
   [R, 2K] 32-bit buffer per rank (K=100, R=512: 400 KB) and a merge kernel orders the S*K candidates
   by (value desc, id asc) — the tf.nn.top_k tie rule of Base.py:181.
+  Evaluation by label rank (sharded_rank) needs less: each rank counts the items of its shard that come before the label, and ONE
+  all-reduce (SUM) of [R] integers gives the ranks.
 * Training: data parallel over sequences (per-sample LayerNorm and per-sequence attention make samples
   independent).  The loss normalises by sums over the BATCH (weighted rows, next-event marks); the engine all-reduces those
   two integers before the step (TrainEngine._global_counts), every rank differentiates its share of the global-batch loss
@@ -48,6 +50,19 @@ def sharded_topk(local_topk: Callable[[int, int], Tuple[torch.Tensor, torch.Tens
     cand_val = gathered[:, :, :K].contiguous().view(torch.float32)
     cand_idx = gathered[:, :, K:].contiguous()
     return merge(cand_val, cand_idx)
+
+
+def sharded_rank(count_local: Callable[[int, int], torch.Tensor], num_rows: int,
+                 group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+    """Evaluation by label rank over a row-sharded item table: count_local(i0, i1) -> int32 [R], the number of items of the shard that
+    come before each row's label in the (value desc, id asc) order (zeros for an empty shard).  The rank is the SUM over the shards:
+    ONE all-reduce of [R] integers — no candidate lists, no merge."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    count = count_local(*shard_bounds(num_rows, world, rank)).contiguous()
+    if world > 1:
+        dist.all_reduce(count, op=dist.ReduceOp.SUM, group=group)
+    return count
 
 
 def allreduce_mean_(flat_grad: torch.Tensor, group: Optional[dist.ProcessGroup] = None) -> None:

@@ -70,6 +70,9 @@ def args(argv=None):
     p.add_argument("--deterministic", action="store_true",
                    help="EasyDGL: bitwise reproducible training (main.py:157-168 pins TF_DETERMINISTIC_OPS): the item-table gradient "
                         "as ordered sums instead of f32 atomics, in the engine and in train_step")
+    p.add_argument("--eval_by_rank", action="store_true",
+                   help="evaluate by the label's rank (one counting sweep over the item table, ops.score_label_rank) instead of a top-K "
+                        "list; same H / N metrics plus MRR")
     a = p.parse_args(argv)
     return a
 
@@ -149,10 +152,11 @@ def regressive_batch(tok, tim, is_training: bool):
     return {"seqs_i": tok[:, :-1].contiguous(), "seqs_t": tim}, (tok[:, 1:].contiguous() if is_training else tok)
 
 
-def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None) -> Dict[str, float]:
+def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
     prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
-    (--device_data) — the batches are then assembled on the device, in file order."""
+    (--device_data) — the batches are then assembled on the device, in file order.  `by_rank`: the metrics from the label's rank
+    (model.eval_step(by_rank=True)) — the same H / N values plus "MRR"."""
     import torch
     from . import data as D
     model.reset_metrics()
@@ -160,7 +164,7 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None) -> D
         loader.set_epoch(None)
         for _ in range(len(loader)):
             feats, labels = loader.next()
-            model.eval_step(feats, labels, mask_seen=mask_seen)
+            model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
         return model.metrics()
     n = ids.shape[0]
     masked = hasattr(model, "mask")
@@ -168,7 +172,7 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None) -> D
         tok = torch.as_tensor(ids[lo:lo + batch_size]).cuda()
         tim = torch.as_tensor(ts[lo:lo + batch_size]).cuda()
         feats, labels = D.device_mask_last(tok, tim, model.mask) if masked else regressive_batch(tok, tim, False)
-        model.eval_step(feats, labels, mask_seen=mask_seen)
+        model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
     return model.metrics()
 
 
@@ -203,6 +207,7 @@ def run(FLAGS) -> Dict[str, float]:
             if np.any((np.diff(tt, axis=1) < 0) & (ii[:, :-1] != 0)):
                 raise ValueError(f"{name}: timestamps decrease inside a sequence; TGAT needs time-sorted records")
     device_data = bool(getattr(FLAGS, "device_data", False))
+    by_rank = bool(getattr(FLAGS, "eval_by_rank", False))     # (the default cut-offs keep "H100": early stopping reads it either way)
     # --device_data --graph: the batch no longer arrives from the host, so the EasyDGL step can be replayed as one graph
     engine_graph = device_data and bool(getattr(FLAGS, "graph", False))
     engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs) else None
@@ -287,9 +292,9 @@ def run(FLAGS) -> Dict[str, float]:
             break
         if epoch % FLAGS.eval_per_steps:
             continue
-        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader)
+        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank)
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
-        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader)
+        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank)
         if stopper.step(running_loss, vl["H100"], vl, te):
             break
     return stopper.summary()

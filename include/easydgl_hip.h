@@ -467,6 +467,37 @@ int edgl_topk_merge(const float* cand_val, const int32_t* cand_idx, int S, int R
 int edgl_rank_metrics(const int32_t* topk_idx, int R, int K, const int64_t* label, float* metrics,
                       void* stream);
 
+/* ---- K6r: evaluation by label rank — Base.py:150-201 without a top-K list.  For row r with label y = labels[r] (int64, 0 <= y < I)
+ * and v_j = -inf at the row's seen ids, else rows[r] . table[j] + [-1000, out_bias][j] (table row 0 reads as zeros):
+ *     count[r] += #{ j in [i0, i1), j != y : v_j > v_y  or  (v_j == v_y and j < y) }          (-0.0 == +0.0)
+ * Over [0, I) that is the index of y in the (value desc, id asc) order of edgl_mask_topk / edgl_score_topk_fused, so HR@k, NDCG@k
+ * and MRR follow for any k; counts over disjoint ranges (item chunks, table shards) add.  label_val f32 [R] holds v_y (-inf when the
+ * label is itself seen) and MUST be the bits the counting pass forms for the pair (r, y): the tie rule on duplicated items depends
+ * on it.  Fused form (Base.py:150-201): bf16, C in {64, 128, 256}, 1 <= i1 - i0 <= 262144 per call, i0 % 8 == 0, seen 16-byte
+ * aligned; edgl_score_label_value runs the sweep's own MFMA chain on gathered label rows (once per batch), edgl_score_rank_fused is
+ * one sweep on the matrix pipe with the seen ids as an LDS bitmap and integer atomics into count (exact, order-independent).  The
+ * three host queries (Base.py:150-201: no device work) answer: shape taken (1 / 0), workspace BYTES (0 for every shape taken — the
+ * workspace argument may then be NULL; -1 for a shape not taken), item slices of the plan (-1 likewise).  A shape not taken is
+ * refused with EDGL_ERR_SHAPE and the bound in the text: no silent fallback. */
+int edgl_score_rank_supported(int R, int C, int n_items, int T, int dtype);
+long edgl_score_rank_workspace(int R, int C, int n_items, int T);
+int edgl_score_rank_slices(int R, int C, int n_items, int T);
+int edgl_score_label_value(const void* rows, const void* table, const float* out_bias, const int64_t* seen, int T,
+                           const int64_t* labels, int R, int C, int I, float* label_val, int dtype, void* stream);
+int edgl_score_rank_fused(const void* rows, const void* table, const float* out_bias, const int64_t* seen, int T,
+                          const int64_t* labels, const float* label_val, int R, int C, int I, int i0, int i1, int32_t* count,
+                          void* workspace, int dtype, void* stream);
+/* Tile form (Base.py:150-201; any dtype and width): logits f32 [R, n] of the item range starting at i0 (i0 % 8 == 0), read and NOT
+ * modified.  edgl_label_value_tile writes label_val[r] for the rows whose label lies in [i0, i0 + n) (the tile's own value, -inf when
+ * the label is seen) and leaves the others untouched; edgl_rank_count_tile adds the tile's share of the count. */
+int edgl_label_value_tile(const float* logits, int R, int n, int i0, const int64_t* seen, int T, const int64_t* labels,
+                          float* label_val, void* stream);
+int edgl_rank_count_tile(const float* logits, int R, int n, int i0, const int64_t* seen, int T, const int64_t* labels,
+                         const float* label_val, int32_t* count, void* stream);
+/* Metric sums from ranks (Base.py:150-201 for any k): rank int32 [R], ks int32 [nk <= 8] (device);
+ * sums f32 [2 nk + 1] += H@k.., N@k.., MRR with H = [rank < k], N = H / log2(rank + 2), MRR = 1 / (rank + 1); fixed summation order. */
+int edgl_rank_metrics_from_rank(const int32_t* rank, int R, const int32_t* ks, int nk, float* sums, void* stream);
+
 /* ---- K5, "flash" form (used by the static training engine): the forward scoring pass already accumulates the row
  * gradients, so the [R, I] logits are computed twice per step instead of three times.
  * edgl_score_flash_fwd: one pass over the item rows [i0, i1) gives row_lse (as edgl_score_lse_fwd), label_logit, and keeps
