@@ -5,32 +5,26 @@
 // for ANY k, and counts over disjoint item ranges (chunks, table shards) simply add.
 //
 //   fused form (bf16, C in {64, 128, 256}) — two launches per item range, no logits in HBM:
-//     label_value_kernel   v_y of every row by the sweep's own MFMA chain (same instruction, same k order, accumulator started from
-//                          the item's bias) on a tile of GATHERED label rows: 32 query rows against their 32 label items, the
-//                          diagonal kept.  An MFMA result element depends on its own operand row and column only, so these are
-//                          the bits the sweep forms for the pair (r, y) — the tie rule on duplicated items rests on that.  -inf
-//                          where the label is one of the row's seen ids.  Once per batch, whatever the number of ranges.
-//     rank_sweep_kernel    the geometry of evk::eval_sweep_kernel (k_eval_topk.hip): a workgroup = 64 query rows (128 at C = 256) x
-//                          one item slice, item tiles through a double-buffered LDS image, the query rows in registers as B
-//                          fragments, v_mfma_f32_32x32x16_bf16 with the items on the accumulator registers: a lane's 16 values of a
-//                          tile belong to ONE row and are compared with that row's v_y in place.  The rows' seen ids are an LDS
-//                          bitmap over the slice; a seen item counts as -inf.  One integer atomic per (row, workgroup) adds into
-//                          count[r] — exact and order-independent (DESIGN rule 13).
+//     label_value_kernel   v_y of every row by the sweep's own MFMA chain — evs::score_step (eval_sweep.h), k ascending, the accumulator
+//                          started from the item's bias — on a tile of GATHERED label rows: 32 query rows against their 32 label
+//                          items, the diagonal kept.  An MFMA result element depends on its own operand row and column only, so
+//                          these are the bits the sweep forms for the pair (r, y) — the tie rule on duplicated items rests on
+//                          that.  -inf where the label is one of the row's seen ids.  Once per batch, whatever the number of ranges.
+//     rank_sweep_kernel    eval_sweep.h's sweep (workgroup = query block x item slice, tile ring, seen bitmap, bias-started chain).
+//                          This file adds what is done with an MFMA tile: a lane's 16 values belong to ONE row and are compared
+//                          with that row's v_y in place, a seen item counting as -inf; the per-row counts in LDS behind the bias
+//                          rows; and the epilogue: one integer atomic per (row, workgroup) adds into count[r] — exact and
+//                          order-independent (DESIGN rule 13).
 //   tile form (any dtype / width) over an [R, n] f32 logits tile that is read and not modified:
 //     label_value_tile_kernel   v_y from the tile for the rows whose label lies in it (+ the seen test), other rows untouched
 //     rank_count_tile_kernel    one workgroup per (row, segment of 8192 items): seen bitmap of the segment, compare, count
 //   rank_metrics_from_rank_kernel   sums[2 nk + 1] += (H@k.., N@k.., MRR) of a batch of ranks, fixed summation order.
 #include <algorithm>
 
-#include "edgl_common.h"
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
+#include "eval_sweep.h"
 
 namespace evr {
-
-__host__ __device__ constexpr int qb_of(int C) { return C == 256 ? 128 : 64; }     // query rows per workgroup (as evk::qb_of)
-constexpr int MAX_ITEMS = 262144;      // items per call
-__host__ __device__ constexpr int slice_cap(int C) { return C == 256 ? 2048 : 4096; }   // items of a slice: 32 KB of seen bitmap per workgroup
+using namespace evs;
 
 struct P {
     const bf16* rows; const bf16* table; const float* bias; const int64_t* seen; const int64_t* labels; const float* label_val;
@@ -40,67 +34,26 @@ struct P {
 };
 
 template <int C, int NZ, int NWS>
-struct Geo {
-    static constexpr int QB = qb_of(C);
-    static constexpr int NTHR = 64 * (QB / 32) * NWS;
-    static constexpr int LDZ = C + 8;                          // bf16 elements per LDS row (16-byte shift per row: conflict-free 16-byte fragment reads)
-    static constexpr int ZB = NZ * LDZ * 2;
-    static constexpr int OFF_Z = 0, OFF_BIAS = 2 * ZB, OFF_CNT = OFF_BIAS + 2 * NZ * 4;   // per-row counts [QB]
-    static constexpr int OFF_BMP = OFF_CNT + QB * 4;           // seen bitmap [QB][words]
-    static constexpr int bytes(int slice_items) { return OFF_BMP + QB * ((slice_items + 31) / 32) * 4; }
-    static constexpr int PIECES = NZ * C / 8 / NTHR;           // 16-byte pieces of an item tile per thread
-    static_assert(NZ * C / 8 % NTHR == 0 && NZ % (32 * NWS) == 0 && PIECES >= 1 && NTHR >= NZ, "tile geometry");
+struct Geo : SweepGeo<C, NZ, NWS> {
+    using S = SweepGeo<C, NZ, NWS>;
+    static constexpr int OFF_CNT = S::OFF_OWN;                 // per-row counts [QB]
+    static constexpr int OFF_BMP = OFF_CNT + S::QB * 4;        // seen bitmap [QB][words]
+    static constexpr int bytes(int slice_items) { return OFF_BMP + S::QB * ((slice_items + 31) / 32) * 4; }
+    static_assert(NZ * C / 8 % S::NTHR == 0 && NZ % (32 * NWS) == 0 && S::PIECES >= 1 && S::NTHR >= NZ, "tile geometry");
 };
-
-// one item tile: global -> registers, unconditional loads with the rows clamped into the table (item 0 is the zero-padded row:
-// coding.py:56-57); then registers -> LDS with the bias row: -1000 for item 0 (Base.py:106-113), -inf behind the range
-template <int C, int NZ, int NWS>
-__device__ __forceinline__ void tile_load(const P& p, int item0, uint4 (&r)[Geo<C, NZ, NWS>::PIECES], float& b) {
-    constexpr int CP = C / 8, NTHR = Geo<C, NZ, NWS>::NTHR;
-#pragma unroll
-    for (int j = 0; j < Geo<C, NZ, NWS>::PIECES; ++j) {
-        const int pc = threadIdx.x + NTHR * j, row = pc / CP, c8 = pc % CP;
-        const int item = min(item0 + row, p.I - 1);
-        r[j] = *reinterpret_cast<const uint4*>(p.table + (long)item * C + c8 * 8);
-    }
-    const int it = item0 + (int)threadIdx.x;
-    b = (threadIdx.x < NZ && it < p.i1 && it > 0) ? p.bias[min(it, p.I - 1) - 1] : 0.f;
-}
-template <int C, int NZ, int NWS>
-__device__ __forceinline__ void tile_store(const P& p, int item0, uint4 (&r)[Geo<C, NZ, NWS>::PIECES], float b, char* zbuf, float* bbuf) {
-    constexpr int CP = C / 8, NTHR = Geo<C, NZ, NWS>::NTHR;
-#pragma unroll
-    for (int j = 0; j < Geo<C, NZ, NWS>::PIECES; ++j) {
-        const int pc = threadIdx.x + NTHR * j, row = pc / CP, c8 = pc % CP;
-        if (item0 + row == 0) r[j] = make_uint4(0u, 0u, 0u, 0u);
-        *reinterpret_cast<uint4*>(zbuf + row * (Geo<C, NZ, NWS>::LDZ * 2) + c8 * 16) = r[j];
-    }
-    if (threadIdx.x < NZ) {
-        const int it = item0 + (int)threadIdx.x;
-        bbuf[threadIdx.x] = it >= p.i1 ? -INFINITY : (it == 0 ? -1000.0f : b);
-    }
-}
 
 template <int C, int NZ, int NWS>
 __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void rank_sweep_kernel(P p) {
     using G_ = Geo<C, NZ, NWS>;
-    constexpr int CK = C / 16, NTW = NZ / (32 * NWS), LDZB = G_::LDZ * 2, NTHR = G_::NTHR, QB = G_::QB;
+    constexpr int CK = C / 16, NTW = NZ / (32 * NWS), NTHR = G_::NTHR, QB = G_::QB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = wave / NWS, sw = wave % NWS, l32 = lane & 31, hi = lane >> 5;
-    // XCD-aware order (speed only; workgroup id b runs on XCD b % 8): the query blocks of ONE item slice are consecutive workgroups
-    // of ONE XCD, so the slice's table rows come out of that XCD's L2 for all but the first of them (as evk::eval_sweep_kernel)
-    const int nqb = (p.R + QB - 1) / QB;
-    const int xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3;
-    const int slice = (jx / nqb) * 8 + xcd;
+    const int slice = sweep_slice<QB>(p);
     if (slice >= p.nslices) return;
-    const int q0 = (jx % nqb) * QB;
-    // ---- this wave's 32 query rows as B fragments, straight from global memory (once per workgroup) ----------------------------------
+    const int q0 = sweep_qblock<QB>(p) * QB;
     bf16x8 xf[CK];
-    {
-        const bf16* xrow = p.rows + (long)min(q0 + 32 * h + l32, p.R - 1) * C + hi * 8;
 #pragma unroll
-        for (int k = 0; k < CK; ++k) xf[k] = *reinterpret_cast<const bf16x8*>(xrow + k * 16);
-    }
+    for (int k = 0; k < CK; ++k) xf[k] = query_frag<C>(p, q0 + 32 * h + l32, hi, k);
     int* rowcnt = reinterpret_cast<int*>(smem + G_::OFF_CNT);
     uint32_t* bmp = reinterpret_cast<uint32_t*>(smem + G_::OFF_BMP);
     const int bw = (p.tps * NZ + 31) / 32;        // bitmap words per row
@@ -108,8 +61,6 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void rank_sweep_kernel(
     for (int i = tid; i < QB * bw; i += NTHR) bmp[i] = 0u;
     const int tile_lo = slice * p.tps, ntile_all = (p.i1 - p.i0 + NZ - 1) / NZ;
     const int tile_hi = min(ntile_all, tile_lo + p.tps);
-    // two register staging sets: the loads of tile t + 2 leave while tile t is multiplied and tile t + 1 waits in the other set for
-    // its LDS buffer.  Out-of-range tiles are loaded clamped and never stored.
     uint4 stg[G_::PIECES], stg2[G_::PIECES];
     float stb, stb2;
     if (tile_lo < tile_hi) {
@@ -119,8 +70,7 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void rank_sweep_kernel(
     }
     __syncthreads();
     {
-        // the rows' seen ids that fall into this slice as a bitmap (Base.py:156-163): the rows' ids are one contiguous run of int64
-        // (16-byte aligned), read as pairs, up to 16 loads in flight per thread before the first LDS atomic
+        // the rows' seen ids that fall into this slice as a bitmap (Base.py:156-163; the loads in batches: eval_sweep.h)
         const int item_lo = p.i0 + tile_lo * NZ, item_hi = min(p.i1, p.i0 + tile_hi * NZ);
         const int nid = min(QB, p.R - q0) * p.T, npair = nid / 2;
         const int64_t* sbase = p.seen + (long)q0 * p.T;
@@ -151,28 +101,15 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void rank_sweep_kernel(
     const uint32_t* brow = bmp + (32 * h + l32) * bw;
     int tot = 0;
     int buf = 0;
-    // one trip = two tiles: tile t from LDS buffer `buf` with set A holding tile t + 1 and set B taking tile t + 2, then the same with
-    // the sets swapped (static names: register arrays cannot be indexed by the trip's parity)
+    // the tile ring (eval_sweep.h): tile t from LDS buffer `buf` with set A holding tile t + 1 and set B taking tile t + 2
     auto one_tile = [&](int t, uint4 (&sa)[G_::PIECES], float& ba, uint4 (&sb)[G_::PIECES], float& bbn) {
         const int tn = t + 1, tnn = t + 2;
         if (tnn < tile_hi) tile_load<C, NZ, NWS>(p, p.i0 + tnn * NZ, sb, bbn);
         asm volatile("" ::: "memory");
-        const char* zb = smem + G_::OFF_Z + buf * G_::ZB;
-        const float* bb = reinterpret_cast<const float*>(smem + G_::OFF_BIAS) + buf * NZ;
 #pragma unroll
         for (int u = 0; u < NTW; ++u) {
             const int m0 = (sw * NTW + u) * 32;               // the MFMA tile's first item row inside the LDS tile
-            f32x16 acc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // D[m][n] starts from the item's bias: m = 8 j + 4 hi + i
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(bb + m0 + 8 * j + 4 * hi);
-                acc[4 * j] = b4[0]; acc[4 * j + 1] = b4[1]; acc[4 * j + 2] = b4[2]; acc[4 * j + 3] = b4[3];
-            }
-#pragma unroll
-            for (int k = 0; k < CK; ++k) {
-                const bf16x8 zf = *reinterpret_cast<const bf16x8*>(zb + (m0 + l32) * LDZB + k * 32 + hi * 16);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(zf, xf[k], acc, 0, 0, 0);
-            }
+            const f32x16 acc = score_tile<C, NZ, NWS>(smem, buf, m0, l32, hi, xf);
             // The MFMA tile's 32 items are ONE word of the row's bitmap; register 4 j + i of this lane is the item at offset 8 j + i
             // from `base`.  Items strictly below the label count on >=, items above it on >: both counts are kept and the lane takes
             // the one its 16 items call for; the one tile that holds the label or the end of the range is counted item by item.
@@ -243,7 +180,7 @@ __global__ __launch_bounds__(64) void label_value_kernel(const bf16* rows, const
             for (int i = 0; i < 8; ++i) zf[i] = (bf16)0.0f;
         }
         const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xrow + k * 16);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(zf, xf, acc, 0, 0, 0);
+        acc = score_step(zf, xf, acc);
     }
     const int esel = 4 * (l32 >> 3) + (l32 & 3);     // the register of row m == l32 (held by the lane half (l32 >> 2) & 1)
     float d = acc[0];
@@ -340,7 +277,7 @@ struct Plan { int nz, nslices, tps; };
 // K + T, candidate cap, 4096-item minimum) exist here.
 inline bool make_plan(int R, int C, int n_items, int T, Plan& pl) {
     if (!(C == 64 || C == 128 || C == 256) || R < 1 || T < 0 || n_items < 1 || n_items > MAX_ITEMS) return false;
-    pl.nz = C == 256 ? 64 : 128;
+    pl.nz = nz_of(C);
     const int ntile = (n_items + pl.nz - 1) / pl.nz;
     const int nrb = (R + qb_of(C) - 1) / qb_of(C);
     int want = std::max(std::max(256 / nrb, 1), (n_items + slice_cap(C) - 1) / slice_cap(C));
@@ -353,7 +290,7 @@ inline bool make_plan(int R, int C, int n_items, int T, Plan& pl) {
 template <int C, int NZ, int NWS>
 int launch(P p, const Plan& pl, hipStream_t st) {
     using G_ = Geo<C, NZ, NWS>;
-    const dim3 grid(8 * ((p.R + G_::QB - 1) / G_::QB) * ((pl.nslices + 7) / 8));      // (query block, slice) from the id: see rank_sweep_kernel
+    const dim3 grid(sweep_grid(p.R, G_::QB, pl.nslices));
     auto k = rank_sweep_kernel<C, NZ, NWS>;
     const int lds = G_::bytes(pl.tps * NZ);
     EDGL_REQUIRE(lds <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_score_rank_fused: %d B of LDS", lds);
@@ -410,14 +347,12 @@ extern "C" int edgl_score_rank_fused(const void* rows, const void* table, const 
     evr::Plan pl;
     EDGL_REQUIRE(evr::make_plan(R, C, i1 - i0, T, pl), EDGL_ERR_SHAPE,
                  "edgl_score_rank_fused: shape not taken (R=%d C=%d items=%d T=%d; C in {64, 128, 256}, 1 <= items <= %d per call)", R, C,
-                 i1 - i0, T, evr::MAX_ITEMS);
+                 i1 - i0, T, evs::MAX_ITEMS);
     evr::P p{};
     p.rows = (const bf16*)rows; p.table = (const bf16*)table; p.bias = out_bias; p.seen = seen; p.labels = labels; p.label_val = label_val;
     p.T = T; p.R = R; p.I = I; p.i0 = i0; p.i1 = i1; p.nslices = pl.nslices; p.tps = pl.tps; p.count = count;
     hipStream_t st = (hipStream_t)stream;
-    if (C == 64) return evr::launch<64, 128, 4>(p, pl, st);
-    if (C == 128) return evr::launch<128, 128, 4>(p, pl, st);
-    return evr::launch<256, 64, 2>(p, pl, st);
+    return evs::sweep_dispatch(C, [&](auto g) { return evr::launch<g.C, g.NZ, g.NWS>(p, pl, st); });
 }
 
 extern "C" int edgl_label_value_tile(const float* logits, int R, int n, int i0, const int64_t* seen, int T, const int64_t* labels,

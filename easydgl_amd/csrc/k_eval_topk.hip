@@ -18,24 +18,20 @@
 //                              mask, radix select (topk_select.h)
 // Four launches; every launch boundary costs ~4.5 us on this device (the first build had six and was slower than the two kernels it
 // replaced), so nothing small stands alone: the overflow list and the exact fallback live inside the ranking launch.
-// Both sweeps: a workgroup = 64 rows x one item slice; item tiles of NZ rows stream through a double-buffered LDS image, the 64 query
-// rows stay in registers as MFMA B fragments; D[item][query] = Z . X^T with v_mfma_f32_32x32x16_bf16 (items on the accumulator
-// registers, the query on the lane: a lane's 16 values of a tile belong to ONE row, so group maxima and threshold tests need no
-// cross-lane traffic).  bf16, C in {64, 128, 256}.
+// Both sweeps are eval_sweep.h's sweep (workgroup = query block x item slice, tile ring, seen bitmap, bias-started MFMA chain).  This
+// file adds what they do with an MFMA tile's 16 logits per lane — pass 1: group maxima, pass 2: runs with a hit into the workgroup's
+// list — with pass 2's LDS regions (run list, dump slots, counts, seen bitmap) and its epilogue, the bound, the ranking and the plan.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
+#include "eval_sweep.h"
 #include "topk_select.h"
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 namespace evk {
+using namespace evs;
 
 constexpr int GPS = 16;                        // groups per (row, slice)
-// query rows per workgroup: 64; 128 at C = 256, where the table no longer fits an L2 at the catalogues this width is used with and
-// every query block reads every slice again (1 M items x 512 B: the sweeps ran on the L2 -> LDS traffic of 8 query blocks)
-__host__ __device__ constexpr int qb_of(int C) { return C == 256 ? 128 : 64; }
 constexpr int RSTR = 24;          // pass 2: a workgroup's LDS list of RUNS — 4 logits of consecutive items | hit mask + row | first item
 constexpr int OVERFLOW = 0x40000000;           // added to a row's count when a list dropped entries
 
@@ -49,81 +45,37 @@ struct P {
     float* out_val; int32_t* out_idx;
 };
 
-// NWS: waves across the items of a tile (the workgroup is QB / 32 x NWS waves: 32 query rows x NZ / NWS items each).  Four at C <= 128 —
-// two waves per SIMD: the sweep's MFMA chains and the second sweep's hit bookkeeping are one dependent stream per wave, and a lone
-// wave per SIMD has nothing to put into the other's shadow.
 template <int C, int NZ, int NWS>
-struct Geo {
-    static constexpr int QB = qb_of(C);
-    static constexpr int NTHR = 64 * (QB / 32) * NWS;
+struct Geo : SweepGeo<C, NZ, NWS> {
+    using S = SweepGeo<C, NZ, NWS>;
+    static constexpr int QB = S::QB, NTHR = S::NTHR;
     static constexpr int RCAP = QB == 64 ? 1024 : 1536;       // runs a workgroup's list holds (more of them: every row goes the exact way)
-    static constexpr int LDZ = C + 8;                          // bf16 elements per LDS row (16-byte shift per row: conflict-free 16-byte fragment reads)
-    static constexpr int ZB = NZ * LDZ * 2;
-    static constexpr int OFF_Z = 0, OFF_BIAS = 2 * ZB, OFF_LIST = OFF_BIAS + 2 * NZ * 4;
+    static constexpr int OFF_LIST = S::OFF_OWN;
     static constexpr int LISTB = RCAP * RSTR, DUMB = NTHR * RSTR;   // the run list; one dump slot per thread (stores without a branch)
     static constexpr int OFF_DUM = OFF_LIST + LISTB;
     static constexpr int OFF_CNT = OFF_DUM + DUMB;             // list length, then per-row counts [QB] and global bases [QB]
     static constexpr int OFF_BMP = OFF_CNT + 16 + 2 * QB * 4;  // seen bitmap [QB][words]
-    static constexpr int BYTES_GMAX = OFF_BIAS + 2 * NZ * 4;
+    static constexpr int BYTES_GMAX = S::OFF_OWN;
     static constexpr int bytes_emit(int slice_items) { return OFF_BMP + QB * ((slice_items + 31) / 32) * 4; }
-    static constexpr int PIECES = NZ * C / 8 / NTHR;           // 16-byte pieces of an item tile per thread
-    static_assert(NZ * C / 8 % NTHR == 0 && NZ % (32 * NWS) == 0 && 8 % NWS == 0 && PIECES >= 1, "tile geometry");
+    static_assert(NZ * C / 8 % NTHR == 0 && NZ % (32 * NWS) == 0 && 8 % NWS == 0 && S::PIECES >= 1, "tile geometry");
 };
-
-// one item tile: global -> registers (rows clamped into the table; item 0 is the zero-padded row: coding.py:56-57)
-template <int C, int NZ, int NWS>
-__device__ __forceinline__ void tile_load(const P& p, int item0, uint4 (&r)[Geo<C, NZ, NWS>::PIECES], float& b) {
-    constexpr int CP = C / 8, NTHR = Geo<C, NZ, NWS>::NTHR;
-#pragma unroll
-    for (int j = 0; j < Geo<C, NZ, NWS>::PIECES; ++j) {
-        const int pc = threadIdx.x + NTHR * j, row = pc / CP, c8 = pc % CP;
-        const int item = min(item0 + row, p.I - 1);
-        r[j] = *reinterpret_cast<const uint4*>(p.table + (long)item * C + c8 * 8);
-    }
-    const int it = item0 + (int)threadIdx.x;   // (threads < NZ: the tile's bias row — EasyDGL.py:149-151, Base.py:110)
-    b = (threadIdx.x < NZ && it < p.i1 && it > 0) ? p.bias[min(it, p.I - 1) - 1] : 0.f;
-}
-template <int C, int NZ, int NWS>
-__device__ __forceinline__ void tile_store(const P& p, int item0, uint4 (&r)[Geo<C, NZ, NWS>::PIECES], float b, char* zbuf, float* bbuf) {
-    constexpr int CP = C / 8, NTHR = Geo<C, NZ, NWS>::NTHR;
-#pragma unroll
-    for (int j = 0; j < Geo<C, NZ, NWS>::PIECES; ++j) {
-        const int pc = threadIdx.x + NTHR * j, row = pc / CP, c8 = pc % CP;
-        if (item0 + row == 0) r[j] = make_uint4(0u, 0u, 0u, 0u);
-        *reinterpret_cast<uint4*>(zbuf + row * (Geo<C, NZ, NWS>::LDZ * 2) + c8 * 16) = r[j];
-    }
-    if (threadIdx.x < NZ) {
-        const int it = item0 + (int)threadIdx.x;
-        bbuf[threadIdx.x] = it >= p.i1 ? -INFINITY : (it == 0 ? -1000.0f : b);
-    }
-}
 
 // EMIT = false: pass 1 (group maxima);  true: pass 2 (candidates)
 template <int C, int NZ, int NWS, bool EMIT>
 __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void eval_sweep_kernel(P p) {
     using G_ = Geo<C, NZ, NWS>;
-    constexpr int CK = C / 16, NTW = NZ / (32 * NWS), LDZB = G_::LDZ * 2, NTHR = G_::NTHR;
+    constexpr int CK = C / 16, NTW = NZ / (32 * NWS), NTHR = G_::NTHR;
     constexpr int JG = 8 / NWS;       // group maxima per lane (GPS = 16 groups per slice = NWS waves x 2 lane halves x JG)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int QB = G_::QB, RCAP = G_::RCAP;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = wave / NWS, sw = wave % NWS, l32 = lane & 31, hi = lane >> 5;
-    // XCD-aware order (speed only; observed placement: workgroup id b runs on XCD b % 8): the query blocks of ONE item slice are
-    // consecutive workgroups of ONE XCD, so that they run side by side and the slice's table rows come out of that XCD's L2 for all
-    // but the first of them — in (query block, slice) grid order the 8 query blocks of a slice sat on 8 XCDs and every one of them
-    // pulled the slice from HBM (1 M items: 8 x 512 MB per sweep)
-    const int nqb = (p.R + QB - 1) / QB;
-    const int xcd = (int)blockIdx.x & 7, jx = (int)blockIdx.x >> 3;
-    const int slice = (jx / nqb) * 8 + xcd;
+    const int slice = sweep_slice<QB>(p);
     if (slice >= p.nslices) return;
-    const int q0 = (jx % nqb) * QB;
+    const int q0 = sweep_qblock<QB>(p) * QB;
     int* lcount = reinterpret_cast<int*>(smem + G_::OFF_CNT);
-    // ---- this wave's 32 query rows as B fragments, straight from global memory (once per workgroup: no LDS image) -------------------
     bf16x8 xf[CK];
-    {
-        const bf16* xrow = p.rows + (long)min(q0 + 32 * h + l32, p.R - 1) * C + hi * 8;
 #pragma unroll
-        for (int k = 0; k < CK; ++k) xf[k] = *reinterpret_cast<const bf16x8*>(xrow + k * 16);
-    }
+    for (int k = 0; k < CK; ++k) xf[k] = query_frag<C>(p, q0 + 32 * h + l32, hi, k);
     int* rowcnt = lcount + 4;                     // [QB] survivors per row, then [QB] the rows' bases in their global lists
     uint32_t* bmp = reinterpret_cast<uint32_t*>(smem + G_::OFF_BMP);
     const int bw = (p.tps * NZ + 31) / 32;        // bitmap words per row
@@ -135,9 +87,6 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void eval_sweep_kernel(
     const int tile_lo = slice * p.tps, ntile_all = (p.i1 - p.i0 + NZ - 1) / NZ;
     const int tile_hi = min(ntile_all, tile_lo + p.tps);
     const int tstep = EMIT ? 1 : p.stride;
-    // Two register staging sets: the loads of tile t + 2 leave while tile t is multiplied and tile t + 1 waits in the other set for
-    // its LDS buffer — with one set a workgroup had ONE 32 KB tile in flight per 2 us memory round trip (the sweep ran at 9 % of
-    // the matrix pipe on a 1 M-item table).  Out-of-range tiles are loaded clamped and never stored.
     uint4 stg[G_::PIECES], stg2[G_::PIECES];
     float stb, stb2;
     if (tile_lo < tile_hi) {
@@ -147,11 +96,8 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void eval_sweep_kernel(
     }
     __syncthreads();
     if constexpr (EMIT) {
-        // the rows' seen ids that fall into this slice as a bitmap (Base.py:156-163): all loads of a batch out before the first LDS
-        // atomic (a load -> atomic loop is one memory round trip per id: 25 per thread)
+        // the rows' seen ids that fall into this slice as a bitmap (Base.py:156-163; the loads in batches: eval_sweep.h)
         const int item_lo = p.i0 + tile_lo * NZ, item_hi = min(p.i1, p.i0 + tile_hi * NZ);
-        // the 64 rows' ids are one contiguous run of int64 (16-byte aligned: 64 T ids per row block): pairs by 16-byte loads, up to
-        // 16 in flight per thread — one memory round trip at T = 101, two at T = 201
         const int nid = min(QB, p.R - q0) * p.T, npair = nid / 2;
         const int64_t* sbase = p.seen + (long)q0 * p.T;
         auto mark = [&](int i, int64_t v) {
@@ -182,28 +128,15 @@ __global__ __launch_bounds__(64 * (qb_of(C) / 32) * NWS) void eval_sweep_kernel(
     float thr = 0.f;
     if constexpr (EMIT) thr = p.thr[min(q, p.R - 1)];
     int buf = 0;
-    // one trip = two tiles: tile t from LDS buffer `buf` with set A holding tile t + 1 and set B taking tile t + 2, then the same with
-    // the sets swapped (static names: register arrays cannot be indexed by the trip's parity)
+    // the tile ring (eval_sweep.h): tile t from LDS buffer `buf` with set A holding tile t + 1 and set B taking tile t + 2
     auto one_tile = [&](int t, uint4 (&sa)[G_::PIECES], float& ba, uint4 (&sb)[G_::PIECES], float& bbn) {
         const int tn = t + tstep, tnn = t + 2 * tstep;
         if (tnn < tile_hi) tile_load<C, NZ, NWS>(p, p.i0 + tnn * NZ, sb, bbn);
         asm volatile("" ::: "memory");
-        const char* zb = smem + G_::OFF_Z + buf * G_::ZB;
-        const float* bb = reinterpret_cast<const float*>(smem + G_::OFF_BIAS) + buf * NZ;
 #pragma unroll
         for (int u = 0; u < NTW; ++u) {
             const int m0 = (sw * NTW + u) * 32;               // the MFMA tile's first item row inside the LDS tile
-            f32x16 acc;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                     // D[m][n] starts from the item's bias: m = 8 j + 4 hi + i
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(bb + m0 + 8 * j + 4 * hi);
-                acc[4 * j] = b4[0]; acc[4 * j + 1] = b4[1]; acc[4 * j + 2] = b4[2]; acc[4 * j + 3] = b4[3];
-            }
-#pragma unroll
-            for (int k = 0; k < CK; ++k) {
-                const bf16x8 zf = *reinterpret_cast<const bf16x8*>(zb + (m0 + l32) * LDZB + k * 32 + hi * 16);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(zf, xf[k], acc, 0, 0, 0);
-            }
+            const f32x16 acc = score_tile<C, NZ, NWS>(smem, buf, m0, l32, hi, xf);
             if constexpr (!EMIT) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -446,23 +379,22 @@ __global__ __launch_bounds__(256) void eval_rank_kernel(P p) {
     radix_select_row(x, ni, p.i0, K, ov, oi);
 }
 
-constexpr int MAX_ITEMS = 262144;     // per call: 64 item slices of <= 4096 items (the seen bitmap of a workgroup: 32 KB of LDS)
 struct Plan { int nz, nslices, tps, stride, G, cap; size_t off_thr, off_count, off_cval, off_cidx, off_scratch, bytes; };
 inline bool make_plan(int R, int C, int n_items, int T, int K, Plan& pl) {
     if (!(C == 64 || C == 128 || C == 256) || K < 1 || K > 128 || R < 1 || T < 0 || n_items < 4096 || n_items > (1 << 30)) return false;
-    pl.nz = C == 256 ? 64 : 128;
+    pl.nz = nz_of(C);
     const int ntile = (n_items + pl.nz - 1) / pl.nz;
     const int QB = qb_of(C);
     const int nrb = (R + QB - 1) / QB;
     // fill the chip AND keep the bound selective: three times as many groups as the rank of the bound among them
     int want = std::max(256 / std::max(nrb, 1), (3 * (K + T) + GPS - 1) / GPS);
-    want = std::max(want, (n_items + (C == 256 ? 2047 : 4095)) / (C == 256 ? 2048 : 4096));   // a slice's seen bitmap
+    want = std::max(want, (n_items + slice_cap(C) - 1) / slice_cap(C));   // a slice's seen bitmap
     want = std::min(std::min(want, 64), ntile);
     pl.tps = (ntile + want - 1) / want;
     pl.nslices = (ntile + pl.tps - 1) / pl.tps;
     pl.G = pl.nslices * GPS;
     // (the seen bitmap of a workgroup: 64 rows x its slice's items / 8 bytes of LDS beside the tiles and the entry list)
-    if (pl.G < K + T + GPS || pl.G > 1024 || pl.tps * pl.nz > (C == 256 ? 2048 : 4096) + pl.nz) return false;
+    if (pl.G < K + T + GPS || pl.G > 1024 || pl.tps * pl.nz > slice_cap(C) + pl.nz) return false;
     // Expected candidates per row: a group maximum reaches the bound with probability P = rank / G, so an element does with
     // p = 1 - (1 - P)^(1 / group size) and a row lists n p of them (iid scores; real ones cluster less than the cap's margin).  Pass 1
     // over every second tile halves the groups (the bound stays valid: the sampled groups are disjoint item sets all the same) and
@@ -488,7 +420,7 @@ template <int C, int NZ, int NWS>
 int launch(P p, const Plan& pl, hipStream_t st) {
     using G_ = Geo<C, NZ, NWS>;
     constexpr int NTHR = G_::NTHR;
-    const dim3 grid(8 * ((p.R + G_::QB - 1) / G_::QB) * ((pl.nslices + 7) / 8));      // (query block, slice) from the id: see eval_sweep_kernel
+    const dim3 grid(sweep_grid(p.R, G_::QB, pl.nslices));
     auto k1 = eval_sweep_kernel<C, NZ, NWS, false>;
     auto k2 = eval_sweep_kernel<C, NZ, NWS, true>;
     const int be = G_::bytes_emit(pl.tps * NZ);
@@ -510,7 +442,7 @@ int launch(P p, const Plan& pl, hipStream_t st) {
 // (logits tile) + edgl_mask_topk.  There is no silent fallback inside the library.
 extern "C" int edgl_score_topk_fused_supported(int R, int C, int n_items, int T, int K, int dtype) {
     evk::Plan pl;
-    return dtype == EDGL_BF16 && n_items <= evk::MAX_ITEMS && evk::make_plan(R, C, n_items, T, K, pl) ? 1 : 0;
+    return dtype == EDGL_BF16 && n_items <= evs::MAX_ITEMS && evk::make_plan(R, C, n_items, T, K, pl) ? 1 : 0;
 }
 extern "C" long edgl_score_topk_fused_workspace(int R, int C, int n_items, int T, int K) {
     evk::Plan pl;
@@ -525,7 +457,7 @@ extern "C" int edgl_score_topk_fused(const void* rows, const void* table, const 
     EDGL_REQUIRE(dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_score_topk_fused: bf16 only (dtype %d)", dtype);
     EDGL_REQUIRE(I > 1 && i0 >= 0 && i1 <= I && i0 < i1 && i0 % 8 == 0, EDGL_ERR_SHAPE, "edgl_score_topk_fused: bad item range [%d, %d) of %d", i0, i1, I);
     evk::Plan pl;
-    EDGL_REQUIRE(i1 - i0 <= evk::MAX_ITEMS && evk::make_plan(R, C, i1 - i0, T, K, pl), EDGL_ERR_SHAPE,
+    EDGL_REQUIRE(i1 - i0 <= evs::MAX_ITEMS && evk::make_plan(R, C, i1 - i0, T, K, pl), EDGL_ERR_SHAPE,
                  "edgl_score_topk_fused: shape not taken (R=%d C=%d items=%d T=%d K=%d; see edgl_score_topk_fused_supported)", R, C, i1 - i0, T, K);
     char* ws = (char*)workspace;
     evk::P p{};
@@ -536,7 +468,5 @@ extern "C" int edgl_score_topk_fused(const void* rows, const void* table, const 
     p.cidx = reinterpret_cast<int32_t*>(ws + pl.off_cidx); p.cap = pl.cap;
     p.scratch = reinterpret_cast<float*>(ws + pl.off_scratch); p.out_val = out_val; p.out_idx = out_idx;
     hipStream_t st = (hipStream_t)stream;
-    if (C == 64) return evk::launch<64, 128, 4>(p, pl, st);
-    if (C == 128) return evk::launch<128, 128, 4>(p, pl, st);
-    return evk::launch<256, 64, 2>(p, pl, st);
+    return evs::sweep_dispatch(C, [&](auto g) { return evk::launch<g.C, g.NZ, g.NWS>(p, pl, st); });
 }
