@@ -8,10 +8,40 @@ import torch
 from torch import nn
 
 from .. import ops
+from ..module.coding import glorot_uniform_
+
+
+class _Dense(nn.Module):
+    """tf.layers.dense parameters: kernel [in,out] glorot_uniform, bias zeros."""
+
+    def __init__(self, n_in, n_out, gen):
+        super().__init__()
+        self.kernel = nn.Parameter(glorot_uniform_(torch.empty(n_in, n_out), gen))
+        self.bias = nn.Parameter(torch.zeros(n_out))
+
+
+class _LayerNorm(nn.Module):
+    """Base.layernorm parameters (Base.py:36-49): beta zeros, gamma ones over the last axis."""
+
+    def __init__(self, n):
+        super().__init__()
+        self.beta = nn.Parameter(torch.zeros(n))
+        self.gamma = nn.Parameter(torch.ones(n))
+
+
+class _FeedForward(nn.Module):
+    """Base.FeedForward([C, C]) (Base.py:70-87): Conv1D(k=1, relu) -> dropout -> Conv1D(k=1) -> dropout -> + input."""
+
+    def __init__(self, C_, gen):
+        super().__init__()
+        self.inner = _Dense(C_, C_, gen)      # dense/Inner
+        self.readout = _Dense(C_, C_, gen)    # dense/Readout
 
 
 class Sequential(nn.Module):
     """Base.py:90-207.  Reads the same FLAGS fields as the reference (Base.py:92-104)."""
+
+    tf_numpy = True     # tf_values() / tf_gradients() hand float32 numpy arrays out (EasyDGL: tensors on the parameters' device)
 
     def __init__(self, num_items, FLAGS):
         super().__init__()
@@ -28,7 +58,8 @@ class Sequential(nn.Module):
         cd = getattr(FLAGS, "compute_dtype", "bf16")
         self.act_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}[cd]
         self._arena: Optional[torch.Tensor] = None
-        self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (EasyDGL at a head dim the kernels do not tile)
+        self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (a head dim the kernels do not tile)
+        self._metrics = None
         # hand-over state between this model and the static engines that train it (engine.TrainEngine)
         self._state_ahead = False        # the step counters already hold the NEXT step's values (settle_state undoes it)
         self._state_pinned = False       # a captured graph keeps the counters' addresses: no engine swaps the buffers any more
@@ -158,7 +189,10 @@ class Sequential(nn.Module):
         step.warmup_loss = warm_loss   # loss of the last eager warm-up step (a real optimizer step on the capture batch)
         return step
 
-    # ---- channel padding (TGAT / TiSASRec / CTSMA; EasyDGL has its own forms of the same in model/easydgl.py) -----------------
+    # ---- the variable table and channel padding --------------------------------------------------------------------------------
+    # A model lists its variables ONCE, in _pad_specs(): (TF name, parameter, per-axis index map reference -> stored or None for an
+    # axis kept whole, initialiser of the reference-shaped variable).  tf_values() / tf_gradients() / load_tf_variables() /
+    # padded_leak() / _init_padded() / mask_padded_grads() below are derived from that list and speak the reference's shapes.
     # A head dim the attention kernels do not tile (they take 16 / 32 / 64 / 128; the reference's own default is --num_units 50
     # --num_heads 1, main.py:35-37) runs at the next supported head dim with ZERO-PADDED channels: every parameter is stored at the
     # padded width, head h's true channels sit at [h * dh_pad, h * dh_pad + dh_true), the padded rows / columns are zero and stay
@@ -166,9 +200,8 @@ class Sequential(nn.Module):
     # LayerNorms take their moments over the real channels and return nothing into the padded ones); the score scale 1 / sqrt(dh)
     # and coding.py's sqrt(num_units) are those of the TRUE width.  What is not zero on a padded entry by itself (rounding residue
     # of a softmax backward's row sums against TGAT's constant time code, the intensity MLP's padded hidden units) is zeroed by
-    # mask_padded_grads in front of every optimizer launch.  tf_values() / tf_gradients() / load_tf_variables() speak the
-    # reference's shapes.  A model lists its variables in _pad_specs(): (TF name, parameter, per-axis index map true -> padded or
-    # None, initialiser of the TRUE-shape variable).
+    # mask_padded_grads in front of every optimizer launch.  The index maps come from _cmap() / _mlp_maps(); without padding they
+    # are the identity (plus the offset of a column block), so an unpadded model is the trivial case of the same code.
     def _setup_channel_pad(self, who: str, max_pad_dim: int = 128) -> None:
         from ..module import temporal as T
         self.width_true = self.num_units
@@ -184,20 +217,41 @@ class Sequential(nn.Module):
         self.num_units = H * dhp
         self.qk_scale = float(dht) ** -0.5
 
+    def _finish_pad(self, gen) -> None:
+        """End of a constructor: a padded model hands its attention units the true score scale and redraws its variables."""
+        if self.pad[0]:
+            for blk in self.layers:
+                blk.attention.qk_scale = self.qk_scale
+            self._init_padded(gen)
+
+    def _head_dims(self):
+        """(stored, reference) head dim."""
+        return self.pad if self.pad[0] else (self.num_units // self.num_heads,) * 2
+
     def _cmap(self, blocks: int = 1) -> torch.Tensor:
-        """True channel -> padded channel, for `blocks` concatenated [C]-wide column blocks (K | V, item | position ...)."""
-        dhp, dht = self.pad
+        """True channel -> stored channel, for `blocks` concatenated [C]-wide column blocks (K | V, item | position ...)."""
+        dhp, dht = self._head_dims()
         c = torch.arange(self.width_true)
         one = (c // dht) * dhp + (c % dht)
         return torch.cat([one + k * self.num_units for k in range(blocks)])
+
+    def _mlp_maps(self):
+        """Maps of the intensity MLP (temporal.BiMAU / MAU): its input rows (dh channels + the span), its hidden units (e, u) and
+        the u axis of its output weights."""
+        dhp, dht = self._head_dims()
+        j = torch.arange(dht * self.num_events)
+        return torch.cat([torch.arange(dht), torch.tensor([dhp])]), (j // dht) * dhp + (j % dht), torch.arange(dht)
 
     def _pad_specs(self):
         raise NotImplementedError
 
     @staticmethod
     def _spec_index(t, maps):
-        idx = [torch.arange(t.shape[a]) if m is None else m for a, m in enumerate(maps)]
-        return torch.meshgrid(*[i.to(t.device) for i in idx], indexing="ij")
+        """Index of the reference-shaped variable inside the stored tensor `t`: the outer product of the mapped axes, an axis kept
+        whole as a slice (a million-row table is not indexed element by element)."""
+        mapped = [m.to(t.device) for m in maps if m is not None]
+        grid = iter(torch.meshgrid(*mapped, indexing="ij") if mapped else ())
+        return tuple(slice(None) if m is None else next(grid) for m in maps)
 
     @staticmethod
     def _spec_shape(p, maps):
@@ -205,9 +259,9 @@ class Sequential(nn.Module):
 
     @torch.no_grad()
     def _init_padded(self, gen) -> None:
-        """The reference's initialisers on the TRUE shapes (glorot limits of the true fans), scattered into zeroed padded storage."""
+        """The reference's initialisers on the TRUE shapes (glorot limits of the true fans), scattered into zeroed padded storage.
+        Draws from `gen` in the order of the table."""
         import numpy as np
-        from ..module.coding import glorot_uniform_
         specs = self._pad_specs()
         for _, p, _, _ in specs:
             p.data.zero_()
@@ -215,6 +269,8 @@ class Sequential(nn.Module):
             shp = self._spec_shape(p, maps)
             if kind == "glorot":
                 v = glorot_uniform_(torch.empty(shp), gen)
+            elif kind == "normal":         # temporal.py:393 N(0, 0.02): BiMAU's QKVT kernel
+                v = torch.randn(shp, generator=gen) * 0.02
             elif kind == "ones":
                 v = torch.ones(shp)
             elif kind == "linspace9":      # coding.py:104-108 TimeFunctionCoding.basis_freq
@@ -285,8 +341,22 @@ class Sequential(nn.Module):
             out[name] = t.detach()[self._spec_index(t, maps)].clone()
         return out
 
+    def _tf_out(self, vals):
+        return {k: v.float().cpu().numpy() for k, v in vals.items()} if self.tf_numpy else vals
+
+    def tf_values(self):
+        """Reference variable name -> value in the REFERENCE's shape (a copy; channel-padded models strip the padding)."""
+        return self._tf_out(self._padded_values(False))
+
+    def tf_gradients(self):
+        """Reference variable name -> gradient of the last backward in the reference's shape (a copy; K | V (| T_) kernels that are
+        stored as one matrix come back as the reference's dense_1 .. dense_3)."""
+        return self._tf_out(self._padded_values(True))
+
     @torch.no_grad()
-    def _load_padded(self, values) -> None:
+    def load_tf_variables(self, values) -> None:
+        """`values`: TF variable name (scope `main/` stripped) -> array in the reference's shape, as the oracles' init_params list
+        them; any other shape is refused."""
         import numpy as np
         specs = self._pad_specs()
         for _, p, _, _ in specs:
@@ -322,3 +392,92 @@ class Sequential(nn.Module):
     def make_output_bias(self) -> nn.Parameter:
         """output_bias(inf_pad=True): variable [num_items-1] zeros; the used bias is concat([-1000], var)."""
         return nn.Parameter(torch.zeros(self.num_items - 1))
+
+    # ---- helpers of the models' forward passes ---------------------------------------------------------------
+    def _drop(self, rate, stream_id, is_training) -> ops.Drop:
+        if not is_training or rate <= 0.0:
+            return ops.NO_DROP
+        return ops.Drop(rate, self._rng_state, stream_id)
+
+    def _linear(self, x, d: _Dense, act=False):
+        return ops.LinearFn.apply(x, d.kernel, d.bias, self.compute(d.kernel), act)
+
+    def _feed_forward(self, y, ff: _FeedForward, i, ids, is_training):
+        """Base.FeedForward of block `i` behind its LayerNorm `y` (Base.py:79-86); `ids`: ff_tail's key ids (TGAT.py:70) or None."""
+        hd = self.hidden_dropout_rate
+        inner = self._linear(y, ff.inner, "relu")                                                            # Base.py:79
+        if is_training and hd > 0.0:   # Base.py:80: dropout(inner) — an identity LayerNorm-free path: a scaled copy
+            inner = ops.dropout(inner, self._drop(hd, 11 + 4 * i, True))
+        out = self._linear(inner, ff.readout)                                                                # Base.py:82
+        return ops.ff_tail(out, y, ids, self._drop(hd, 12 + 4 * i, is_training))                             # Base.py:83-86
+
+    @staticmethod
+    def _last_pos(ids):
+        """Gather index [B, 1] of the last position: the row an evaluation scores."""
+        return torch.full((ids.shape[0], 1), ids.shape[1] - 1, device=ids.device, dtype=torch.int64)
+
+    @staticmethod
+    def _last_labels(labels):
+        return (labels[:, -1] if labels.dim() == 2 else labels).contiguous()
+
+    # ---- Sequential.train (Base.py:119-144) ------------------------------------------------------------------
+    def train_step(self, features, labels):
+        """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar)."""
+        self.settle_state()
+        ops.rng_advance(self._rng_state)
+        self.detach_grads()
+        loss = self.train_loss(features, labels)
+        loss.backward()
+        self.collect_grads()
+        self.mask_padded_grads()
+        self.optimizer_step()
+        return loss.detach()
+
+    # ---- Sequential.eval (Base.py:150-207) -------------------------------------------------------------------
+    @torch.no_grad()
+    def eval_topk(self, features, mask_seen=True, K=100):
+        logits = self.forward(features, False)
+        return ops.mask_topk(logits, 0, features["seqs_i"] if mask_seen else None, K)
+
+    @torch.no_grad()
+    def eval_rank(self, features, labels, mask_seen=True):
+        """int32 [B]: the label's place in the (logit desc, item id asc) order of the unseen catalogue (Base.py:150-201), counted on the
+        materialised logits — no top-K list, the logits are left as they are."""
+        logits = self.forward(features, False)
+        return ops.rank_from_logits(logits, 0, features["seqs_i"] if mask_seen else None, self._last_labels(labels))
+
+    def reset_metrics(self, ks=None):
+        """`ks`: the cut-offs of the by-rank metrics (eval_step(by_rank=True)); default (10, 50, 100), at most 8."""
+        dev = self._arena.device
+        self._metrics = torch.zeros(6, device=dev, dtype=torch.float32)
+        self._metric_count = 0
+        self._rank_ks = tuple(int(k) for k in (ks or (10, 50, 100)))
+        if not 1 <= len(self._rank_ks) <= 8:
+            raise ValueError(f"reset_metrics: 1 to 8 cut-offs (got {self._rank_ks})")
+        self._rank_ks_dev = torch.tensor(self._rank_ks, device=dev, dtype=torch.int32)
+        self._rank_sums = torch.zeros(2 * len(self._rank_ks) + 1, device=dev, dtype=torch.float32)
+        self._rank_count = 0
+
+    @torch.no_grad()
+    def eval_step(self, features, labels, mask_seen=True, by_rank=False):
+        if self._metrics is None:
+            self.reset_metrics()
+        if by_rank:
+            if self._metric_count != self._rank_count:
+                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
+            ops.rank_metrics_from_rank(self.eval_rank(features, labels, mask_seen), self._rank_ks_dev, self._rank_sums)
+            self._rank_count += labels.shape[0]
+        else:
+            if self._rank_count:
+                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
+            _, idx = self.eval_topk(features, mask_seen)
+            ops.rank_metrics(idx, labels[:, -1].contiguous(), self._metrics)
+        self._metric_count += labels.shape[0]
+
+    def metrics(self) -> Dict[str, float]:
+        if getattr(self, "_rank_count", 0):     # by-rank steps: H / N at the chosen cut-offs and the mean reciprocal rank
+            vals = (self._rank_sums / self._rank_count).tolist()
+            names = [f"H{k}" for k in self._rank_ks] + [f"N{k}" for k in self._rank_ks] + ["MRR"]
+            return dict(zip(names, vals))
+        vals = (self._metrics / max(1, self._metric_count)).tolist()
+        return dict(zip(("H10", "H50", "H100", "N10", "N50", "N100"), vals))

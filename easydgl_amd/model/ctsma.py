@@ -21,17 +21,7 @@ from torch import nn
 from .. import ops
 from ..module import coding as C
 from ..module import temporal as T
-from .base import Sequential
-from .easydgl import EasyDGL, _Dense, _LayerNorm
-
-
-class _FeedForward(nn.Module):
-    """Base.FeedForward([C, C]) (Base.py:70-87): Conv1D(k=1, relu) -> dropout -> Conv1D(k=1) -> dropout -> + input."""
-
-    def __init__(self, C_, gen):
-        super().__init__()
-        self.inner = _Dense(C_, C_, gen)      # dense/Inner
-        self.readout = _Dense(C_, C_, gen)    # dense/Readout
+from .base import Sequential, _FeedForward, _LayerNorm
 
 
 class _Block(nn.Module):
@@ -70,20 +60,14 @@ class CTSMA(Sequential):
             self.layers.append(_Block(2 * C_ if i == 0 else C_, C_, self.num_heads, self.num_events,
                                       self.attention_probs_dropout_rate, gen))
         self.out_ln = _LayerNorm(C_)                                                                         # outln
-        self._metrics = None
-        if self.pad[0]:
-            for blk in self.layers:
-                blk.attention.qk_scale = self.qk_scale
-            self._init_padded(gen)
+        self._finish_pad(gen)
 
     def _pad_specs(self):
-        """(TF name, parameter, axis maps true -> padded, initialiser) of every variable, for the channel-padded storage."""
-        dhp, dht = self.pad
-        E, Cp = self.num_events, self.num_units
+        """The variable table (model/base.py): (TF name, parameter, axis maps reference -> stored, initialiser).  K | V | T_ are
+        one stored matrix whose column blocks are the reference's dense_1 .. dense_3."""
+        Cp = self.num_units
         c = self._cmap()
-        j = torch.arange(dht * E)
-        jmap = (j // dht) * dhp + (j % dht)                                   # hidden unit (e, u) of the intensity MLP
-        st_rows = torch.cat([torch.arange(dht), torch.tensor([dhp])])        # its inputs: dh channels + the span
+        st_rows, jmap, u = self._mlp_maps()        # intensity MLP: inputs (dh channels + the span), hidden units (e, u), output u
         sp = [("CSTMA/item_embs/lookup_table", self.item_embs.lookup_table, (None, c), "glorot"),
               ("CSTMA/spatial_embs/embedding/lookup_table", self.pcoding.pembs.lookup_table, (None, c), "glorot"),
               ("CSTMA/output_bias", self.output_bias, (None,), "zeros"),
@@ -101,7 +85,7 @@ class CTSMA(Sequential):
                 sp += [(a + f"dense_{k}/kernel", att.kvt_kernel, (cin, c + (k - 1) * Cp), "glorot"),
                        (a + f"dense_{k}/bias", att.kvt_bias, (c + (k - 1) * Cp,), "zeros")]
             sp += [(st + "dense/kernel", att.st_kernel, (st_rows, jmap), "glorot"), (st + "dense/bias", att.st_bias, (jmap,), "zeros"),
-                   (st + "weight", att.weight, (None, torch.arange(dht)), "glorot"), (st + "scaling", att.scaling, (None,), "zeros"),
+                   (st + "weight", att.weight, (None, u), "glorot"), (st + "scaling", att.scaling, (None,), "zeros"),
                    (pre + "feed-forward/LayerNorm/gamma", blk.ff_ln.gamma, (c,), "ones"),
                    (pre + "feed-forward/LayerNorm/beta", blk.ff_ln.beta, (c,), "zeros"),
                    (pre + "feed-forward/Inner/kernel", blk.ff.inner.kernel, (c, c), "glorot"),
@@ -112,19 +96,6 @@ class CTSMA(Sequential):
 
     def l2_param_names(self):
         return ["item_embs.lookup_table", "pcoding.pembs.lookup_table"]
-
-    def finalize(self, device):
-        super().finalize(device)
-        for blk in self.layers:
-            blk.attention.compute = self.compute
-        return self
-
-    _drop = EasyDGL._drop
-    reset_metrics = EasyDGL.reset_metrics
-    metrics = EasyDGL.metrics
-
-    def _linear(self, x, d: _Dense, act=False):
-        return ops.LinearFn.apply(x, d.kernel, d.bias, self.compute(d.kernel), act)
 
     def encoder(self, features, is_training, gather_pos):
         """CTSMA.py:48-83: (rows [B*Mg, C] of the final LayerNorm at gather_pos (None: all positions), [lambda])."""
@@ -141,19 +112,13 @@ class CTSMA(Sequential):
             att, lam = blk.attention(q_in, x, ids, spans, marks, is_training, True,
                                      drop=self._drop(self.attention_probs_dropout_rate, 10 + 4 * i, is_training))
             y = ops.AddLayerNormFn.apply(att, None, blk.ff_ln.gamma, blk.ff_ln.beta, ops.NO_DROP, None, pad)     # :75
-            inner = self._linear(y, blk.ff.inner, "relu")                                                        # Base.py:79
-            if is_training and hd > 0.0:   # Base.py:80: dropout(inner) — an identity LayerNorm-free path: a scaled copy
-                inner = ops.dropout(inner, self._drop(hd, 11 + 4 * i, True))
-            out = self._linear(inner, blk.ff.readout)                                                            # Base.py:82
-            x = ops.ff_tail(out, y, None, self._drop(hd, 12 + 4 * i, is_training))                               # Base.py:83-86
+            x = self._feed_forward(y, blk.ff, i, None, is_training)                                              # Base.py:79-86
             lams.append(lam)
         rows = ops.AddLayerNormFn.apply(x, None, self.out_ln.gamma, self.out_ln.beta, ops.NO_DROP, gather_pos, pad)   # :82-83
         return rows, lams
 
     def forward(self, features: Dict[str, torch.Tensor], is_training: bool):
-        ids = features["seqs_i"]
-        gp = None if is_training else torch.full((ids.shape[0], 1), ids.shape[1] - 1, device=ids.device, dtype=torch.int64)
-        rows, lams = self.encoder(features, is_training, gp)
+        rows, lams = self.encoder(features, is_training, None if is_training else self._last_pos(features["seqs_i"]))
         self._last_lams = lams
         rows = rows.reshape(-1, self.num_units)
         tab = self.item_embs.lookup_table
@@ -173,79 +138,3 @@ class CTSMA(Sequential):
                 loss = loss + ops.TppFn.apply(lam, None, labels.contiguous(), features["seqs_t"].contiguous(),
                                               self.mark_lookup_table, self.num_heads, self.ct_reg)
         return loss
-
-    train_step = EasyDGL.train_step
-
-    @torch.no_grad()
-    def eval_topk(self, features, mask_seen=True, K=100):
-        logits = self.forward(features, False)
-        return ops.mask_topk(logits, 0, features["seqs_i"] if mask_seen else None, K)
-
-    @torch.no_grad()
-    def eval_rank(self, features, labels, mask_seen=True):
-        """int32 [B]: the label's place in the (logit desc, item id asc) order of the unseen catalogue (Base.py:150-201), counted on the
-        materialised logits — no top-K list, the logits are left as they are."""
-        logits = self.forward(features, False)
-        return ops.rank_from_logits(logits, 0, features["seqs_i"] if mask_seen else None, EasyDGL._last_labels(labels))
-
-    eval_step = EasyDGL.eval_step
-
-    # ---- interop with the reference's variable naming (tests / checkpoints converted from TF) ------------------------
-    def load_tf_variables(self, values: Dict[str, np.ndarray]) -> None:
-        """`values`: TF variable name (scope `main/` stripped) -> array, as oracle/ctsma_ref.init_params lists them."""
-        if self.pad[0]:
-            return self._load_padded(values)
-        def put(param, arr):
-            with torch.no_grad():
-                param.copy_(torch.as_tensor(np.asarray(arr), dtype=param.dtype).reshape(param.shape))
-        put(self.item_embs.lookup_table, values["CSTMA/item_embs/lookup_table"])
-        put(self.pcoding.pembs.lookup_table, values["CSTMA/spatial_embs/embedding/lookup_table"])
-        put(self.output_bias, values["CSTMA/output_bias"])
-        for i, blk in enumerate(self.layers):
-            pre = f"num_blocks_{i}/"
-            a = pre + "attention/modulating_attention/"
-            put(blk.att_ln.gamma, values[pre + "attention/LayerNorm/gamma"])
-            put(blk.att_ln.beta, values[pre + "attention/LayerNorm/beta"])
-            put(blk.attention.q_kernel, values[a + "dense/kernel"])
-            put(blk.attention.q_bias, values[a + "dense/bias"])
-            put(blk.attention.kvt_kernel, np.concatenate([values[a + f"dense_{j}/kernel"] for j in (1, 2, 3)], axis=1))
-            put(blk.attention.kvt_bias, np.concatenate([values[a + f"dense_{j}/bias"] for j in (1, 2, 3)]))
-            st = a + "sequential_temporal_combined/"
-            put(blk.attention.st_kernel, values[st + "dense/kernel"])
-            put(blk.attention.st_bias, values[st + "dense/bias"])
-            put(blk.attention.weight, values[st + "weight"])
-            put(blk.attention.scaling, values[st + "scaling"])
-            put(blk.ff_ln.gamma, values[pre + "feed-forward/LayerNorm/gamma"])
-            put(blk.ff_ln.beta, values[pre + "feed-forward/LayerNorm/beta"])
-            put(blk.ff.inner.kernel, values[pre + "feed-forward/Inner/kernel"])
-            put(blk.ff.inner.bias, values[pre + "feed-forward/Inner/bias"])
-            put(blk.ff.readout.kernel, values[pre + "feed-forward/Readout/kernel"])
-            put(blk.ff.readout.bias, values[pre + "feed-forward/Readout/bias"])
-        put(self.out_ln.gamma, values["outln/LayerNorm/gamma"])
-        put(self.out_ln.beta, values["outln/LayerNorm/beta"])
-        self.sync_shadow()
-
-    def tf_gradients(self) -> Dict[str, np.ndarray]:
-        """Gradients of the last backward under the TF variable names (K|V|T_ split back into dense_1..3)."""
-        if self.pad[0]:
-            return {k: v.float().cpu().numpy() for k, v in self._padded_values(True).items()}
-        g = lambda q: q.grad.detach().float().cpu().numpy()
-        out = {"CSTMA/item_embs/lookup_table": g(self.item_embs.lookup_table),
-               "CSTMA/spatial_embs/embedding/lookup_table": g(self.pcoding.pembs.lookup_table), "CSTMA/output_bias": g(self.output_bias)}
-        C_ = self.num_units
-        for i, blk in enumerate(self.layers):
-            pre = f"num_blocks_{i}/"
-            a = pre + "attention/modulating_attention/"
-            out[pre + "attention/LayerNorm/gamma"], out[pre + "attention/LayerNorm/beta"] = g(blk.att_ln.gamma), g(blk.att_ln.beta)
-            out[a + "dense/kernel"], out[a + "dense/bias"] = g(blk.attention.q_kernel), g(blk.attention.q_bias)
-            kk, kb = g(blk.attention.kvt_kernel), g(blk.attention.kvt_bias)
-            for j in (1, 2, 3):
-                out[a + f"dense_{j}/kernel"], out[a + f"dense_{j}/bias"] = kk[:, (j - 1) * C_:j * C_], kb[(j - 1) * C_:j * C_]
-            st = a + "sequential_temporal_combined/"
-            out[st + "dense/kernel"], out[st + "dense/bias"] = g(blk.attention.st_kernel), g(blk.attention.st_bias)
-            out[st + "weight"], out[st + "scaling"] = g(blk.attention.weight), g(blk.attention.scaling)
-            out[pre + "feed-forward/LayerNorm/gamma"], out[pre + "feed-forward/LayerNorm/beta"] = g(blk.ff_ln.gamma), g(blk.ff_ln.beta)
-            out[pre + "feed-forward/Inner/kernel"], out[pre + "feed-forward/Inner/bias"] = g(blk.ff.inner.kernel), g(blk.ff.inner.bias)
-            out[pre + "feed-forward/Readout/kernel"], out[pre + "feed-forward/Readout/bias"] = g(blk.ff.readout.kernel), g(blk.ff.readout.bias)
-        out["outln/LayerNorm/gamma"], out["outln/LayerNorm/beta"] = g(self.out_ln.gamma), g(self.out_ln.beta)
-        return out

@@ -21,26 +21,7 @@ from torch import nn
 from .. import ops
 from ..module import coding as C
 from ..module import temporal as T
-from ..module.coding import glorot_uniform_
-from .base import Sequential
-
-
-class _Dense(nn.Module):
-    """tf.layers.dense parameters: kernel [in,out] glorot_uniform, bias zeros."""
-
-    def __init__(self, n_in, n_out, gen):
-        super().__init__()
-        self.kernel = nn.Parameter(glorot_uniform_(torch.empty(n_in, n_out), gen))
-        self.bias = nn.Parameter(torch.zeros(n_out))
-
-
-class _LayerNorm(nn.Module):
-    """Base.layernorm parameters (Base.py:36-49): beta zeros, gamma ones over the last axis."""
-
-    def __init__(self, n):
-        super().__init__()
-        self.beta = nn.Parameter(torch.zeros(n))
-        self.gamma = nn.Parameter(torch.ones(n))
+from .base import Sequential, _Dense, _LayerNorm  # noqa: F401  (the parameter holders are imported from here elsewhere)
 
 
 class _Block(nn.Module):
@@ -55,6 +36,7 @@ class _Block(nn.Module):
 
 
 class EasyDGL(Sequential):
+    tf_numpy = False     # tf_values() / tf_gradients(): torch tensors on the parameters' device
 
     def __init__(self, num_items, FLAGS):
         super().__init__(num_items, FLAGS)
@@ -81,24 +63,15 @@ class EasyDGL(Sequential):
         self.deterministic = bool(getattr(FLAGS, "deterministic", False))
 
         gen = torch.Generator().manual_seed(self.seed)
-        # A head dim the attention kernels do not tile (they take 16 / 32 / 64 / 128; the reference's own defaults are
-        # --num_units 50 --num_heads 1, main.py:35-37): the model runs at the next supported head dim with ZERO-PADDED channels —
-        # every parameter is stored at the padded width, its padded rows / columns are zero and stay zero (their gradients are
-        # exactly zero: padded Q / K / V / T_ columns, W1 rows and dense rows are 0; the joint LayerNorm takes its moments over
-        # the real channels and returns no gradient into the padded ones; the one exception, the intensity MLP's output weights
-        # of the padded hidden units, is masked in mask_padded_grads), the score scale 1 / sqrt(dh) and coding.py's sqrt(C) are
-        # those of the TRUE width.  tf_values() / load_tf_variables() / tf_gradients() speak the reference's shapes.
-        self.width_true = self.num_units
-        dh_true = self.num_units // self.num_heads if self.num_heads > 0 and self.num_units % self.num_heads == 0 else 0
-        self.pad = (0, 0)
-        if dh_true and dh_true not in T.SUPPORTED_HEAD_DIMS:
-            dh_pad = next((d for d in T.SUPPORTED_HEAD_DIMS if d >= dh_true), None)
-            if dh_pad is None or dh_true % 2:
-                raise ValueError(f"EasyDGL: head dim num_units/num_heads = {dh_true}: even head dims up to {T.SUPPORTED_HEAD_DIMS[-1]} "
-                                 "run (zero-padded to the next of 16 / 32 / 64 / 128)")
-            self.pad = (dh_pad, dh_true)
-            self.num_units = self.num_heads * dh_pad
-        self.qk_scale = float(dh_true) ** -0.5 if self.pad[0] else 0.0
+        # A head dim the attention kernels do not tile runs zero-padded at the next of 16 / 32 / 64 / 128 (model/base.py: channel
+        # padding); here only even head dims (the time code pairs channels), and nothing above the largest kernel.  The one
+        # gradient that is not zero on a padded entry by itself is masked in mask_padded_grads.
+        H = self.num_heads
+        dh = self.num_units // H if H > 0 and self.num_units % H == 0 else 0
+        if dh and dh not in T.SUPPORTED_HEAD_DIMS and (dh % 2 or dh > T.SUPPORTED_HEAD_DIMS[-1]):
+            raise ValueError(f"EasyDGL: head dim num_units/num_heads = {dh}: even head dims up to {T.SUPPORTED_HEAD_DIMS[-1]} "
+                             "run (zero-padded to the next of 16 / 32 / 64 / 128)")
+        self._setup_channel_pad("EasyDGL")
         C_ = self.num_units
         # variable scope "CSTMA" (EasyDGL.py:49-57)
         self.item_embs = C.Embedding(self.num_items, C_, self.l2_reg, zero_pad=True, scale=True, gen=gen)
@@ -117,90 +90,55 @@ class EasyDGL(Sequential):
         #  EasyDGL.py:138)
         self.transform = _Dense(3 * C_ if FLAGS.num_blocks == 0 else C_, C_, gen)       # cls/predictions/transform/dense
         self.transform_ln = _LayerNorm(C_)         # cls/predictions/transform/LayerNorm
-        self._metrics = None
-        if self.pad[0]:
-            for blk in self.layers:
-                blk.attention.qk_scale = self.qk_scale
-            self._init_padded(gen)
+        self._finish_pad(gen)
 
-    # ---- channel padding (self.pad = (dh_pad, dh_true)) ---------------------------------------------------------------
-    def _pad_maps(self):
-        """Index maps true -> padded for every axis kind of the parameters."""
-        dhp, dht = self.pad
-        H, E, Ct, Cp = self.num_heads, self.num_events, self.width_true, self.num_units
-        c = torch.arange(Ct)
-        cmap = (c // dht) * dhp + (c % dht)
-        j = torch.arange(dht * E)
-        return dict(c=cmap, c3=torch.cat([cmap + k * Cp for k in range(3)]), c4=torch.cat([cmap + k * Cp for k in range(4)]),
-                    h2=torch.arange(2 * Ct), j=(j // dht) * dhp + (j % dht),
-                    st_rows=torch.cat([torch.arange(dht), torch.tensor([dhp])]), u=torch.arange(dht))
-
+    # ---- the variable table (model/base.py derives load / values / gradients / the padded storage from it) ----------------------
     def _pad_specs(self):
-        """TF variable name -> (parameter, axis maps (None = axis kept), initialiser of the TRUE-shape variable)."""
-        mp = self._pad_maps()
-        sp = {
-            "CSTMA/item_embs/lookup_table": (self.item_embs.lookup_table, (None, mp["c"]), "glorot"),
-            "CSTMA/mark_embs/lookup_table": (self.mark_embs.lookup_table, (None, mp["c"]), "glorot"),
-            "CSTMA/spatial_embs/embedding/lookup_table": (self.pcoding.pembs.lookup_table, (None, mp["c"]), "glorot"),
-            "CSTMA/output_bias": (self.output_bias, (None,), "zeros"),
-            "cls/predictions/transform/dense/kernel": (self.transform.kernel, (mp["c"], mp["c"]), "glorot"),
-            "cls/predictions/transform/dense/bias": (self.transform.bias, (mp["c"],), "zeros"),
-            "cls/predictions/transform/LayerNorm/beta": (self.transform_ln.beta, (mp["c"],), "zeros"),
-            "cls/predictions/transform/LayerNorm/gamma": (self.transform_ln.gamma, (mp["c"],), "ones"),
-        }
+        """(TF name, parameter, axis maps reference -> stored (None = axis kept), initialiser of the TRUE-shape variable)."""
+        c, c3, c4 = self._cmap(), self._cmap(3), self._cmap(4)
+        h2 = torch.arange(2 * self.width_true)
+        st_rows, j, u = self._mlp_maps()
+        tr = self.transform
+        sp = [("CSTMA/item_embs/lookup_table", self.item_embs.lookup_table, (None, c), "glorot"),
+              ("CSTMA/mark_embs/lookup_table", self.mark_embs.lookup_table, (None, c), "glorot"),
+              ("CSTMA/spatial_embs/embedding/lookup_table", self.pcoding.pembs.lookup_table, (None, c), "glorot"),
+              ("CSTMA/output_bias", self.output_bias, (None,), "zeros"),
+              ("cls/predictions/transform/dense/kernel", tr.kernel, (c if self.layers else c3, c), "glorot"),   # (no block: 3C rows)
+              ("cls/predictions/transform/dense/bias", tr.bias, (c,), "zeros"),
+              ("cls/predictions/transform/LayerNorm/beta", self.transform_ln.beta, (c,), "zeros"),
+              ("cls/predictions/transform/LayerNorm/gamma", self.transform_ln.gamma, (c,), "ones")]
         for i, blk in enumerate(self.layers):
             pre = f"layer_{i}/"
-            st = pre + "attention/self/TMAU/sequential_temporal_combined/"
+            tm = pre + "attention/self/TMAU/"
+            st = tm + "sequential_temporal_combined/"
             a = blk.attention
-            sp[pre + "attention/self/TMAU/dense/kernel"] = (a.dense_kernel, (mp["c3"] if i == 0 else mp["c"], mp["c4"]), "normal")
-            sp[pre + "attention/self/TMAU/dense/bias"] = (a.dense_bias, (mp["c4"],), "zeros")
-            sp[st + "dense/kernel"] = (a.st_kernel, (mp["st_rows"], mp["j"]), "glorot")
-            sp[st + "dense/bias"] = (a.st_bias, (mp["j"],), "zeros")
-            sp[st + "weight"] = (a.weight, (None, mp["u"]), "glorot")
-            sp[st + "scaling"] = (a.scaling, (None,), "zeros")
-            sp[pre + "attention/output/dense/kernel"] = (blk.att_out.kernel, (mp["c"], mp["c"]), "glorot")
-            sp[pre + "attention/output/dense/bias"] = (blk.att_out.bias, (mp["c"],), "zeros")
-            sp[pre + "attention/output/LayerNorm/beta"] = (blk.att_ln.beta, (mp["c"],), "zeros")
-            sp[pre + "attention/output/LayerNorm/gamma"] = (blk.att_ln.gamma, (mp["c"],), "ones")
-            sp[pre + "intermediate/dense/kernel"] = (blk.inter.kernel, (mp["c"], mp["h2"]), "glorot")
-            sp[pre + "intermediate/dense/bias"] = (blk.inter.bias, (mp["h2"],), "zeros")
-            sp[pre + "output/dense/kernel"] = (blk.out.kernel, (mp["h2"], mp["c"]), "glorot")
-            sp[pre + "output/dense/bias"] = (blk.out.bias, (mp["c"],), "zeros")
-            sp[pre + "output/LayerNorm/beta"] = (blk.out_ln.beta, (mp["c"],), "zeros")
-            sp[pre + "output/LayerNorm/gamma"] = (blk.out_ln.gamma, (mp["c"],), "ones")
+            sp += [(tm + "dense/kernel", a.dense_kernel, (c3 if i == 0 else c, c4), "normal"),
+                   (tm + "dense/bias", a.dense_bias, (c4,), "zeros"),
+                   (st + "dense/kernel", a.st_kernel, (st_rows, j), "glorot"),
+                   (st + "dense/bias", a.st_bias, (j,), "zeros"),
+                   (st + "weight", a.weight, (None, u), "glorot"),
+                   (st + "scaling", a.scaling, (None,), "zeros"),
+                   (pre + "attention/output/dense/kernel", blk.att_out.kernel, (c, c), "glorot"),
+                   (pre + "attention/output/dense/bias", blk.att_out.bias, (c,), "zeros"),
+                   (pre + "attention/output/LayerNorm/beta", blk.att_ln.beta, (c,), "zeros"),
+                   (pre + "attention/output/LayerNorm/gamma", blk.att_ln.gamma, (c,), "ones"),
+                   (pre + "intermediate/dense/kernel", blk.inter.kernel, (c, h2), "glorot"),
+                   (pre + "intermediate/dense/bias", blk.inter.bias, (h2,), "zeros"),
+                   (pre + "output/dense/kernel", blk.out.kernel, (h2, c), "glorot"),
+                   (pre + "output/dense/bias", blk.out.bias, (c,), "zeros"),
+                   (pre + "output/LayerNorm/beta", blk.out_ln.beta, (c,), "zeros"),
+                   (pre + "output/LayerNorm/gamma", blk.out_ln.gamma, (c,), "ones")]
         return sp
 
-    @staticmethod
-    def _true_shape(p, maps):
-        return tuple(p.shape[a] if m is None else len(m) for a, m in enumerate(maps))
-
-    @staticmethod
-    def _scatter(dst, maps, src):
-        """dst (padded, any device) <- zeros, with src (true shape) at the mapped indices."""
-        idx = [torch.arange(dst.shape[a]) if m is None else m for a, m in enumerate(maps)]
-        dst.zero_()
-        dst[torch.meshgrid(*[i.to(dst.device) for i in idx], indexing="ij")] = src.to(dst.device, dst.dtype)
-
-    @staticmethod
-    def _gather(src, maps):
-        idx = [torch.arange(src.shape[a]) if m is None else m for a, m in enumerate(maps)]
-        return src[torch.meshgrid(*[i.to(src.device) for i in idx], indexing="ij")]
+    def tf_variable_map(self) -> Dict[str, nn.Parameter]:
+        """Reference variable name (scope main/...) -> parameter (each parameter is one variable here)."""
+        return {name: p for name, p, _, _ in self._pad_specs()}
 
     @torch.no_grad()
     def _init_padded(self, gen):
-        """The reference's initialisers on the TRUE shapes (glorot limits of the true fans; temporal.py:393 N(0, 0.02)), scattered
-        into the zero-padded storage; the time-code scales are those of the true width (coding.py:132-136)."""
-        for name, (p, maps, kind) in self._pad_specs().items():
-            shp = self._true_shape(p, maps)
-            if kind == "glorot":
-                v = glorot_uniform_(torch.empty(shp), gen)
-            elif kind == "normal":
-                v = torch.randn(shp, generator=gen) * 0.02
-            elif kind == "ones":
-                v = torch.ones(shp)
-            else:
-                v = torch.zeros(shp)
-            self._scatter(p.data, maps, v)
+        """The base initialisers (temporal.py:393 N(0, 0.02) among them), then the time-code scales of the TRUE width
+        (coding.py:132-136)."""
+        super()._init_padded(gen)
         dhp, dht = self.pad
         Ct, Cp = self.width_true, self.num_units
         true_scale = np.power(10000, np.arange(0, Ct, 2) * 1.0 / Ct).astype(np.float32)      # pair j of the TRUE channels
@@ -220,48 +158,8 @@ class EasyDGL(Sequential):
             if g is not None:
                 g[:, self.pad[1]:].zero_()
 
-    @torch.no_grad()
-    def tf_values(self) -> Dict[str, torch.Tensor]:
-        """Reference variable name -> value in the REFERENCE's shape (a copy; channel-padded models strip the padding)."""
-        if not self.pad[0]:
-            return {k: p.detach().clone() for k, p in self.tf_variable_map().items()}
-        return {k: self._gather(p.detach(), maps).clone() for k, (p, maps, _) in self._pad_specs().items()}
-
-    @torch.no_grad()
-    def tf_gradients(self) -> Dict[str, torch.Tensor]:
-        """Reference variable name -> gradient in the reference's shape (a copy)."""
-        if not self.pad[0]:
-            return {k: p.grad.detach().clone() for k, p in self.tf_variable_map().items()}
-        return {k: self._gather(p.grad.detach(), maps).clone() for k, (p, maps, _) in self._pad_specs().items()}
-
-    @torch.no_grad()
-    def padded_leak(self) -> float:
-        """Largest |value| on a padded entry of any parameter (0.0 for a healthy model; tests)."""
-        worst = 0.0
-        for k, (p, maps, _) in self._pad_specs().items():
-            q = p.detach().clone()
-            idx = [torch.arange(q.shape[a]) if m is None else m for a, m in enumerate(maps)]
-            q[torch.meshgrid(*[i.to(q.device) for i in idx], indexing="ij")] = 0
-            worst = max(worst, float(q.abs().max()))
-        return worst
-
     def l2_param_names(self):
         return ["item_embs.lookup_table", "mark_embs.lookup_table", "pcoding.pembs.lookup_table"]
-
-    def finalize(self, device):
-        super().finalize(device)
-        for blk in self.layers:
-            blk.attention.compute = self.compute
-        return self
-
-    # ---- helpers ---------------------------------------------------------------------------------------
-    def _drop(self, rate, stream_id, is_training) -> ops.Drop:
-        if not is_training or rate <= 0.0:
-            return ops.NO_DROP
-        return ops.Drop(rate, self._rng_state, stream_id)
-
-    def _linear(self, x, d: _Dense, gelu=False):
-        return ops.LinearFn.apply(x, d.kernel, d.bias, self.compute(d.kernel), gelu)
 
     def encode(self, features, is_training):
         """EasyDGL.py:70-95 -> (X0 [B,T,3C], spans [B,T], marks [B,T,E] uint8)."""
@@ -293,11 +191,11 @@ class EasyDGL(Sequential):
             att = self._linear(att, blk.att_out)                                                   # :113
             att = ops.AddLayerNormFn.apply(att, layer_in[:, :, :C_], blk.att_ln.gamma, blk.att_ln.beta,
                                            self._drop(self.hidden_dropout_rate, 11 + 4 * i, is_training), None, self.pad)  # :114-116
-            inter = self._linear(att, blk.inter, gelu=True)                                        # :120-121
+            inter = self._linear(att, blk.inter, True)                                        # :120-121
             out = self._linear(inter, blk.out)                                                     # :125
             x = ops.AddLayerNormFn.apply(out, att, blk.out_ln.gamma, blk.out_ln.beta,
                                          self._drop(self.hidden_dropout_rate, 12 + 4 * i, is_training), None, self.pad)   # :126-128
-        so = self._linear(x, self.transform, gelu=True)                                           # :138
+        so = self._linear(x, self.transform, True)                                           # :138
         rows = ops.AddLayerNormFn.apply(so, None, self.transform_ln.gamma, self.transform_ln.beta, ops.NO_DROP,
                                         gather_pos, self.pad)                                      # :139,142-146
         return rows, lams
@@ -345,10 +243,7 @@ class EasyDGL(Sequential):
         return y, rows
 
     def _gather_pos(self, features, is_training):
-        ids = features["seqs_i"]
-        if is_training:
-            return features["masked_positions"].contiguous()
-        return torch.full((ids.shape[0], 1), ids.shape[1] - 1, device=ids.device, dtype=torch.int64)
+        return features["masked_positions"].contiguous() if is_training else self._last_pos(features["seqs_i"])
 
     # ---- EasyDGL.__call__ ------------------------------------------------------------------------------
     def forward(self, features: Dict[str, torch.Tensor], is_training: bool):
@@ -374,18 +269,6 @@ class EasyDGL(Sequential):
                                               features["seqs_t"], self.mark_lookup_table, self.num_heads,
                                               self.ct_reg / self.num_heads)
         return loss
-
-    def train_step(self, features, labels):
-        """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar)."""
-        self.settle_state()
-        ops.rng_advance(self._rng_state)
-        self.detach_grads()
-        loss = self.train_loss(features, labels)
-        loss.backward()
-        self.collect_grads()
-        self.mask_padded_grads()
-        self.optimizer_step()
-        return loss.detach()
 
     # ---- Sequential.eval (Base.py:150-207) ----------------------------------------------------------------
     @torch.no_grad()
@@ -418,10 +301,6 @@ class EasyDGL(Sequential):
             return ops.topk_merge(torch.stack(vals), torch.stack(idxs))
         return parallel.sharded_topk(local_topk, ops.topk_merge, self.num_items, K, group)
 
-    @staticmethod
-    def _last_labels(labels):
-        return (labels[:, -1] if labels.dim() == 2 else labels).contiguous()
-
     @torch.no_grad()
     def eval_rank(self, features, labels, mask_seen=True):
         """int32 [B]: the place of each sequence's true next item in the (logit desc, item id asc) order of the unseen catalogue
@@ -448,86 +327,3 @@ class EasyDGL(Sequential):
         if world is not None:   # in-process emulation of `world` shards
             return sum(count_local(*parallel.shard_bounds(self.num_items, world, r)) for r in range(world))
         return parallel.sharded_rank(count_local, self.num_items, group)
-
-    def reset_metrics(self, ks=None):
-        """`ks`: the cut-offs of the by-rank metrics (eval_step(by_rank=True)); default (10, 50, 100), at most 8."""
-        dev = self._arena.device
-        self._metrics = torch.zeros(6, device=dev, dtype=torch.float32)
-        self._metric_count = 0
-        self._rank_ks = tuple(int(k) for k in (ks or (10, 50, 100)))
-        if not 1 <= len(self._rank_ks) <= 8:
-            raise ValueError(f"reset_metrics: 1 to 8 cut-offs (got {self._rank_ks})")
-        self._rank_ks_dev = torch.tensor(self._rank_ks, device=dev, dtype=torch.int32)
-        self._rank_sums = torch.zeros(2 * len(self._rank_ks) + 1, device=dev, dtype=torch.float32)
-        self._rank_count = 0
-
-    @torch.no_grad()
-    def eval_step(self, features, labels, mask_seen=True, by_rank=False):
-        if self._metrics is None:
-            self.reset_metrics()
-        if by_rank:
-            if self._metric_count != self._rank_count:
-                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
-            ops.rank_metrics_from_rank(self.eval_rank(features, labels, mask_seen), self._rank_ks_dev, self._rank_sums)
-            self._rank_count += labels.shape[0]
-        else:
-            if self._rank_count:
-                raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
-            _, idx = self.eval_topk(features, mask_seen)
-            ops.rank_metrics(idx, labels[:, -1].contiguous(), self._metrics)
-        self._metric_count += labels.shape[0]
-
-    def metrics(self) -> Dict[str, float]:
-        if getattr(self, "_rank_count", 0):     # by-rank steps: H / N at the chosen cut-offs and the mean reciprocal rank
-            vals = (self._rank_sums / self._rank_count).tolist()
-            names = [f"H{k}" for k in self._rank_ks] + [f"N{k}" for k in self._rank_ks] + ["MRR"]
-            return dict(zip(names, vals))
-        vals = (self._metrics / max(1, self._metric_count)).tolist()
-        return dict(zip(("H10", "H50", "H100", "N10", "N50", "N100"), vals))
-
-    # ---- interop with the oracle's parameter naming (tests) -----------------------------------------------
-    def tf_variable_map(self) -> Dict[str, nn.Parameter]:
-        """Reference variable name (scope main/...) -> parameter."""
-        m = {
-            "CSTMA/item_embs/lookup_table": self.item_embs.lookup_table,
-            "CSTMA/mark_embs/lookup_table": self.mark_embs.lookup_table,
-            "CSTMA/spatial_embs/embedding/lookup_table": self.pcoding.pembs.lookup_table,
-            "CSTMA/output_bias": self.output_bias,
-            "cls/predictions/transform/dense/kernel": self.transform.kernel,
-            "cls/predictions/transform/dense/bias": self.transform.bias,
-            "cls/predictions/transform/LayerNorm/beta": self.transform_ln.beta,
-            "cls/predictions/transform/LayerNorm/gamma": self.transform_ln.gamma,
-        }
-        for i, blk in enumerate(self.layers):
-            pre = f"layer_{i}/"
-            st = pre + "attention/self/TMAU/sequential_temporal_combined/"
-            m[pre + "attention/self/TMAU/dense/kernel"] = blk.attention.dense_kernel
-            m[pre + "attention/self/TMAU/dense/bias"] = blk.attention.dense_bias
-            m[st + "dense/kernel"] = blk.attention.st_kernel
-            m[st + "dense/bias"] = blk.attention.st_bias
-            m[st + "weight"] = blk.attention.weight
-            m[st + "scaling"] = blk.attention.scaling
-            m[pre + "attention/output/dense/kernel"] = blk.att_out.kernel
-            m[pre + "attention/output/dense/bias"] = blk.att_out.bias
-            m[pre + "attention/output/LayerNorm/beta"] = blk.att_ln.beta
-            m[pre + "attention/output/LayerNorm/gamma"] = blk.att_ln.gamma
-            m[pre + "intermediate/dense/kernel"] = blk.inter.kernel
-            m[pre + "intermediate/dense/bias"] = blk.inter.bias
-            m[pre + "output/dense/kernel"] = blk.out.kernel
-            m[pre + "output/dense/bias"] = blk.out.bias
-            m[pre + "output/LayerNorm/beta"] = blk.out_ln.beta
-            m[pre + "output/LayerNorm/gamma"] = blk.out_ln.gamma
-        return m
-
-    @torch.no_grad()
-    def load_tf_variables(self, values: Dict[str, np.ndarray]) -> None:
-        if self.pad[0]:
-            for name, (p, maps, _) in self._pad_specs().items():
-                v = torch.as_tensor(np.asarray(values[name]), dtype=torch.float32)
-                if tuple(v.shape) != self._true_shape(p, maps):
-                    raise ValueError(f"{name}: expected shape {self._true_shape(p, maps)}, got {tuple(v.shape)}")
-                self._scatter(p.data, maps, v)
-        else:
-            for name, p in self.tf_variable_map().items():
-                p.copy_(torch.as_tensor(np.asarray(values[name]), dtype=torch.float32).to(p.device))
-        self.sync_shadow()

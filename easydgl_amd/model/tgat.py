@@ -15,16 +15,13 @@ from __future__ import annotations
 
 from typing import Dict
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import ops
 from ..module import coding as C
 from ..module import temporal as T
-from .base import Sequential
-from .ctsma import _FeedForward
-from .easydgl import EasyDGL, _Dense, _LayerNorm
+from .base import Sequential, _FeedForward, _LayerNorm
 
 
 class _Block(nn.Module):
@@ -62,17 +59,10 @@ class TGAT(Sequential):
             self.layers.append(_Block(C_, self.num_heads, self.attention_probs_dropout_rate, self.l2_reg, self.pcoding_K,
                                       self.tcoding_K, gen))
         self.out_ln = _LayerNorm(C_)
-        self._metrics = None
         self._finish_pad(gen)
 
-    def _finish_pad(self, gen):
-        if self.pad[0]:
-            for blk in self.layers:
-                blk.attention.qk_scale = self.qk_scale
-            self._init_padded(gen)
-
     def _pad_specs(self):
-        """(TF name, parameter, axis maps, initialiser) of every variable in _tf_map(), for the channel-padded storage."""
+        """The variable table (model/base.py): (TF name, parameter, axis maps reference -> stored, initialiser), from _tf_map()."""
         c = self._cmap()
         specs = []
         for name, (param, sl) in self._tf_map().items():
@@ -97,7 +87,6 @@ class TGAT(Sequential):
         super().finalize(device)
         self._violations = torch.zeros(1, device=device, dtype=torch.int32)
         for blk in self.layers:
-            blk.attention.compute = self.compute
             blk.attention.time_scale = self.time_scale
             blk.attention.violations = self._violations
         return self
@@ -108,13 +97,6 @@ class TGAT(Sequential):
         if n:
             self._violations.zero_()
             raise ValueError(f"{n} positions with decreasing timestamps: sort each sequence by time (see model/tgat.py)")
-
-    _drop = EasyDGL._drop
-    reset_metrics = EasyDGL.reset_metrics
-    metrics = EasyDGL.metrics
-
-    def _linear(self, x, d: _Dense, act=False):
-        return ops.LinearFn.apply(x, d.kernel, d.bias, self.compute(d.kernel), act)
 
     def encoder(self, features, is_training, gather_pos):
         """TGAT.py:44-73: rows of the final LayerNorm at gather_pos (None: all positions)."""
@@ -130,16 +112,11 @@ class TGAT(Sequential):
             att = blk.attention(qn, x, (ids, ts), is_training, True,
                                 self._drop(self.attention_probs_dropout_rate, 10 + 4 * i, is_training))
             y = ops.AddLayerNormFn.apply(att, None, blk.ff_ln.gamma, blk.ff_ln.beta, ops.NO_DROP, None, pad)      # :69
-            inner = self._linear(y, blk.ff.inner, "relu")                                                         # Base.py:79
-            if is_training and hd > 0.0:
-                inner = ops.dropout(inner, self._drop(hd, 11 + 4 * i, True))                                      # Base.py:80
-            out = self._linear(inner, blk.ff.readout)                                                             # Base.py:82
-            x = ops.ff_tail(out, y, ids, self._drop(hd, 12 + 4 * i, is_training))                                 # Base.py:83-86, TGAT.py:70
+            x = self._feed_forward(y, blk.ff, i, ids, is_training)                                                # Base.py:79-86, TGAT.py:70
         return ops.AddLayerNormFn.apply(x, None, self.out_ln.gamma, self.out_ln.beta, ops.NO_DROP, gather_pos, pad)   # :72-73
 
     def forward(self, features: Dict[str, torch.Tensor], is_training: bool):
-        ids = features["seqs_i"]
-        gp = None if is_training else torch.full((ids.shape[0], 1), ids.shape[1] - 1, device=ids.device, dtype=torch.int64)
+        gp = None if is_training else self._last_pos(features["seqs_i"])
         rows = self.encoder(features, is_training, gp).reshape(-1, self.num_units)
         tab = self.item_embs.lookup_table
         return ops.ScoreLogitsFn.apply(rows, tab, self.output_bias, self.compute(tab))                            # :74-83
@@ -155,32 +132,20 @@ class TGAT(Sequential):
                 loss = loss + ops.L2Fn.apply(self.get_parameter(n), self.l2_reg)
         return loss
 
-    train_step = EasyDGL.train_step
-
-    @torch.no_grad()
-    def eval_topk(self, features, mask_seen=True, K=100):
-        logits = self.forward(features, False)
-        return ops.mask_topk(logits, 0, features["seqs_i"] if mask_seen else None, K)
-
-    @torch.no_grad()
-    def eval_rank(self, features, labels, mask_seen=True):
-        """int32 [B]: the label's place in the (logit desc, item id asc) order of the unseen catalogue (Base.py:150-201), counted on the
-        materialised logits — no top-K list, the logits are left as they are."""
-        logits = self.forward(features, False)
-        return ops.rank_from_logits(logits, 0, features["seqs_i"] if mask_seen else None, EasyDGL._last_labels(labels))
-
-    eval_step = EasyDGL.eval_step
-
     # ---- interop with the reference's variable naming (tests / checkpoints converted from TF) ------------------------
     def _tf_map(self):
         """TF variable name -> (parameter, column slice or None)."""
-        C_ = self.num_units
         m = {"TGAT/item_embs/lookup_table": (self.item_embs.lookup_table, None),
              "TGAT/pcoding_K/embedding/lookup_table": (self.pcoding_K.pembs.lookup_table, None),
              "TGAT/tcoding_K/basis_freq": (self.tcoding_K.basis_freq, None),
              "TGAT/tcoding_K/phase": (self.tcoding_K.phase, None),
              "TGAT/output_bias": (self.output_bias, None),
              "out_ln/LayerNorm/gamma": (self.out_ln.gamma, None), "out_ln/LayerNorm/beta": (self.out_ln.beta, None)}
+        return self._block_tf_map(m)
+
+    def _block_tf_map(self, m):
+        """Adds the per-block variables (the same names and wiring in TGAT and TiSASRec) to `m`."""
+        C_ = self.num_units
         for i, blk in enumerate(self.layers):
             pre = f"num_blocks_{i}/"
             a = pre + "attention/attention/timeinterval/"
@@ -195,27 +160,3 @@ class TGAT(Sequential):
             m[pre + "feedforward/Inner/kernel"], m[pre + "feedforward/Inner/bias"] = (blk.ff.inner.kernel, None), (blk.ff.inner.bias, None)
             m[pre + "feedforward/Readout/kernel"], m[pre + "feedforward/Readout/bias"] = (blk.ff.readout.kernel, None), (blk.ff.readout.bias, None)
         return m
-
-    def load_tf_variables(self, values: Dict[str, np.ndarray]) -> None:
-        if self.pad[0]:
-            return self._load_padded(values)
-        with torch.no_grad():
-            for name, (param, sl) in self._tf_map().items():
-                src = torch.as_tensor(np.asarray(values[name]), dtype=param.dtype)
-                (param if sl is None else param[..., sl]).copy_(src)
-        self.sync_shadow()
-
-    def tf_values(self) -> Dict[str, np.ndarray]:
-        """Reference variable name -> value in the reference's shape (channel-padded models strip the padding)."""
-        if self.pad[0]:
-            return {k: v.float().cpu().numpy() for k, v in self._padded_values(False).items()}
-        return {name: (p if sl is None else p[..., sl]).detach().float().cpu().numpy() for name, (p, sl) in self._tf_map().items()}
-
-    def tf_gradients(self) -> Dict[str, np.ndarray]:
-        if self.pad[0]:
-            return {k: v.float().cpu().numpy() for k, v in self._padded_values(True).items()}
-        out = {}
-        for name, (param, sl) in self._tf_map().items():
-            g = param.grad.detach().float().cpu().numpy()
-            out[name] = g if sl is None else g[..., sl]
-        return out

@@ -11,9 +11,7 @@ from torch import nn
 
 from ..module import coding as C
 from ..module import temporal as T
-from .base import Sequential
-from .ctsma import _FeedForward
-from .easydgl import _LayerNorm
+from .base import Sequential, _FeedForward, _LayerNorm
 from .tgat import TGAT
 
 
@@ -53,7 +51,6 @@ class TiSASRec(TGAT):
         for _ in range(FLAGS.num_blocks):
             self.layers.append(_Block(C_, self.num_heads, self.attention_probs_dropout_rate, self.l2_reg, codings, gen))
         self.out_ln = _LayerNorm(C_)
-        self._metrics = None
         self._finish_pad(gen)
 
     def l2_param_names(self):
@@ -63,7 +60,6 @@ class TiSASRec(TGAT):
     def finalize(self, device):
         Sequential.finalize(self, device)
         for blk in self.layers:
-            blk.attention.compute = self.compute
             blk.attention.time_scale = self.time_scale
             blk.attention.timelen = self.timelen
         return self
@@ -72,23 +68,9 @@ class TiSASRec(TGAT):
         """The interval buckets clip negative differences exactly as the reference does: nothing to check."""
 
     def _tf_map(self):
-        C_ = self.num_units
         m = {"TiSASRec/item_embs/lookup_table": (self.item_embs.lookup_table, None),
              "TiSASRec/output_bias": (self.output_bias, None),
              "out_ln/LayerNorm/gamma": (self.out_ln.gamma, None), "out_ln/LayerNorm/beta": (self.out_ln.beta, None)}
         for n in ("pcoding_K", "pcoding_V", "tcoding_K", "tcoding_V"):
             m[f"TiSASRec/{n}/embedding/lookup_table"] = (getattr(self, n).pembs.lookup_table, None)
-        for i, blk in enumerate(self.layers):
-            pre = f"num_blocks_{i}/"
-            a = pre + "attention/attention/timeinterval/"
-            m[pre + "attention/LayerNorm/gamma"] = (blk.att_ln.gamma, None)
-            m[pre + "attention/LayerNorm/beta"] = (blk.att_ln.beta, None)
-            m[a + "dense/kernel"], m[a + "dense/bias"] = (blk.attention.q_kernel, None), (blk.attention.q_bias, None)
-            for j in (1, 2):
-                sl = slice((j - 1) * C_, j * C_)
-                m[a + f"dense_{j}/kernel"], m[a + f"dense_{j}/bias"] = (blk.attention.kv_kernel, sl), (blk.attention.kv_bias, sl)
-            m[pre + "feedforward/LayerNorm/gamma"] = (blk.ff_ln.gamma, None)
-            m[pre + "feedforward/LayerNorm/beta"] = (blk.ff_ln.beta, None)
-            m[pre + "feedforward/Inner/kernel"], m[pre + "feedforward/Inner/bias"] = (blk.ff.inner.kernel, None), (blk.ff.inner.bias, None)
-            m[pre + "feedforward/Readout/kernel"], m[pre + "feedforward/Readout/bias"] = (blk.ff.readout.kernel, None), (blk.ff.readout.bias, None)
-        return m
+        return self._block_tf_map(m)

@@ -224,7 +224,7 @@ def test_fused_block_tail_matches_the_unfused_kernels(case, drop):
             t = b[k]
             cols = padc if t.shape[-1] == 64 else torch.zeros(t.shape[-1], dtype=torch.bool, device="cuda")
             assert float(t[..., cols].abs().max() if cols.any() else 0.0) == 0.0, k
-        for name, (prm, maps, _) in m._pad_specs().items():      # gradients: nothing on a padded entry (the intensity MLP's output
+        for name, prm, maps, _ in m._pad_specs():                # gradients: nothing on a padded entry (the intensity MLP's output
             if name.endswith("sequential_temporal_combined/weight"):   # weights of padded hidden units are the one masked exception)
                 continue
             g = prm.grad.detach().clone()
