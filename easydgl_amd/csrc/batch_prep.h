@@ -1,6 +1,6 @@
 // Batch preparation of a training step — the row compaction map of the scoring and the slot data of the TPP regulariser: both read
 // labels / masked positions / timestamps only.  As device functions, so that they run either as kernels of their own
-// (edgl_compact_scan_labels: k_score.hip; edgl_tpp_prep: k_misc.hip) or as extra workgroups of the encoder's launch
+// (edgl_compact_scan_labels: k_ce.hip; edgl_tpp_prep: k_misc.hip) or as extra workgroups of the encoder's launch
 // (edgl_encode_fwd_prep: k_encode.hip) — on the main stream, in front of everything that reads them, without a side stream whose
 // join the first attention kernel would wait for.
 #pragma once

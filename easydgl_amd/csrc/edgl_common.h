@@ -56,6 +56,14 @@ int edgl_gemm2_try_strip(const void* A, const void* B, void* C, int M, int N, in
 long edgl_gemm2_tn_workspace(int R, int Kf, int N);
 int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int N, int ldx, int ldy, int ldc, float* dbias,
                       int accumulate, float* workspace, hipStream_t st);
+// queue / flush of the grouped weight-gradient launch (k_gemm2.hip), behind edgl_gemm_dw_defer
+int edgl_gemm2_tn_defer(int on, hipStream_t st);
+// ordered sums over a sorted plan (k_segsum.hip): the item scatter of edgl_encode_bwd_add_det and the one-hot term of
+// edgl_score_flash_label_term_det
+int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* dx0, const void* add1, const void* add2, float sq, float rate,
+                      const uint64_t* rng, uint32_t stream_id, float* d_item, void* plan, int dtype, hipStream_t st);
+int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
+                      const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype, hipStream_t st);
 
 // ----------------------------------------------------------------------------------------------
 // element types: activations / GEMM operands are float (exact-f32 MFMA path) or bf16

@@ -598,8 +598,6 @@ extern "C" int edgl_encode_bwd_add_ct(const int64_t* ids, const uint8_t* marks, 
 }
 // edgl_encode_bwd_add_ct with the item scatter as an ordered sum over a sorted plan (k_segsum.hip) instead of f32 atomics: the
 // position / mark stage and its reductions are the same launches, d_item is bitwise reproducible (coding.py:60-64).
-int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* dx0, const void* add1, const void* add2, float sq, float rate,
-                      const uint64_t* rng, uint32_t stream_id, float* d_item, void* plan, int dtype, hipStream_t st);
 extern "C" int edgl_encode_bwd_add_det(const int64_t* ids, const uint8_t* marks, const void* dx0, const void* add1, const void* add2, int B,
                                        int T, int C, int E, int I, float drop_rate, const uint64_t* rng_state, uint32_t stream_id,
                                        float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, void* plan, int dtype,

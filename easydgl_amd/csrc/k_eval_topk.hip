@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void eval_thr_kernel(const float* gmax, int R,
 // One workgroup per row.  n = the row's candidate count:
 //   0 <= n <= cap   the K-th largest of the 256 thread maxima (a thread holds <= 4 candidates) bounds the K-th largest candidate from
 //                   below; the candidates at or above it are compacted and each one's rank among them in (value desc, index asc) is
-//                   its place in the output (as topk_merge_kernel in k_score.hip).  More than 512 of them (tie blocks): exact way.
+//                   its place in the output (as topk_merge_kernel in k_eval_tile.hip).  More than 512 of them (tie blocks): exact way.
 //   otherwise       exact: the row's logits into its scratch row (VALU dot products: the operands are bf16, the sum f32), seen
 //                   mask, radix select over the row.
 template <int C>

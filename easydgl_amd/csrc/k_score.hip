@@ -1,4 +1,5 @@
-// K5/K6/K7: tied-embedding scoring against the item table.
+// K5: tied-embedding scoring against the item table.  (The rows around the loss — compaction, CE loss — are k_ce.hip; evaluation
+// on a materialised logits tile, K6 / K7, is k_eval_tile.hip.)
 //   logits[r, n] = rows[r,:] . table[n,:] + bias[n]   (EasyDGL.py:149-150; table row 0 acts as zeros,
 //   bias = concat([-1000], output_bias) — coding.py:56-57, Base.py:106-110)
 // Training never materialises the [R, I] logits: the forward keeps an online (max, sum-exp) per row
@@ -25,8 +26,6 @@
 #include "edgl_common.h"
 #include "score_plan.h"
 #include "score_strip.h"
-#include "topk_select.h"
-#include "batch_prep.h"
 
 namespace {
 
@@ -1162,36 +1161,6 @@ __global__ void flash_finish_kernel(const float* slabs, const float* part, const
     }
 }
 
-// Rows whose label is 0 (a masked position that fell on padding) have weight 0 in the loss (EasyDGL.py:180): they
-// contribute nothing to the loss or to any gradient.  compact_scan orders the weighted rows first
-// (perm[j] = original row of compact row j, inv[r] = compact index of row r or -1, nvalid = #weighted rows), so the
-// scoring kernels can skip the rest exactly.
-__global__ __launch_bounds__(1024) void compact_scan_kernel(const int64_t* labels, int R, int32_t* perm, int32_t* inv,
-                                                            int32_t* nvalid, int64_t* labels_c) {
-    __shared__ int wcnt[2 * 16 * 16];
-    batch_prep::compact_scan_body<1024>(labels, R, perm, inv, nvalid, labels_c, wcnt);
-}
-template <typename T>
-__global__ void compact_gather_kernel(const T* rows, const int64_t* labels, const int32_t* perm, int R, int C, T* rows_c,
-                                      int64_t* labels_c) {
-    const int vpr = C / ElemTraits<T>::VEC;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)R * vpr; i += (long)gridDim.x * blockDim.x) {
-        const int j = (int)(i / vpr), cv = (int)(i % vpr);
-        const int r = perm[j];
-        st16<T>(rows_c + (long)j * C + cv * ElemTraits<T>::VEC, r >= 0 ? ld16<T>(rows + (long)r * C + cv * ElemTraits<T>::VEC) : zero16<T>());
-        if (cv == 0) labels_c[j] = r >= 0 ? labels[r] : 0;
-    }
-}
-template <typename T>
-__global__ void scatter_rows_kernel(const T* rows_c, const int32_t* inv, int R, int C, T* rows) {
-    const int vpr = C / ElemTraits<T>::VEC;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)R * vpr; i += (long)gridDim.x * blockDim.x) {
-        const int r = (int)(i / vpr), cv = (int)(i % vpr);
-        const int j = inv[r];
-        st16<T>(rows + (long)r * C + cv * ElemTraits<T>::VEC, j >= 0 ? ld16<T>(rows_c + (long)j * C + cv * ElemTraits<T>::VEC) : zero16<T>());
-    }
-}
-
 // [rows, C] -> [C, ld] transposed copy (operand images for the second MFMA product).  Two matrices per launch (the compacted
 // rows and the item table): blocks [0, nbx0) of the x grid belong to the first.
 template <typename T>
@@ -1214,489 +1183,6 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* src0, long rows
         if (c0 + c < C && r0 + r < ld) dst[(long)(c0 + c) * ld + r0 + r] = tile[r][c];
     }
 }
-
-// ---------------------------------------------------------------------------------------------
-// CE loss from (lse, label logit) — EasyDGL.py:155,177-185
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void ce_loss_kernel(const float* row_lse, const float* label_logit, const int64_t* labels, int R,
-                                                       float* loss_out, float* coef, const float* add_in, const float* add_in2,
-                                                       const int32_t* wtotal) {
-    // one workgroup; a thread keeps up to CE_KEEP of its rows' probabilities in registers between the two passes (the loads of
-    // a pass are independent, so they overlap instead of paying one memory round trip per row)
-    constexpr int CE_KEEP = 16;
-    __shared__ float red[16];
-    float py[CE_KEEP];
-    float num = 0.f, den = 0.f;
-    {   // all 3 * CE_KEEP loads issued before the first use (`m < R && labels[..]` is a guarded load: a branch and a wait per row
-        // — 16 dependent round trips, 10 us for this kernel)
-        int64_t lb[CE_KEEP];
-        float lg[CE_KEEP], ls[CE_KEEP];
-#pragma unroll
-        for (int i = 0; i < CE_KEEP; ++i) {
-            const int mc = min((int)threadIdx.x + i * 1024, R - 1);
-            lb[i] = labels[mc]; lg[i] = label_logit[mc]; ls[i] = row_lse[mc];
-        }
-#pragma unroll
-        for (int i = 0; i < CE_KEEP; ++i) asm volatile("" : "+v"(lb[i]), "+v"(lg[i]), "+v"(ls[i]));
-#pragma unroll
-        for (int i = 0; i < CE_KEEP; ++i) {
-            const int m = threadIdx.x + i * 1024;
-            const bool on = (m < R) & (lb[i] != 0);   // weight 0 (EasyDGL.py:180): lse may be undefined for such rows
-            const float v = __expf(lg[i] - ls[i]);
-            py[i] = on ? v : -1.f;
-            num += on ? -__logf(v + 1e-5f) : 0.f;
-            den += on ? 1.f : 0.f;
-        }
-    }
-    for (int m = threadIdx.x + CE_KEEP * 1024; m < R; m += 1024) {
-        if (labels[m] == 0) continue;
-        num += -__logf(__expf(label_logit[m] - row_lse[m]) + 1e-5f);
-        den += 1.f;
-    }
-    num = block_sum(num, red);
-    den = block_sum(den, red);
-    const float W = (wtotal ? (float)wtotal[0] : den) + 1e-5f;     // data parallel: the weighted rows of all ranks
-    if (threadIdx.x == 0) loss_out[0] = num / W + (add_in ? add_in[0] : 0.f) + (add_in2 ? add_in2[0] : 0.f);   // + regularisation terms
-    if (!coef) return;    // (the flash forward wrote the coefficients: edgl_score_flash_fwd_coef)
-#pragma unroll
-    for (int i = 0; i < CE_KEEP; ++i) {
-        const int m = threadIdx.x + i * 1024;
-        if (m < R) coef[m] = py[i] >= 0.f ? (1.f / W) * (py[i] / (py[i] + 1e-5f)) : 0.f;
-    }
-    for (int m = threadIdx.x + CE_KEEP * 1024; m < R; m += 1024) {
-        float cf = 0.f;
-        if (labels[m] != 0) {
-            const float v = __expf(label_logit[m] - row_lse[m]);
-            cf = (1.f / W) * (v / (v + 1e-5f));
-        }
-        coef[m] = cf;
-    }
-}
-
-// ce_loss_kernel for a forward that left per-workgroup sums of -log(p_label + 1e-5) (flash_finish_lse_kernel: ce_part): the loss is
-// their sum over the weighted-row count (+ the regularisation terms) — a few thousand numbers instead of three arrays of R rows,
-// and nothing of the batch (labels, lse, label logits) is read: the launch may run any time before the next forward rewrites ce_part.
-__global__ __launch_bounds__(1024) void ce_loss_parts_kernel(const float* ce_part, int nparts, float* loss_out,
-                                                             const float* add_in, const float* add_in2, const int32_t* wtotal) {
-    __shared__ float red[16];
-    float num = 0.f;
-    for (int i0 = threadIdx.x; i0 < nparts; i0 += 1024 * 4) {
-        float v[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = ce_part[min(i0 + j * 1024, nparts - 1)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) num += i0 + j * 1024 < nparts ? v[j] : 0.f;
-    }
-    num = block_sum(num, red);
-    if (threadIdx.x != 0) return;
-    const float W = (wtotal ? (float)wtotal[0] : ce_part[nparts]) + 1e-5f;     // (the count rides behind the sums)
-    loss_out[0] = num / W + (add_in ? add_in[0] : 0.f) + (add_in2 ? add_in2[0] : 0.f);
-}
-
-// ---------------------------------------------------------------------------------------------
-// K6: mask seen items + per-row top-K (Base.py:156-163,181); K7 merge; metrics (Base.py:181-201)
-// ---------------------------------------------------------------------------------------------
-// one workgroup per row: 4-pass radix select of the K-th largest key, then ordered compaction (topk_select.h)
-__global__ __launch_bounds__(256) void mask_topk_kernel(float* logits, int R, int n, int i0, const int64_t* seen,
-                                                        int T, int K, float* out_val, int32_t* out_idx) {
-    const int row = blockIdx.x, tid = threadIdx.x;
-    float* x = logits + (long)row * n;
-    if (seen) {
-        for (int t = tid; t < T; t += blockDim.x) {
-            const long id = seen[(long)row * T + t] - i0;
-            if (id >= 0 && id < n) x[id] = -INFINITY;
-        }
-        __syncthreads();
-    }
-    radix_select_row(x, n, i0, K, out_val + (long)row * K, out_idx + (long)row * K);
-}
-
-// The same selection with the row in REGISTERS (n <= 256 * NJ): the 4-pass form above re-reads the row five times and builds its
-// histograms with LDS atomics that pile up on a handful of bins (the logits of a row share their exponent bits) — 194 us for 512
-// rows of 20 001 items, none of it memory time.  Here a thread keeps its NJ keys.
-//   Fast path: the K-th largest of the 256 THREAD MAXIMA is a lower bound L of the K-th largest key (K distinct elements lie at or
-//   above it), so the top K are among the elements >= L — a few hundred for any row without heavy ties.  They are compacted
-//   into LDS and sorted there by (key descending, index ascending): no pass over all keys per bit, no tie logic.
-//   Otherwise (more than TK_CAP candidates: tie blocks, degenerate rows) the K-th largest key is found bit by bit over ALL keys (32
-//   rounds of "how many keys are >= prefix | bit": one compare per key, the wave total from the ballot's population count), then
-//   the elements above it and the ties at it are gathered — ties in index order only when there are more of them than places left.
-constexpr int TK_CAP = 1024;
-template <int NJ>
-__global__ __launch_bounds__(256) void mask_topk_reg_kernel(float* logits, int R, int n, int i0, const int64_t* seen,
-                                                            int T, int K, float* out_val, int32_t* out_idx) {
-    __shared__ int wcnt[2][4];
-    __shared__ int cnt_gt, cnt_eq;
-    __shared__ float cval[128];
-    __shared__ int cidx[128];
-    __shared__ int wave_eq[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    float* x = logits + (long)row * n;
-    if (seen) {
-        for (int t = tid; t < T; t += 256) {
-            const long id = seen[(long)row * T + t] - i0;
-            if (id >= 0 && id < n) x[id] = -INFINITY;
-        }
-        __syncthreads();
-    }
-    // The row as aligned 16-byte pieces (a row of odd length starts anywhere): piece q = tid + 256 jq of the pieces from the aligned
-    // address below the row's first element; register j = 4 jq + c holds element  i = 4 q + c - d  (d = the row's offset into its
-    // first piece), or key 0 — below every float's key — outside the row.  (4-byte loads: 256 bytes per wave instruction, 1.3 TB/s.)
-    static_assert(NJ % 4 == 0, "registers in groups of one piece");
-    const long e0 = (long)row * n;
-    const int d = (int)(e0 & 3);
-    const float4* xa = reinterpret_cast<const float4*>(logits + (e0 - d));
-    const int npiece = (n + d + 3) >> 2;
-    auto elem = [&](int j) { return 4 * (tid + 256 * (j >> 2)) + (j & 3) - d; };
-    uint32_t key[NJ];
-#pragma unroll
-    for (int jq = 0; jq < NJ / 4; ++jq) {
-        const int q = tid + 256 * jq;
-        const float4 v = xa[min(q, npiece - 1)];
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int i = 4 * q + c - d;
-            key[4 * jq + c] = (i >= 0 && i < n) ? float_key(vv[c]) : 0u;
-        }
-    }
-    const int Keff = min(K, n);
-    // ---- fast path: candidates at or above the K-th largest thread maximum ----------------------------------------------------------
-    __shared__ __attribute__((aligned(16))) uint32_t ckey[TK_CAP];
-    __shared__ __attribute__((aligned(16))) int cix[TK_CAP];
-    __shared__ int ccount;
-    {
-        uint32_t tmax = key[0];
-#pragma unroll
-        for (int j = 1; j < NJ; ++j) tmax = max(tmax, key[j]);
-        // L = the Keff-th largest of the 256 maxima: ONE wave searches it bit by bit on four values per lane (ballots only, no
-        // workgroup barrier per bit)
-        __shared__ uint32_t tmx[256];
-        __shared__ uint32_t Lsh;
-        tmx[tid] = tmax;
-        __syncthreads();
-        if (w == 0) {
-            const uint32_t m0 = tmx[lane], m1 = tmx[lane + 64], m2 = tmx[lane + 128], m3 = tmx[lane + 192];
-            uint32_t Lw = 0u;
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t cand = Lw | (1u << bit);
-                const int c = __popcll(__ballot(m0 >= cand)) + __popcll(__ballot(m1 >= cand)) + __popcll(__ballot(m2 >= cand)) +
-                              __popcll(__ballot(m3 >= cand));
-                if (c >= Keff) Lw = cand;
-            }
-            if (lane == 0) Lsh = Lw;
-        }
-        __syncthreads();
-        const uint32_t L = Lsh;
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) c += __popcll(__ballot(key[j] >= L));
-        if (tid == 0) ccount = 0;
-        if (lane == 0) wcnt[0][w] = c;
-        __syncthreads();
-        const int C = wcnt[0][0] + wcnt[0][1] + wcnt[0][2] + wcnt[0][3];
-        if (C <= TK_CAP) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-                if (key[j] >= L) {
-                    const int pos = atomicAdd(&ccount, 1);
-                    ckey[pos] = key[j]; cix[pos] = elem(j);
-                }
-            __syncthreads();
-            if (C <= 256) {
-                // few candidates (the usual case): every thread ranks its own candidate against all of them — its rank in (key
-                // descending, index ascending) is its place in the output; no sort, no further barrier
-                for (int i = tid; i < K; i += 256) { if (i >= Keff) { out_val[(long)row * K + i] = -INFINITY; out_idx[(long)row * K + i] = -1; } }
-                // (the list is read four candidates per LDS instruction, two such groups in flight: one 32-bit read per candidate
-                //  and iteration was a chain of ~C LDS round trips)
-                if (tid < 4) { ckey[C + tid] = 0u; cix[C + tid] = 0x7fffffff; }      // (C <= 256 < TK_CAP - 4) padding: precedes nobody
-                __syncthreads();
-                if (tid < C) {
-                    const uint32_t a = ckey[tid];
-                    const int ia = cix[tid];
-                    int rank = 0;
-#pragma unroll 2
-                    for (int q = 0; q < C; q += 4) {
-                        const uint4 b = *reinterpret_cast<const uint4*>(ckey + q);
-                        const int4 ib = *reinterpret_cast<const int4*>(cix + q);
-                        rank += ((b.x > a) || (b.x == a && ib.x < ia)) ? 1 : 0;
-                        rank += ((b.y > a) || (b.y == a && ib.y < ia)) ? 1 : 0;
-                        rank += ((b.z > a) || (b.z == a && ib.z < ia)) ? 1 : 0;
-                        rank += ((b.w > a) || (b.w == a && ib.w < ia)) ? 1 : 0;
-                    }
-                    if (rank < Keff) { out_val[(long)row * K + rank] = key_float(a); out_idx[(long)row * K + rank] = ia + i0; }
-                }
-                return;
-            }
-            int P2 = 512;
-            while (P2 < C) P2 <<= 1;
-            for (int t = C + tid; t < P2; t += 256) { ckey[t] = 0u; cix[t] = 0x7fffffff; }
-            __syncthreads();
-            for (int k = 2; k <= P2; k <<= 1)
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int t = tid; t < P2; t += 256) {
-                        const int ixj = t ^ j;
-                        if (ixj > t) {
-                            const uint32_t a = ckey[t], b = ckey[ixj];
-                            const int ia = cix[t], ib = cix[ixj];
-                            const bool a_first = (a > b) || (a == b && ia < ib);
-                            const bool up = (t & k) == 0;
-                            if (up ? !a_first : a_first) { ckey[t] = b; ckey[ixj] = a; cix[t] = ib; cix[ixj] = ia; }
-                        }
-                    }
-                    __syncthreads();
-                }
-            for (int i = tid; i < K; i += 256) {
-                out_val[(long)row * K + i] = i < Keff ? key_float(ckey[i]) : -INFINITY;
-                out_idx[(long)row * K + i] = i < Keff ? cix[i] + i0 : -1;
-            }
-            return;
-        }
-        __syncthreads();
-    }
-    // ---- the K-th largest key: the largest P with |{key >= P}| >= K -------------------------------------------------------------
-    uint32_t prefix = 0u;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t cand = prefix | (1u << bit);
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) c += __popcll(__ballot(key[j] >= cand));     // wave total (scalar unit)
-        if (lane == 0) wcnt[bit & 1][w] = c;
-        __syncthreads();                                                             // (two buffers: one barrier per round)
-        const int tot = wcnt[bit & 1][0] + wcnt[bit & 1][1] + wcnt[bit & 1][2] + wcnt[bit & 1][3];
-        if (tot >= Keff) prefix = cand;
-    }
-    // ---- gather: keys above the prefix (any order), ties at the prefix (the `remaining` lowest indices) ----------------------------
-    if (tid == 0) { cnt_gt = 0; cnt_eq = 0; }
-    if (tid < 128) { cval[tid] = -INFINITY; cidx[tid] = 0x7fffffff; }
-    int c_gt = 0, c_eq = 0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { c_gt += __popcll(__ballot(key[j] > prefix)); c_eq += __popcll(__ballot(key[j] == prefix)); }
-    __syncthreads();
-    if (lane == 0) { atomicAdd(&cnt_gt, c_gt); atomicAdd(&cnt_eq, c_eq); }
-    __syncthreads();
-    const int n_gt = cnt_gt, n_eq = cnt_eq, remaining = Keff - n_gt;
-    __syncthreads();
-    if (tid == 0) { cnt_gt = 0; cnt_eq = 0; }
-    __syncthreads();
-    const bool all_ties = n_eq <= remaining;     // (n_eq >= remaining by construction: == means every tie is taken)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int i = elem(j);
-        if (key[j] > prefix) {
-            const int pos = atomicAdd(&cnt_gt, 1);
-            if (pos < 128) { cval[pos] = key_float(key[j]); cidx[pos] = i; }
-        } else if (all_ties && key[j] == prefix && i >= 0 && i < n) {
-            const int pos = n_gt + atomicAdd(&cnt_eq, 1);
-            if (pos < 128) { cval[pos] = key_float(key[j]); cidx[pos] = i; }
-        }
-    }
-    if (!all_ties) {      // more ties than places: index order — one pass per 1024 consecutive elements (a thread's piece = 4 of them)
-#pragma unroll 1
-        for (int jq = 0; jq < NJ / 4; ++jq) {
-            uint32_t k4[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int q = 0; q < NJ / 4; ++q)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) k4[c] = q == jq ? key[4 * q + c] : k4[c];
-            const int ibase = 4 * (tid + 256 * jq) - d;
-            bool eq[4];
-            int below = 0, wtot = 0, own = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                eq[c] = k4[c] == prefix && ibase + c >= 0 && ibase + c < n;
-                const unsigned long long bal = __ballot(eq[c]);
-                below += __popcll(bal & ((1ull << lane) - 1ull));
-                wtot += __popcll(bal);
-            }
-            if (lane == 0) wave_eq[w] = wtot;
-            __syncthreads();
-            int offs = cnt_eq + below;
-            for (int ww = 0; ww < w; ++ww) offs += wave_eq[ww];
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if (eq[c]) {
-                    const int pos = offs + own;
-                    if (pos < remaining) { cval[n_gt + pos] = key_float(prefix); cidx[n_gt + pos] = ibase + c; }
-                    ++own;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) cnt_eq += wave_eq[0] + wave_eq[1] + wave_eq[2] + wave_eq[3];
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-    // bitonic sort of 128 candidates by (value desc, index asc)
-    for (int k = 2; k <= 128; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (tid < 128) {
-                const int ixj = tid ^ j;
-                if (ixj > tid) {
-                    const float a = cval[tid], b = cval[ixj];
-                    const int ia = cidx[tid], ib = cidx[ixj];
-                    const bool a_first = (a > b) || (a == b && ia < ib);  // a should precede b
-                    const bool up = (tid & k) == 0;
-                    if (up ? !a_first : a_first) { cval[tid] = b; cval[ixj] = a; cidx[tid] = ib; cidx[ixj] = ia; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = tid; i < K; i += 256) {
-        out_val[(long)row * K + i] = i < Keff ? cval[i] : -INFINITY;
-        out_idx[(long)row * K + i] = i < Keff ? cidx[i] + i0 : -1;
-    }
-}
-
-// candidates [S][R][K] -> global top-K by (value desc, index asc); S*K <= 1024
-// counts (optional, [R]): the first counts[row] slots of a row's S*K (slot j = list j / K, place j % K) hold candidates, the rest
-// is unwritten memory (the fused evaluation scoring appends candidates: k_eval_topk.hip); a row whose count exceeds S*K is left
-// to that file's exact fallback kernel and not written here.
-__global__ __launch_bounds__(256) void topk_merge_kernel(const float* cand_val, const int32_t* cand_idx, int S, int R,
-                                                         int K, float* out_val, int32_t* out_idx, const int32_t* counts) {
-    __shared__ float v[1024];
-    __shared__ int ix[1024];
-    const int row = blockIdx.x, tid = threadIdx.x;
-    int n = S * K;
-    if (counts) {
-        const int c = counts[row];
-        if (c < 0 || c > n) return;
-        n = c;
-    }
-    {   // the four slots of a thread: all eight loads out before the first use (slot index clamped: no load behind a branch)
-        int id4[4]; float v4[4];
-        const int SK = S * K;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = min(tid + 256 * j, SK - 1), s = i / K, k = i - s * K;
-            id4[j] = cand_idx[((long)s * R + row) * K + k];
-            v4[j] = cand_val[((long)s * R + row) * K + k];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(id4[j]), "+v"(v4[j]));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int i = tid + 256 * j;
-            const bool ok = i < n && id4[j] >= 0;
-            v[i] = ok ? v4[j] : -INFINITY;
-            ix[i] = ok ? id4[j] : 0x7fffffff;
-        }
-    }
-    // Fast path (any input order; as in mask_topk_reg_kernel): a thread looks at its <= 4 candidates, the K-th largest of the 256 thread
-    // maxima is a lower bound of the K-th largest candidate, the candidates at or above it — a few hundred — are compacted and each
-    // one's rank among them, in (value descending, index ascending), is its place in the output.  ~3 us instead of the 42 us of the
-    // 1024-element bitonic sort below, which stays for inputs with more than 256 candidates above the bound (tie blocks).
-    {
-        __shared__ uint32_t tmx[256];
-        __shared__ uint32_t Lsh;
-        __shared__ __attribute__((aligned(16))) uint32_t ckey[264];
-        __shared__ __attribute__((aligned(16))) int cix[264];
-        __shared__ int ccount, wsum[4];
-        const int lane = tid & 63, w = tid >> 6;
-        const int Keff = min(K, n);
-        uint32_t key[4];
-        int kid[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = tid + 256 * q;      // (n <= 1024)
-            const bool ok = i < n && ix[i] != 0x7fffffff;
-            key[q] = ok ? float_key(v[i]) : 0u;
-            kid[q] = ok ? ix[i] : 0x7fffffff;
-        }
-        tmx[tid] = max(max(key[0], key[1]), max(key[2], key[3]));
-        if (tid == 0) ccount = 0;
-        __syncthreads();
-        if (w == 0) {
-            const uint32_t m0 = tmx[lane], m1 = tmx[lane + 64], m2 = tmx[lane + 128], m3 = tmx[lane + 192];
-            uint32_t Lw = 0u;
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t cand = Lw | (1u << bit);
-                const int c = __popcll(__ballot(m0 >= cand)) + __popcll(__ballot(m1 >= cand)) + __popcll(__ballot(m2 >= cand)) +
-                              __popcll(__ballot(m3 >= cand));
-                if (c >= Keff) Lw = cand;
-            }
-            if (lane == 0) Lsh = Lw;
-        }
-        __syncthreads();
-        const uint32_t L = max(Lsh, 1u);      // (key 0: invalid / absent candidates never qualify)
-        int c = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) c += __popcll(__ballot(key[q] >= L));
-        if (lane == 0) wsum[w] = c;
-        __syncthreads();
-        const int C = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (C <= 256) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (key[q] >= L) {
-                    const int pos = atomicAdd(&ccount, 1);
-                    ckey[pos] = key[q]; cix[pos] = kid[q];
-                }
-            for (int i = tid; i < K; i += blockDim.x) { out_val[(long)row * K + i] = -INFINITY; out_idx[(long)row * K + i] = -1; }
-            __syncthreads();
-            if (tid < 4) { ckey[C + tid] = 0u; cix[C + tid] = 0x7fffffff; }
-            __syncthreads();
-            if (tid < C) {
-                const uint32_t a = ckey[tid];
-                const int ia = cix[tid];
-                int rank = 0;
-#pragma unroll 2
-                for (int q = 0; q < C; q += 4) {
-                    const uint4 b = *reinterpret_cast<const uint4*>(ckey + q);
-                    const int4 ib = *reinterpret_cast<const int4*>(cix + q);
-                    // (a repeated (value, index) pair: the copy that sits first in the list goes first)
-                    rank += ((b.x > a) || (b.x == a && (ib.x < ia || (ib.x == ia && q < tid)))) ? 1 : 0;
-                    rank += ((b.y > a) || (b.y == a && (ib.y < ia || (ib.y == ia && q + 1 < tid)))) ? 1 : 0;
-                    rank += ((b.z > a) || (b.z == a && (ib.z < ia || (ib.z == ia && q + 2 < tid)))) ? 1 : 0;
-                    rank += ((b.w > a) || (b.w == a && (ib.w < ia || (ib.w == ia && q + 3 < tid)))) ? 1 : 0;
-                }
-                if (rank < K) { out_val[(long)row * K + rank] = key_float(a); out_idx[(long)row * K + rank] = ia; }
-            }
-            return;
-        }
-        __syncthreads();
-    }
-    for (int k = 2; k <= 1024; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < 1024; t += blockDim.x) {
-                const int ixj = t ^ j;
-                if (ixj > t) {
-                    const float a = v[t], b = v[ixj];
-                    const int ia = ix[t], ib = ix[ixj];
-                    const bool a_first = (a > b) || (a == b && ia < ib);
-                    const bool up = (t & k) == 0;
-                    if (up ? !a_first : a_first) { v[t] = b; v[ixj] = a; ix[t] = ib; ix[ixj] = ia; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = tid; i < K; i += blockDim.x) {
-        out_val[(long)row * K + i] = v[i];
-        out_idx[(long)row * K + i] = ix[i] == 0x7fffffff ? -1 : ix[i];
-    }
-}
-
-__global__ void rank_metrics_kernel(const int32_t* topk, int R, int K, const int64_t* label, float* metrics) {
-    __shared__ float red[8];
-    float h10 = 0, h50 = 0, h100 = 0, n10 = 0, n50 = 0, n100 = 0;
-    for (int r = threadIdx.x; r < R; r += blockDim.x) {
-        const int lab = (int)label[r];
-        int rank = -1;
-        for (int k = 0; k < K && k < 100; ++k)
-            if (topk[(long)r * K + k] == lab) { rank = k; break; }
-        if (rank >= 0) {
-            const float gain = 1.0f / log2f((float)rank + 2.0f);
-            if (rank < 10) { h10 += 1; n10 += gain; }
-            if (rank < 50) { h50 += 1; n50 += gain; }
-            h100 += 1; n100 += gain;
-        }
-    }
-    float vals[6] = {h10, h50, h100, n10, n50, n100};
-    for (int i = 0; i < 6; ++i) {
-        const float t = block_sum(vals[i], red);
-        if (threadIdx.x == 0) metrics[i] += t;
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -1945,8 +1431,9 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
     return EDGL_OK;
 }
 
-int check_score(const void* rows, const void* table, const float* out_bias, int R, int C, int I, int i0, int i1,
-                int dtype, const char* who) {
+// The arguments every scoring entry point takes: checked (errors carry the name `who`), then copied into a fresh ScoreP.
+int check_score(ScoreP& p, const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R, int C, int I,
+                int i0, int i1, const int32_t* nvalid, int dtype, const char* who) {
     EDGL_REQUIRE(rows && table && out_bias, EDGL_ERR_NULL, "%s: null pointer", who);
     EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "%s: bad dtype %d", who, dtype);
     EDGL_REQUIRE(R > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1 && (i0 % 8) == 0, EDGL_ERR_SHAPE,
@@ -1955,6 +1442,9 @@ int check_score(const void* rows, const void* table, const float* out_bias, int 
                  "%s: operands must be 16-byte aligned", who);
     EDGL_REQUIRE(C >= 32 && C <= 512 && (C & (C - 1)) == 0, EDGL_ERR_SHAPE, "%s: C=%d unsupported (power of two in [32, 512])",
                  who, C);
+    p = ScoreP{};
+    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
+    p.i1 = i1; p.nvalid = nvalid;
     return EDGL_OK;
 }
 
@@ -1982,11 +1472,21 @@ int bwd_dispatch(ScoreP p, int C, const BwdPlan& plan, float* ws, void* d_rows, 
 #undef CALL_BWD
 }
 
-}  // namespace
+inline size_t esize_of(int dtype) { return dtype == EDGL_BF16 ? 2 : 4; }
+// the plan of a workspace: `flash` — the one the MODE 1 / 2 calls share (strip kernels where they apply), else edgl_score_ce_bwd's
+inline BwdPlan plan_of(int R, int C, int I, int n_items, int dtype, bool flash) {
+    return bwd_plan(R, C, I, n_items, esize_of(dtype), flash ? use_strip(C, esize_of(dtype)) : 0);
+}
+// run_bwd_mode<T, C / 16, MODE> over the plan of p's shape.  MODE 1 — every flash forward — passes d_rows or NULL and no table side.
+template <int MODE>
+int score_run(const ScoreP& p, float* workspace, void* d_rows, float* d_table, float* d_bias, int dtype, void* stream) {
+    const BwdPlan plan = plan_of(p.R, p.C, p.I, p.i1 - p.i0, dtype, MODE != 0);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == EDGL_F32 ? bwd_dispatch<float, MODE>(p, p.C, plan, workspace, d_rows, d_table, d_bias, st)
+                             : bwd_dispatch<bf16, MODE>(p, p.C, plan, workspace, d_rows, d_table, d_bias, st);
+}
 
-extern "C" int edgl_score_flash_fwd_coef_w(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
-                                           int C, int I, const int32_t* nvalid, const int32_t* wtotal, float* row_lse,
-                                           float* label_logit, float* coef, float* workspace, int dtype, void* stream);
+}  // namespace
 
 // workspace rule of the forward: 2 * R * edgl_score_chunks floats >= 2 * XB * (#workgroups), the most (row, chunk)
 // partial pairs any device-side split of the launch can produce
@@ -2000,72 +1500,19 @@ extern "C" int edgl_score_chunks(int R, int n_items) {
     return (int)best;
 }
 
-// edgl_compact_rows = edgl_compact_scan (labels only: may run as soon as the batch is known, e.g. on a side stream at the start
-// of the step) + edgl_compact_gather (needs the rows)
-extern "C" int edgl_compact_scan(const int64_t* labels, int R, int32_t* perm, int32_t* inv, int32_t* nvalid, void* stream) {
-    EDGL_REQUIRE(labels && perm && inv && nvalid, EDGL_ERR_NULL, "edgl_compact_scan: null pointer");
-    EDGL_REQUIRE(R > 0, EDGL_ERR_SHAPE, "edgl_compact_scan: bad shape R=%d", R);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, labels, R, perm, inv, nvalid, (int64_t*)nullptr);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-// The scan that also writes the compacted labels (labels_c [R]: the labels of the weighted rows first, 0 behind them) — with
-// it and edgl_tail_fwd's row map the rows reach the scoring kernels without edgl_compact_gather.
-extern "C" int edgl_compact_scan_labels(const int64_t* labels, int R, int32_t* perm, int32_t* inv, int32_t* nvalid,
-                                        int64_t* labels_c, void* stream) {
-    EDGL_REQUIRE(labels && perm && inv && nvalid && labels_c, EDGL_ERR_NULL, "edgl_compact_scan_labels: null pointer");
-    EDGL_REQUIRE(R > 0, EDGL_ERR_SHAPE, "edgl_compact_scan_labels: bad shape R=%d", R);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, labels, R, perm, inv, nvalid, labels_c);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-extern "C" int edgl_compact_gather(const void* rows, const int64_t* labels, const int32_t* perm, int R, int C, void* rows_c,
-                                   int64_t* labels_c, int dtype, void* stream) {
-    EDGL_REQUIRE(rows && labels && perm && rows_c && labels_c, EDGL_ERR_NULL, "edgl_compact_gather: null pointer");
-    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_compact_gather: bad dtype %d", dtype);
-    EDGL_REQUIRE(R > 0 && C % (dtype == EDGL_BF16 ? 8 : 4) == 0, EDGL_ERR_SHAPE, "edgl_compact_gather: bad shape R=%d C=%d", R, C);
-    hipStream_t st = (hipStream_t)stream;
-    const long nv = (long)R * C / (dtype == EDGL_BF16 ? 8 : 4);
-    const unsigned nb = (unsigned)std::min<long>((nv + 255) / 256, 2048);
-    if (dtype == EDGL_F32) hipLaunchKernelGGL((compact_gather_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)rows, labels, perm, R, C, (float*)rows_c, labels_c);
-    else hipLaunchKernelGGL((compact_gather_kernel<bf16>), dim3(nb), dim3(256), 0, st, (const bf16*)rows, labels, perm, R, C, (bf16*)rows_c, labels_c);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-extern "C" int edgl_compact_rows(const void* rows, const int64_t* labels, int R, int C, int32_t* perm, int32_t* inv,
-                                 int32_t* nvalid, void* rows_c, int64_t* labels_c, int dtype, void* stream) {
-    EDGL_REQUIRE(rows && labels && perm && inv && nvalid && rows_c && labels_c, EDGL_ERR_NULL, "edgl_compact_rows: null pointer");
-    const int rc = edgl_compact_scan(labels, R, perm, inv, nvalid, stream);
-    return rc ? rc : edgl_compact_gather(rows, labels, perm, R, C, rows_c, labels_c, dtype, stream);
-}
-
-extern "C" int edgl_scatter_rows(const void* rows_c, const int32_t* inv, int R, int C, void* rows, int dtype, void* stream) {
-    EDGL_REQUIRE(rows_c && inv && rows, EDGL_ERR_NULL, "edgl_scatter_rows: null pointer");
-    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_scatter_rows: bad dtype %d", dtype);
-    hipStream_t st = (hipStream_t)stream;
-    const long nv = (long)R * C / (dtype == EDGL_BF16 ? 8 : 4);
-    const unsigned nb = (unsigned)std::min<long>((nv + 255) / 256, 2048);
-    if (dtype == EDGL_F32) hipLaunchKernelGGL((scatter_rows_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)rows_c, inv, R, C, (float*)rows);
-    else hipLaunchKernelGGL((scatter_rows_kernel<bf16>), dim3(nb), dim3(256), 0, st, (const bf16*)rows_c, inv, R, C, (bf16*)rows);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-
 extern "C" int edgl_score_lse_fwd(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                                   int R, int C, int I, int i0, int i1, const int32_t* nvalid, float* row_lse,
                                   float* label_logit, float* logits, float* workspace, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, i0, i1, dtype, "edgl_score_lse_fwd");
+    ScoreP p;
+    int rc = check_score(p, rows, table, out_bias, labels, R, C, I, i0, i1, nvalid, dtype, "edgl_score_lse_fwd");
     if (rc) return rc;
     // row_lse == NULL (with logits): the logits tile only — the evaluation path (score_topk) has no use for the normaliser, and the
     // one-thread-per-row merge of the chunk partials is a chain of dependent loads (46 us per tile at 512 rows)
     EDGL_REQUIRE((row_lse || logits) && workspace && (!labels || label_logit), EDGL_ERR_NULL, "edgl_score_lse_fwd: null output");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
-    p.i1 = i1; p.nvalid = nvalid; p.row_lse = row_lse; p.part = workspace; p.logits = logits;
-    const size_t esize = dtype == EDGL_BF16 ? 2 : 4;
-    const RtCfg cf = rt_cfg(C, esize);
+    p.row_lse = row_lse; p.part = workspace; p.logits = logits;
+    const RtCfg cf = rt_cfg(C, esize_of(dtype));
     const int xbf = 16 * cf.ix * (SNT / 64);
-    const Chunking ch = pick_chunks(xblocks_of(R, xbf), i1 - i0, SCORE_FTARGET, cf.zb, l2_tiles_for(C, esize, 1, cf.zb));
+    const Chunking ch = pick_chunks(xblocks_of(R, xbf), i1 - i0, SCORE_FTARGET, cf.zb, l2_tiles_for(C, esize_of(dtype), 1, cf.zb));
     p.nchunk = ch.nchunk; p.zchunk = ch.zchunk;
     hipStream_t st = (hipStream_t)stream;
     rc = dtype == EDGL_F32 ? fwd_dispatch<float>(p, C, st) : fwd_dispatch<bf16>(p, C, st);
@@ -2085,59 +1532,21 @@ extern "C" int edgl_score_lse_fwd(const void* rows, const void* table, const flo
     return EDGL_OK;
 }
 
-extern "C" int edgl_ce_loss_fwd_add_w(const float* row_lse, const float* label_logit, const int64_t* labels, int R, float* loss_out,
-                                      float* coef, const float* add_in, const float* add_in2, const int32_t* wtotal, void* stream) {
-    EDGL_REQUIRE(row_lse && label_logit && labels && loss_out, EDGL_ERR_NULL, "edgl_ce_loss_fwd: null pointer");   // coef may be NULL
-    hipLaunchKernelGGL(ce_loss_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_lse, label_logit, labels, R, loss_out, coef,
-                       add_in, add_in2, wtotal);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-// number of per-workgroup loss sums edgl_score_flash_fwd_rows_wp writes (0: this shape has no one-launch row finish)
-extern "C" int edgl_score_ce_nparts(int R, int C) {
-    if (!(C == 128 || C == 64 || C == 256 || C == 512) || R <= 0) return 0;
-    const long lpr = C == 512 ? 64 : C / 4;      // (C = 512: eight channels per lane)
-    return (int)std::min<long>(((long)R * lpr + 255) / 256, 4096);
-}
-// loss (EasyDGL.py:181-188) from the sums edgl_score_flash_fwd_rows_wp left in ce_part: sum / (weighted rows + 1e-5) + add_in + add_in2
-// (ce_part: edgl_score_ce_nparts(R, C) sums and, behind them, the weighted-row count — nparts + 1 floats; wtotal: the global count
-// under data parallelism)
-extern "C" int edgl_ce_loss_parts(const float* ce_part, int nparts, float* loss_out, const float* add_in, const float* add_in2,
-                                  const int32_t* wtotal, void* stream) {
-    EDGL_REQUIRE(ce_part && loss_out && nparts > 0, EDGL_ERR_NULL, "edgl_ce_loss_parts: null pointer / bad size");
-    hipLaunchKernelGGL(ce_loss_parts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, ce_part, nparts, loss_out, add_in, add_in2,
-                       wtotal);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-extern "C" int edgl_ce_loss_fwd_add(const float* row_lse, const float* label_logit, const int64_t* labels, int R, float* loss_out,
-                                    float* coef, const float* add_in, const float* add_in2, void* stream) {
-    return edgl_ce_loss_fwd_add_w(row_lse, label_logit, labels, R, loss_out, coef, add_in, add_in2, nullptr, stream);
-}
-extern "C" int edgl_ce_loss_fwd(const float* row_lse, const float* label_logit, const int64_t* labels, int R,
-                                float* loss_out, float* coef, void* stream) {
-    return edgl_ce_loss_fwd_add(row_lse, label_logit, labels, R, loss_out, coef, nullptr, nullptr, stream);
-}
-
 extern "C" long edgl_score_bwd_workspace(int R, int C, int I, int n_items, int dtype) {
-    return bwd_plan(R, C, I, n_items, dtype == EDGL_BF16 ? 2 : 4).total;
+    return plan_of(R, C, I, n_items, dtype, false).total;
 }
 
 extern "C" int edgl_score_ce_bwd(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                                  const float* row_lse, const float* coef, const float* gscale, int R, int C, int I,
                                  int i0, int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias,
                                  float* workspace, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, i0, i1, dtype, "edgl_score_ce_bwd");
+    ScoreP p;
+    const int rc = check_score(p, rows, table, out_bias, labels, R, C, I, i0, i1, nvalid, dtype, "edgl_score_ce_bwd");
     if (rc) return rc;
     EDGL_REQUIRE(labels && row_lse && coef && d_rows && d_table && d_bias && workspace, EDGL_ERR_NULL,
                  "edgl_score_ce_bwd: null pointer");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
-    p.i1 = i1; p.nvalid = nvalid; p.row_lse = const_cast<float*>(row_lse); p.coef = coef; p.gscale = gscale;
-    const BwdPlan plan = bwd_plan(R, C, I, i1 - i0, dtype == EDGL_BF16 ? 2 : 4);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 0>(p, C, plan, workspace, d_rows, d_table, d_bias, st)
-                             : bwd_dispatch<bf16, 0>(p, C, plan, workspace, d_rows, d_table, d_bias, st);
+    p.row_lse = const_cast<float*>(row_lse); p.coef = coef; p.gscale = gscale;
+    return score_run<0>(p, workspace, d_rows, d_table, d_bias, dtype, stream);
 }
 
 // ---- "flash" form: the forward scoring pass already accumulates the row gradients -------------------------------------------
@@ -2148,33 +1557,17 @@ extern "C" int edgl_score_ce_bwd(const void* rows, const void* table, const floa
 // The logits are computed 2x per step (here and in the d_table pass) instead of 3x.  `workspace` (edgl_score_flash_workspace
 // floats) carries the slabs from the forward to the backward call and must not be touched in between.
 extern "C" long edgl_score_flash_workspace(int R, int C, int I, int n_items, int dtype) {
-    return bwd_plan(R, C, I, n_items, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4)).total;
-}
-
-extern "C" int edgl_score_flash_fwd(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
-                                    int C, int I, int i0, int i1, const int32_t* nvalid, float* row_lse, float* label_logit,
-                                    float* workspace, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, i0, i1, dtype, "edgl_score_flash_fwd");
-    if (rc) return rc;
-    EDGL_REQUIRE(labels && row_lse && label_logit && workspace, EDGL_ERR_NULL, "edgl_score_flash_fwd: null pointer");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
-    p.i1 = i1; p.nvalid = nvalid; p.row_lse = row_lse;
-    const BwdPlan plan = bwd_plan(R, C, I, i1 - i0, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
-    hipStream_t st = (hipStream_t)stream;
-    p.lab_out = label_logit;   // row LSE and label logits come out of one small kernel behind the scoring pass
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st)
-                             : bwd_dispatch<bf16, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st);
+    return plan_of(R, C, I, n_items, dtype, true).total;
 }
 
 // The transposed image of the item table depends on the weights only: edgl_score_prepare_table writes it into the flash
-// workspace ahead of time (e.g. on a side stream at the start of the step) and edgl_score_flash_fwd_pre then transposes the
-// rows alone.  Same R, C, I, [i0, i1) and workspace as the forward call that follows.
+// workspace ahead of time (e.g. on a side stream at the start of the step) and edgl_score_flash_fwd_pre(table_ready = 1) then
+// transposes the rows alone.  Same R, C, I, [i0, i1) and workspace as the forward call that follows.
 extern "C" int edgl_score_prepare_table(const void* table, int R, int C, int I, int i0, int i1, float* workspace, int dtype,
                                         void* stream) {
     EDGL_REQUIRE(table && workspace, EDGL_ERR_NULL, "edgl_score_prepare_table: null pointer");
     EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_score_prepare_table: bad dtype %d", dtype);
-    const BwdPlan plan = bwd_plan(R, C, I, i1 - i0, dtype == EDGL_BF16 ? 2 : 4);
+    const BwdPlan plan = plan_of(R, C, I, i1 - i0, dtype, false);
     const long ldt = (long)up8(I);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((ldt + 63) / 64), (C + 63) / 64);
@@ -2184,54 +1577,68 @@ extern "C" int edgl_score_prepare_table(const void* table, int R, int C, int I, 
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
+// (row LSE and label logits come out of one small kernel behind the scoring pass)
 extern "C" int edgl_score_flash_fwd_pre(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
                                         int C, int I, int i0, int i1, const int32_t* nvalid, float* row_lse, float* label_logit,
                                         float* workspace, int table_ready, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, i0, i1, dtype, "edgl_score_flash_fwd");
+    ScoreP p;
+    const int rc = check_score(p, rows, table, out_bias, labels, R, C, I, i0, i1, nvalid, dtype, "edgl_score_flash_fwd");
     if (rc) return rc;
     EDGL_REQUIRE(labels && row_lse && label_logit && workspace, EDGL_ERR_NULL, "edgl_score_flash_fwd: null pointer");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
-    p.i1 = i1; p.nvalid = nvalid; p.row_lse = row_lse; p.lab_out = label_logit; p.table_ready = table_ready;
-    const BwdPlan plan = bwd_plan(R, C, I, i1 - i0, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st)
-                             : bwd_dispatch<bf16, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st);
+    p.row_lse = row_lse; p.lab_out = label_logit; p.table_ready = table_ready;
+    return score_run<1>(p, workspace, nullptr, nullptr, nullptr, dtype, stream);
+}
+extern "C" int edgl_score_flash_fwd(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
+                                    int C, int I, int i0, int i1, const int32_t* nvalid, float* row_lse, float* label_logit,
+                                    float* workspace, int dtype, void* stream) {
+    return edgl_score_flash_fwd_pre(rows, table, out_bias, labels, R, C, I, i0, i1, nvalid, row_lse, label_logit, workspace, 0, dtype, stream);
 }
 // edgl_score_flash_fwd over the whole table for COMPACTED rows (edgl_compact_*: the *nvalid weighted rows first, labels 0 behind
 // them) that also writes the loss coefficients coef[r] = (1 / (n + 1e-5)) * p_y / (p_y + 1e-5), n = *nvalid — what edgl_ce_loss_fwd
 // computes after a reduction over the rows; with them the backward does not wait for the loss kernel (EasyDGL.py:177-185).
+// Data parallel form: `wtotal` (device, may be NULL) = weighted rows of the GLOBAL batch; the coefficients then are those of the
+// global loss (EasyDGL.py:183-185 with the denominator summed over the ranks), and the ranks' gradients ADD UP to its gradient.
+extern "C" int edgl_score_flash_fwd_coef_w(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
+                                           int C, int I, const int32_t* nvalid, const int32_t* wtotal, float* row_lse,
+                                           float* label_logit, float* coef, float* workspace, int dtype, void* stream) {
+    ScoreP p;
+    const int rc = check_score(p, rows, table, out_bias, labels, R, C, I, 0, I, nvalid, dtype, "edgl_score_flash_fwd_coef");
+    if (rc) return rc;
+    EDGL_REQUIRE(labels && row_lse && label_logit && workspace && nvalid && coef, EDGL_ERR_NULL,
+                 "edgl_score_flash_fwd_coef: null pointer (the row count of the compaction is required)");
+    p.row_lse = row_lse; p.lab_out = label_logit; p.coef_out = coef; p.wtotal = wtotal;
+    return score_run<1>(p, workspace, nullptr, nullptr, nullptr, dtype, stream);
+}
 extern "C" int edgl_score_flash_fwd_coef(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
                                          int C, int I, const int32_t* nvalid, float* row_lse, float* label_logit, float* coef,
                                          float* workspace, int dtype, void* stream) {
     return edgl_score_flash_fwd_coef_w(rows, table, out_bias, labels, R, C, I, nvalid, nullptr, row_lse, label_logit, coef, workspace,
                                        dtype, stream);
 }
-// Data parallel form: `wtotal` (device, may be NULL) = weighted rows of the GLOBAL batch; the coefficients then are those of the
-// global loss (EasyDGL.py:183-185 with the denominator summed over the ranks), and the ranks' gradients ADD UP to its gradient.
-extern "C" int edgl_score_flash_fwd_coef_w(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
-                                           int C, int I, const int32_t* nvalid, const int32_t* wtotal, float* row_lse,
-                                           float* label_logit, float* coef, float* workspace, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, 0, I, dtype, "edgl_score_flash_fwd_coef");
-    if (rc) return rc;
-    EDGL_REQUIRE(labels && row_lse && label_logit && workspace && nvalid && coef, EDGL_ERR_NULL,
-                 "edgl_score_flash_fwd_coef: null pointer (the row count of the compaction is required)");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = 0;
-    p.i1 = I; p.nvalid = nvalid; p.row_lse = row_lse; p.lab_out = label_logit; p.coef_out = coef; p.wtotal = wtotal;
-    const BwdPlan plan = bwd_plan(R, C, I, I, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st)
-                             : bwd_dispatch<bf16, 1>(p, C, plan, workspace, nullptr, nullptr, nullptr, st);
-}
 
+// number of per-workgroup loss sums edgl_score_flash_fwd_rows_wp writes (0: this shape has no one-launch row finish)
+extern "C" int edgl_score_ce_nparts(int R, int C) {
+    if (!(C == 128 || C == 64 || C == 256 || C == 512) || R <= 0) return 0;
+    const long lpr = C == 512 ? 64 : C / 4;      // (C = 512: eight channels per lane)
+    return (int)std::min<long>(((long)R * lpr + 255) / 256, 4096);
+}
 // edgl_score_flash_fwd_coef_w that also finishes the rows: d_rows (= gscale * d loss / d rows, what edgl_score_flash_bwd would write)
 // comes out of the same launch as lse / label logits / coefficients; edgl_score_flash_bwd is then called with d_rows = NULL and
-// only runs the table side.
+// only runs the table side.  It also leaves the loss numerator as edgl_score_ce_nparts(R, C) per-workgroup sums in ce_part (NULL:
+// none), for edgl_ce_loss_parts — the loss launch then reads nothing of the batch.
 extern "C" int edgl_score_flash_fwd_rows_wp(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
                                             int C, int I, const int32_t* nvalid, const int32_t* wtotal, const float* gscale,
                                             float* row_lse, float* label_logit, float* coef, void* d_rows, float* ce_part,
-                                            float* workspace, int dtype, void* stream);
+                                            float* workspace, int dtype, void* stream) {
+    ScoreP p;
+    const int rc = check_score(p, rows, table, out_bias, labels, R, C, I, 0, I, nvalid, dtype, "edgl_score_flash_fwd_rows");
+    if (rc) return rc;
+    EDGL_REQUIRE(!ce_part || edgl_score_ce_nparts(R, C) > 0, EDGL_ERR_SHAPE, "edgl_score_flash_fwd_rows_wp: no per-workgroup loss sums at C=%d", C);
+    EDGL_REQUIRE(labels && row_lse && label_logit && workspace && nvalid && coef && d_rows, EDGL_ERR_NULL,
+                 "edgl_score_flash_fwd_rows: null pointer (the row count of the compaction is required)");
+    p.row_lse = row_lse; p.lab_out = label_logit; p.coef_out = coef; p.wtotal = wtotal; p.gscale = gscale; p.ce_part = ce_part;
+    return score_run<1>(p, workspace, d_rows, nullptr, nullptr, dtype, stream);
+}
 extern "C" int edgl_score_flash_fwd_rows_w(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
                                            int C, int I, const int32_t* nvalid, const int32_t* wtotal, const float* gscale,
                                            float* row_lse, float* label_logit, float* coef, void* d_rows, float* workspace,
@@ -2239,31 +1646,23 @@ extern "C" int edgl_score_flash_fwd_rows_w(const void* rows, const void* table, 
     return edgl_score_flash_fwd_rows_wp(rows, table, out_bias, labels, R, C, I, nvalid, wtotal, gscale, row_lse, label_logit, coef, d_rows,
                                         nullptr, workspace, dtype, stream);
 }
-// ... that also leaves the loss numerator as edgl_score_ce_nparts(R, C) per-workgroup sums in ce_part (NULL: none), for
-// edgl_ce_loss_parts — the loss launch then reads nothing of the batch
-extern "C" int edgl_score_flash_fwd_rows_wp(const void* rows, const void* table, const float* out_bias, const int64_t* labels, int R,
-                                            int C, int I, const int32_t* nvalid, const int32_t* wtotal, const float* gscale,
-                                            float* row_lse, float* label_logit, float* coef, void* d_rows, float* ce_part,
-                                            float* workspace, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, 0, I, dtype, "edgl_score_flash_fwd_rows");
-    if (rc) return rc;
-    EDGL_REQUIRE(!ce_part || edgl_score_ce_nparts(R, C) > 0, EDGL_ERR_SHAPE, "edgl_score_flash_fwd_rows_wp: no per-workgroup loss sums at C=%d", C);
-    EDGL_REQUIRE(labels && row_lse && label_logit && workspace && nvalid && coef && d_rows, EDGL_ERR_NULL,
-                 "edgl_score_flash_fwd_rows: null pointer (the row count of the compaction is required)");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = 0;
-    p.i1 = I; p.nvalid = nvalid; p.row_lse = row_lse; p.lab_out = label_logit; p.coef_out = coef; p.wtotal = wtotal; p.gscale = gscale;
-    p.ce_part = ce_part;
-    const BwdPlan plan = bwd_plan(R, C, I, I, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 1>(p, C, plan, workspace, d_rows, nullptr, nullptr, st)
-                             : bwd_dispatch<bf16, 1>(p, C, plan, workspace, d_rows, nullptr, nullptr, st);
-}
 
 extern "C" int edgl_score_flash_bwd_ex(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                                        const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int i0,
                                        int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias,
-                                       float* workspace, int defer_label_term, int dtype, void* stream);
+                                       float* workspace, int defer_label_term, int dtype, void* stream) {
+    ScoreP p;
+    const int rc = check_score(p, rows, table, out_bias, labels, R, C, I, i0, i1, nvalid, dtype, "edgl_score_flash_bwd");
+    if (rc) return rc;
+    // d_rows == NULL: the rows were finished by edgl_score_flash_fwd_rows_w; only d_table / d_bias are computed
+    EDGL_REQUIRE(labels && row_lse && coef && d_table && d_bias && workspace, EDGL_ERR_NULL,
+                 "edgl_score_flash_bwd: null pointer");
+    p.row_lse = const_cast<float*>(row_lse); p.coef = coef; p.gscale = gscale;
+    p.defer_label = (defer_label_term & 1) != 0;
+    p.acc_atomic = (defer_label_term & 2) != 0;      // (bf16, C = 128 strip path only; elsewhere the slabs)
+    p.keep_slabs = (defer_label_term & 4) != 0 && (defer_label_term & 1) != 0 && !gscale && i0 == 0 && i1 == I;
+    return score_run<2>(p, workspace, d_rows, d_table, d_bias, dtype, stream);
+}
 extern "C" int edgl_score_flash_bwd(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
                                     const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int i0,
                                     int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias,
@@ -2281,86 +1680,26 @@ extern "C" int edgl_score_flash_label_term(const void* rows, const int64_t* labe
                                            void* stream) {
     EDGL_REQUIRE(rows && labels && coef && d_table && d_bias, EDGL_ERR_NULL, "edgl_score_flash_label_term: null pointer");
     EDGL_REQUIRE(R > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1, EDGL_ERR_SHAPE, "edgl_score_flash_label_term: bad shape");
-    if (!use_strip(C, dtype == EDGL_BF16 ? 2 : 4)) return EDGL_OK;
+    if (!use_strip(C, esize_of(dtype))) return EDGL_OK;
     return edgl_strip_label_scatter(rows, labels, coef, nvalid, R, C, i0, i1, gscale, d_table, d_bias, (hipStream_t)stream);
 }
 // edgl_score_flash_label_term as an ordered sum over a sorted plan (k_segsum.hip): no f32 atomics, one writer per table row, the
 // same no-op where the product pass already contains the one-hot term (EasyDGL.py:177-185).
-int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
-                      const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype, hipStream_t st);
 extern "C" int edgl_score_flash_label_term_det(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C,
                                                int I, int i0, int i1, const int32_t* nvalid, float* d_table, float* d_bias, void* plan,
                                                int dtype, void* stream) {
     EDGL_REQUIRE(rows && labels && coef && d_table && d_bias && plan, EDGL_ERR_NULL, "edgl_score_flash_label_term_det: null pointer");
     EDGL_REQUIRE(R > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1, EDGL_ERR_SHAPE, "edgl_score_flash_label_term_det: bad shape");
     EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_score_flash_label_term_det: bad dtype %d", dtype);
-    if (!use_strip(C, dtype == EDGL_BF16 ? 2 : 4)) return EDGL_OK;
+    if (!use_strip(C, esize_of(dtype))) return EDGL_OK;
     return edgl_segsum_label(rows, labels, coef, gscale, R, C, I, i0, i1, nvalid, d_table, d_bias, plan, dtype, (hipStream_t)stream);
-}
-extern "C" int edgl_score_flash_bwd_ex(const void* rows, const void* table, const float* out_bias, const int64_t* labels,
-                                       const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int i0,
-                                       int i1, const int32_t* nvalid, void* d_rows, float* d_table, float* d_bias,
-                                       float* workspace, int defer_label_term, int dtype, void* stream) {
-    int rc = check_score(rows, table, out_bias, R, C, I, i0, i1, dtype, "edgl_score_flash_bwd");
-    if (rc) return rc;
-    // d_rows == NULL: the rows were finished by edgl_score_flash_fwd_rows_w; only d_table / d_bias are computed
-    EDGL_REQUIRE(labels && row_lse && coef && d_table && d_bias && workspace, EDGL_ERR_NULL,
-                 "edgl_score_flash_bwd: null pointer");
-    ScoreP p{};
-    p.rows = rows; p.table = table; p.out_bias = out_bias; p.labels = labels; p.R = R; p.C = C; p.I = I; p.i0 = i0;
-    p.i1 = i1; p.nvalid = nvalid; p.row_lse = const_cast<float*>(row_lse); p.coef = coef; p.gscale = gscale;
-    p.defer_label = (defer_label_term & 1) != 0;
-    p.acc_atomic = (defer_label_term & 2) != 0;      // (bf16, C = 128 strip path only; elsewhere the slabs)
-    p.keep_slabs = (defer_label_term & 4) != 0 && (defer_label_term & 1) != 0 && !gscale && i0 == 0 && i1 == I;
-    const BwdPlan plan = bwd_plan(R, C, I, i1 - i0, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_F32 ? bwd_dispatch<float, 2>(p, C, plan, workspace, d_rows, d_table, d_bias, st)
-                             : bwd_dispatch<bf16, 2>(p, C, plan, workspace, d_rows, d_table, d_bias, st);
 }
 
 // Where edgl_score_flash_bwd_ex(defer_label_term & 4) leaves the partial table / bias gradients: out[0] / out[1] = float offsets of the
 // [nslab][I * C] and [nslab][I - 1] slabs inside the flash workspace, out[2] = nslab.  Depends on the shape only.
 extern "C" int edgl_score_flash_slab_info(int R, int C, int I, int n_items, int dtype, long* out) {
     EDGL_REQUIRE(out && (dtype == EDGL_F32 || dtype == EDGL_BF16), EDGL_ERR_NULL, "edgl_score_flash_slab_info: bad arguments");
-    const BwdPlan plan = bwd_plan(R, C, I, n_items, dtype == EDGL_BF16 ? 2 : 4, use_strip(C, dtype == EDGL_BF16 ? 2 : 4));
+    const BwdPlan plan = plan_of(R, C, I, n_items, dtype, true);
     out[0] = plan.off_slabW; out[1] = plan.off_slabB; out[2] = plan.w.nchunk;
-    return EDGL_OK;
-}
-
-extern "C" int edgl_mask_topk(float* logits, int R, int n, int i0, const int64_t* seen, int T, int K, float* out_val,
-                              int32_t* out_idx, void* stream) {
-    EDGL_REQUIRE(logits && out_val && out_idx, EDGL_ERR_NULL, "edgl_mask_topk: null pointer");
-    EDGL_REQUIRE(R > 0 && n > 0 && K > 0 && K <= 128, EDGL_ERR_SHAPE, "edgl_mask_topk: bad shape R=%d n=%d K=%d", R, n, K);
-    static const int reg_form = edgl_env_int("EDGL_TOPK_REG", 1);
-    hipStream_t st = (hipStream_t)stream;
-    if (reg_form && n <= 256 * 16 - 8) hipLaunchKernelGGL(mask_topk_reg_kernel<16>, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);
-    else if (reg_form && n <= 256 * 40 - 8) hipLaunchKernelGGL(mask_topk_reg_kernel<40>, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);
-    else if (reg_form && n <= 256 * 80 - 8) hipLaunchKernelGGL(mask_topk_reg_kernel<80>, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);
-    else hipLaunchKernelGGL(mask_topk_kernel, dim3(R), dim3(256), 0, st, logits, R, n, i0, seen, T, K, out_val, out_idx);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-
-extern "C" int edgl_topk_merge(const float* cand_val, const int32_t* cand_idx, int S, int R, int K, float* out_val,
-                               int32_t* out_idx, void* stream) {
-    EDGL_REQUIRE(cand_val && cand_idx && out_val && out_idx, EDGL_ERR_NULL, "edgl_topk_merge: null pointer");
-    EDGL_REQUIRE(S > 0 && R > 0 && K > 0 && S * K <= 1024, EDGL_ERR_SHAPE, "edgl_topk_merge: S*K=%d > 1024", S * K);
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, cand_val, cand_idx, S, R, K, out_val, out_idx,
-                       (const int32_t*)nullptr);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-// the merge over appended candidate lists (k_eval_topk.hip)
-int edgl_topk_merge_counted(const float* cand_val, const int32_t* cand_idx, const int32_t* counts, int S, int R, int K, float* out_val,
-                            int32_t* out_idx, hipStream_t st) {
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(R), dim3(256), 0, st, cand_val, cand_idx, S, R, K, out_val, out_idx, counts);
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
-}
-
-extern "C" int edgl_rank_metrics(const int32_t* topk_idx, int R, int K, const int64_t* label, float* metrics, void* stream) {
-    EDGL_REQUIRE(topk_idx && label && metrics, EDGL_ERR_NULL, "edgl_rank_metrics: null pointer");
-    hipLaunchKernelGGL(rank_metrics_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, topk_idx, R, K, label, metrics);
-    EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

@@ -1,4 +1,4 @@
-// Per-row top-K selection shared by k_score.hip (K6: mask_topk_kernel) and k_eval_topk.hip (the exact fallback of the fused
+// Per-row top-K selection shared by k_eval_tile.hip (K6: mask_topk_kernel) and k_eval_topk.hip (the exact fallback of the fused
 // evaluation scoring): Base.py:181 tf.nn.top_k — descending, ties to the lower index; -0.0 and +0.0 tie.
 #pragma once
 #include "edgl_common.h"

@@ -948,6 +948,44 @@ def test_score_flash_matches_the_two_pass_kernels(name, dt, tol, R_, C, I):
     assert float(loss1) == float(loss2)
 
 
+def test_score_flash_fwd_pre_with_a_prepared_table_matches_flash_fwd():
+    """edgl_score_prepare_table + edgl_score_flash_fwd_pre(table_ready = 1) against edgl_score_flash_fwd: the transposed table
+    image written ahead of time is the one the forward writes itself (f32 — the dtype that reads it), so lse, label logits and
+    the three gradients of the edgl_score_flash_bwd that follows are the same bits."""
+    from easydgl_amd._lib import F32, check, lib
+    o = ops()
+    R_, C, I = 24, 32, 41
+    rng = np.random.default_rng(5)
+    rows = torch.tensor(_rand((R_, C), rng, 0.6), dtype=torch.float32).cuda()
+    tab = torch.tensor(_rand((I, C), rng, 0.4), dtype=torch.float32).cuda()
+    bias = torch.tensor(_rand((I - 1,), rng, 0.3), dtype=torch.float32).cuda()
+    labels = rng.integers(1, I, size=R_)
+    labels[[2, 3, 11, 23]] = 0
+    rows_c, lab_c, _perm, _inv, nvalid = o.compact_rows(rows, torch.tensor(labels, dtype=torch.int64).cuda())
+    assert int(nvalid.item()) == R_ - 4
+    p, st = o._ptr, o._stream()
+    outs = []
+    for prepared in (False, True):
+        ws = torch.zeros(lib.edgl_score_flash_workspace(R_, C, I, I, F32), device="cuda")
+        lse = torch.zeros(R_, device="cuda"); ll = torch.zeros(R_, device="cuda")
+        if prepared:
+            check(lib.edgl_score_prepare_table(p(tab), R_, C, I, 0, I, p(ws), F32, st), "edgl_score_prepare_table")
+            check(lib.edgl_score_flash_fwd_pre(p(rows_c), p(tab), p(bias), p(lab_c), R_, C, I, 0, I, p(nvalid), p(lse), p(ll), p(ws), 1, F32,
+                                               st), "edgl_score_flash_fwd_pre")
+        else:
+            check(lib.edgl_score_flash_fwd(p(rows_c), p(tab), p(bias), p(lab_c), R_, C, I, 0, I, p(nvalid), p(lse), p(ll), p(ws), F32, st),
+                  "edgl_score_flash_fwd")
+        loss = torch.zeros(1, device="cuda"); coef = torch.zeros(R_, device="cuda")
+        check(lib.edgl_ce_loss_fwd(p(lse), p(ll), p(lab_c), R_, p(loss), p(coef), st), "edgl_ce_loss_fwd")
+        d_rows = torch.zeros_like(rows_c); d_tab = torch.zeros((I, C), device="cuda"); d_b = torch.zeros(I - 1, device="cuda")
+        check(lib.edgl_score_flash_bwd(p(rows_c), p(tab), p(bias), p(lab_c), p(lse), p(coef), None, R_, C, I, 0, I, p(nvalid), p(d_rows),
+                                       p(d_tab), p(d_b), p(ws), F32, st), "edgl_score_flash_bwd")
+        outs.append((lse[:R_ - 4], ll, d_rows, d_tab, d_b))
+    for what, a, b in zip(("lse", "label logits", "d_rows", "d_table", "d_bias"), *outs):
+        assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0, what
+        assert torch.equal(a, b), what
+
+
 def test_deferred_reductions_match_the_immediate_ones():
     """edgl_reduce_defer(1) ... edgl_reduce_flush: one launch for every queued slab reduction — the column form for the few row
     splits of a weight-gradient GEMM (2-24 slabs), the row-lane form for deep lists (one partial row per sample of a LayerNorm
