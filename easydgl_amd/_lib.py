@@ -46,6 +46,8 @@ SIGNATURES = {
     "edgl_encode_bwd_add_ct": (I, [P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, I, P]),
     "edgl_encode_bwd_label_fused": (I, [I, I]),
     "edgl_encode_bwd_add_label": (I, [P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, P, P, P, P, I, P, I, P]),
+    "edgl_dx_encode_supported": (I, [I, I, I, I]),
+    "edgl_dx_encode_bwd_label": (I, [P, P, I, I, P, P, P, P, P, I, I, I, I, I, F, P, U32, P, P, P, P, I, P, P, P, P, I, P, I, P]),
     "edgl_segsum_passes": (I, [I]),
     "edgl_segsum_plan_bytes": (L, [I, I]),
     "edgl_segsum_plan": (I, [P, I, P, I, I, I, P, P]),

@@ -5,8 +5,11 @@
 #include "edgl_common.h"
 #include "batch_prep.h"
 #include "red_batch.h"
+#include "encode_scatter.h"
 
 namespace {
+
+using namespace enc_scatter;
 
 struct EncP {
     const int64_t* ids; const float* ts; const void* item_tab; const float* pos_tab; const float* mark_emb;
@@ -158,22 +161,6 @@ __global__ __launch_bounds__(256) void encode_prep_kernel(EncP p, PrepP q) {
     }
 }
 
-struct EncBwdP {
-    const int64_t* ids; const uint8_t* marks; const void* dx0;
-    int B, T, C, E, I; float rate; const uint64_t* rng; uint32_t stream_id;
-    float* d_item; float* part_pos; float* part_mk; int nchunk;
-    int srows;
-    const void* add1; const void* add2;   // optional [B*T, C] terms added to the item section of dX0 (residual branches)
-    float sq;             // sqrt(true model width): coding.py:62-63 (== sqrt(C) without channel padding)
-    // Optional second job of the MFMA scatter launch (encode_scatter_mfma_kernel): the one-hot term of the tied table's scoring
-    // gradient, d_table[label[r]] -= coef[r] rows[r], d_bias[label[r] - 1] -= coef[r] over the weighted rows (Appendix C; what
-    // edgl_score_flash_label_term applies as a launch of its own) — the same segmented sum over equal ids, on blocks behind the
-    // embedding's: lab_blk0 = first such block (0: none)
-    const void* lab_rows; const int64_t* lab_ids; const float* lab_coef; const int32_t* lab_nvalid; int lab_R; int lab_blk0;
-    float* d_bias;
-    int red_blk0;         // first workgroup of the reduction list that rides in the MFMA scatter launch (RedBatch::blocks of them; 0: in front)
-    float* d_mark_zero;   // [E*C]: cleared by block (0, 0) of the position / mark stage (only row 1 is ever written afterwards)   // rows per block of the scatter stage (<= SROWS; fewer when SROWS*C floats exceed the LDS)
-};
 
 // d_pos / d_mark: grid (T, nchunk): the block owns position t for the b-range of its chunk.  Thread = 4
 // consecutive channels of the position and mark sections (8/16-byte loads); 256/(C/4) rows in flight; block
@@ -243,7 +230,6 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(EncBwdP p) {
 // block takes SROWS consecutive (b,t) rows, finds for every row the first row of the block with the same id
 // (its "leader"), accumulates into LDS (ds_add_f32) per leader, and issues ONE global atomic per distinct id
 // and channel — the hottest row receives (#blocks) adds instead of (#tokens).
-constexpr int SROWS = 128;
 template <typename T>
 __global__ __launch_bounds__(256) void encode_scatter_kernel(EncBwdP p) {
     extern __shared__ float acc[];  // [SROWS][C]
@@ -334,13 +320,6 @@ __global__ __launch_bounds__(256) void encode_scatter_kernel(EncBwdP p) {
 // replaces 64 KB of LDS zeroing, 64 LDS atomics per thread and a 64-trip read-out loop (the kernel took 65 us with the
 // global atomics compiled out: they were never the limit) by 64 MFMAs per wave; the block's sums are formed in one fixed
 // order.  Leaders then add their rows to the table gradient straight from the accumulator registers.
-typedef __attribute__((ext_vector_type(4))) short enc_s16x4;
-__device__ __forceinline__ uint2 enc_tr_read(const bf16* tile, int ld, int k0, int z0, int lane) {
-    const int G = lane >> 4, s = lane & 15;
-    const bf16* p = tile + (k0 + 4 * G + (s >> 2)) * ld + z0 + 4 * (s & 3);
-    enc_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) enc_s16x4*)p);
-    return *reinterpret_cast<uint2*>(&v);
-}
 // CT = channel tiles of one workgroup's slice (C = 16 CT channels starting at blockIdx.y * C of the p.C-wide rows: the 256 / 512-unit
 // recipes run as 2 / 4 slices of 128)
 // Third job of the launch (edgl_reduce_ride; gridDim.y == 1 only): the deferred partial reductions of the backward, rb.blocks
@@ -349,7 +328,6 @@ __device__ __forceinline__ uint2 enc_tr_read(const bf16* tile, int ld, int k0, i
 template <int CT>
 __global__ __launch_bounds__(256) void encode_scatter_mfma_kernel(EncBwdP p, RedBatch rb) {
     constexpr int C = 16 * CT, LDG = C + 8, SR = SROWS;
-    const int CF = p.C, coff = (int)blockIdx.y * C;      // full row width, first channel of this slice
     __shared__ __attribute__((aligned(16))) bf16 Gs[SR * LDG];   // masked gradient rows of the block
     __shared__ __attribute__((aligned(16))) int s_id[SR];
     __shared__ __attribute__((aligned(16))) int s_lead[SR];       // first row with the same id; -1: padding / past the end
@@ -358,124 +336,10 @@ __global__ __launch_bounds__(256) void encode_scatter_mfma_kernel(EncBwdP p, Red
         reduce_rows_vec_block(rb, (int)blockIdx.x - p.red_blk0, reinterpret_cast<float4(*)[9]>(Gs));
         return;
     }
-    const int bx = (int)blockIdx.x - (p.red_blk0 == 0 ? rb.blocks : 0);      // workgroup index among the scatter's own
-    // label job (block-uniform): rows = the compacted head rows, ids = their labels, every row scaled by its loss coefficient
-    const bool lab = p.lab_blk0 > 0 && bx >= p.lab_blk0;
-    const long rows = lab ? (long)(p.lab_nvalid ? min(p.lab_R, p.lab_nvalid[0]) : p.lab_R) : (long)p.B * p.T;
-    const long r0 = (long)(bx - (lab ? p.lab_blk0 : 0)) * SR;
-    if (lab && r0 >= rows) return;
     __shared__ float s_cf[SR], s_cb[SR];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, G = lane >> 4, g4 = G * 4, l15 = lane & 15;
-    if (tid < SR) {
-        const bool in = r0 + tid < rows;
-        if (lab) {
-            const float cf = in ? p.lab_coef[r0 + tid] : 0.f;
-            s_id[tid] = (in && cf != 0.f) ? (int)p.lab_ids[r0 + tid] : 0;      // label 0: weight 0 (EasyDGL.py:180)
-            s_cf[tid] = cf;
-            s_cb[tid] = 0.f;
-        } else {
-            s_id[tid] = in ? (int)p.ids[r0 + tid] : 0;
-        }
-    }
-    // gradient fragments of this thread's rows, all in flight before anything else (rows clamped)
-    constexpr int cpr = C / 4, rows_par = 256 / cpr, NR = SR / rows_par;
-    const int cv = tid % cpr, rl = tid / cpr, c0 = cv * 4;
-    const bf16* dx0 = reinterpret_cast<const bf16*>(lab ? p.lab_rows : p.dx0);
-    const long ldrow = lab ? CF : 3 * CF;
-    const bool adds = p.add1 && !lab;
-    Frag4<bf16> g[NR], ga[NR], gb[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const long row = min(r0 + rl + (long)k * rows_par, rows - 1);
-        g[k] = frag_ld<bf16>(dx0 + row * ldrow + coff + c0);
-        if (adds) {
-            ga[k] = frag_ld<bf16>(reinterpret_cast<const bf16*>(p.add1) + row * CF + coff + c0);
-            gb[k] = frag_ld<bf16>(reinterpret_cast<const bf16*>(p.add2) + row * CF + coff + c0);
-        }
-    }
-    __syncthreads();
-    if (tid < SR) {
-        const int id = s_id[tid];
-        int lead = tid;
-        for (int j4 = (tid >> 2); j4 >= 0; --j4) {
-            const int4 v = *reinterpret_cast<const int4*>(s_id + 4 * j4);
-            const int j = 4 * j4;
-            if (v.w == id && j + 3 < tid) lead = j + 3;
-            if (v.z == id && j + 2 < tid) lead = j + 2;
-            if (v.y == id && j + 1 < tid) lead = j + 1;
-            if (v.x == id && j < tid) lead = j;
-        }
-        s_lead[tid] = id == 0 ? -1 : lead;
-        if (lab && id != 0 && blockIdx.y == 0) atomicAdd(&s_cb[lead], s_cf[tid]);     // bias term of the leader's label
-    }
-    const DropKey dk = make_dropkey(p.rng, p.stream_id, p.rate);
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const int r = rl + k * rows_par;
-        const long row = r0 + r;
-        Frag4<bf16> v = g[k];
-        if (adds) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v.v[j] = from_f32<bf16>(to_f32(v.v[j]) + to_f32(ga[k].v[j]) + to_f32(gb[k].v[j]));
-        }
-        if (lab) {   // coef[r] * rows[r], rounded to the operand dtype of the segmented sum (as the product pass rounds its P)
-            const float cf = s_cf[r];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v.v[j] = from_f32<bf16>(cf * to_f32(v.v[j]));
-        } else if (dk.thresh != 0u) {
-            const uint32_t keep = drop_keep4(dk, (uint64_t)row * 3 * CF + coff + c0);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (!((keep >> j) & 1u)) v.v[j] = from_f32<bf16>(0.f);
-        }
-        *reinterpret_cast<uint2*>(Gs + r * LDG + c0) = *reinterpret_cast<const uint2*>(&v);
-    }
-    __syncthreads();
-    // wave w: leaders [32 w, 32 w + 32) x all channels
-    f32x4 acc[2][CT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) acc[mt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bf16 one = from_f32<bf16>(1.f), zero = from_f32<bf16>(0.f);
-#pragma unroll
-    for (int kb = 0; kb < SR / 32; ++kb) {
-        // k-slot order of the transpose-read fragments: slots 0-3 <-> row 32 kb + 4G + j, slots 4-7 <-> 32 kb + 16 + 4G + j
-        const int4 la = *reinterpret_cast<const int4*>(s_lead + kb * 32 + g4);
-        const int4 lb = *reinterpret_cast<const int4*>(s_lead + kb * 32 + 16 + g4);
-        const int lk[8] = {la.x, la.y, la.z, la.w, lb.x, lb.y, lb.z, lb.w};
-        bf16x8 af[2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const int lead = wave * 32 + mt * 16 + l15;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) af[mt][i] = lk[i] == lead ? one : zero;
-        }
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            bf16x8 bfr;
-            *reinterpret_cast<uint2*>(&bfr) = enc_tr_read(Gs, LDG, kb * 32, ct * 16, lane);
-            *(reinterpret_cast<uint2*>(&bfr) + 1) = enc_tr_read(Gs, LDG, kb * 32 + 16, ct * 16, lane);
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) acc[mt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], bfr, acc[mt][ct], 0, 0, 0);
-        }
-    }
-    // acc[mt][ct][r] = sum for leader 32 w + 16 mt + 4G + r, channel 16 ct + l15
-    const float sqs = lab ? -1.0f : p.sq * dk.scale;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int lead = wave * 32 + mt * 16 + g4 + r;
-            if (s_lead[lead] != lead) continue;   // not a leader (or padding)
-            float* dst = p.d_item + (long)s_id[lead] * CF + coff + l15;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) atomicAdd(dst + ct * 16, sqs * acc[mt][ct][r]);
-        }
-    if (lab && blockIdx.y == 0 && tid < SR && s_lead[tid] == tid) atomicAdd(p.d_bias + s_id[tid] - 1, -s_cb[tid]);
+    // workgroup index among the scatter's own; the body is shared with the QKVT dX GEMM's epilogue (encode_scatter.h)
+    scatter_block<CT>(p, (int)blockIdx.x - (p.red_blk0 == 0 ? rb.blocks : 0), (int)blockIdx.y, Gs, s_id, s_lead, s_cf, s_cb);
 }
-
-constexpr int ENC_NCHUNK = 16;
 
 }  // namespace
 

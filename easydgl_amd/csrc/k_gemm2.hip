@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "edgl_common.h"
+#include "encode_scatter.h"
 
 typedef __attribute__((ext_vector_type(4))) short tr_s16x4;
 
@@ -459,25 +460,42 @@ constexpr int G_LDO = G_BN + 8;      // output staging [128][128]
 // EPI = false: bias-only epilogue, bf16 output staged through LDS.  EPI = true: every epilogue of epi_store4 (GELU / ReLU with
 // the saved pre-activation, x GELU', accumulate, f32 output) written straight from the accumulator fragments (8 / 16 bytes per
 // lane) — the wide layers of the 512-unit recipes (K = 1024 / 1536 / 2048), which the register-strip kernels (K <= 512) do not take.
-template <bool B_KC, bool EPI = false>
-__global__ __launch_bounds__(G_NT, EPI ? 2 : 3) void tile_nn_kernel(StripP p) {
+//
+// MAP (the QKVT dX of the first block with the embedding backward as its epilogue, dx_encode_kernel): a row tile holds 128 SAMPLES at
+// one position t instead of 128 consecutive (b, t) rows — tile (chunk c, position t, column third j) <-> rows r = 0..127 <-> sample
+// b = 128 c + r, global row b T + t; samples past the batch are clamped for the loads and are padding behind them.  Virtual ids run
+// j fastest (the thirds of a row tile share an XCD's L2), then t, then c: the tiles in flight consume one chunk's contiguous rows.
+// The d_pos / d_mark sums over the batch are then column sums inside a tile, and the finished bf16 tile in Os is the row image of the
+// item scatter; dX0 itself is stored only on request (x.dx0_out).
+struct DxEncP {
+    enc_scatter::EncBwdP e;
+    int mapT, mapB;             // T, B of the row map
+    int gemm_blocks;            // workgroups of the GEMM (padded to a multiple of 8); behind them: lab_blocks of the label job, then the riding reductions
+    int lab_blocks;
+    bf16* dx0_out;
+};
+__device__ __forceinline__ void dx_encode_epilogue(const DxEncP& x, bf16* Os, int mb0, int mt, int jn, int n0, int ldc);
+
+template <bool B_KC, bool EPI, bool MAP>
+__device__ __forceinline__ void tile_nn_tile(const StripP& p, const int vid, char* smem, const DxEncP* x) {
     constexpr int A_EL = G_BM * G_LDK, B_EL = B_KC ? G_BN * G_LDK : G_BK * G_LDN;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     bf16* As = reinterpret_cast<bf16*>(smem);                 // [2][A_EL]
     bf16* Bs = As + (EPI ? 2 : 1) * A_EL;                      // [buffers][B_EL]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
     const int G = lane >> 4, g4 = G * 4, l15 = lane & 15;
-    // consecutive workgroups share the row block (its A rows stay in L2 across the N / 128 column tiles)
+    // consecutive virtual ids share the row block (its A rows stay in L2 across the N / 128 column tiles)
     const int nbn = p.N / G_BN;
-    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, ((p.M + G_BM - 1) / G_BM) * nbn);
-    if (vid < 0) return;
     const int m0 = (vid / nbn) * G_BM, n0 = (vid % nbn) * G_BN;
+    const int mapT = MAP ? x->mapT : 1, mapB = MAP ? x->mapB : 0;
+    const int mt = MAP ? (vid / nbn) % mapT : 0, mb0 = MAP ? (vid / nbn) / mapT * G_BM : 0;
+    // global row of tile row R, clamped into the matrix
+#define G_AROW(R) (MAP ? (long)min(mb0 + (R), mapB - 1) * mapT + mt : (long)min(m0 + (R), p.M - 1))
     uint4 pa0, pa1, pa2, pa3, pb0, pb1, pb2, pb3;   // named registers (arrays captured by a lambda end up in scratch here)
     // piece v of an operand tile: A (and B when k-contiguous): row v >> 3, k offset (v & 7) * 8; B n-contiguous: k row v >> 4, n offset (v & 15) * 8
 #define G_LOAD_ONE(PA, PB, I)                                                                                                  \
     {                                                                                                                          \
         const int v = tid + (I) * G_NT, ar = v >> 3, ac = (v & 7) * 8;                                                         \
-        PA = *reinterpret_cast<const uint4*>(p.A + (long)min(m0 + ar, p.M - 1) * p.lda + k0_ + ac);                            \
+        PA = *reinterpret_cast<const uint4*>(p.A + G_AROW(ar) * p.lda + k0_ + ac);                            \
         if constexpr (B_KC) PB = *reinterpret_cast<const uint4*>(p.B + (long)(n0 + ar) * p.ldb + k0_ + ac);                    \
         else PB = *reinterpret_cast<const uint4*>(p.B + (long)(k0_ + (v >> 4)) * p.ldb + n0 + (v & 15) * 8);                   \
     }
@@ -562,16 +580,159 @@ __global__ __launch_bounds__(G_NT, EPI ? 2 : 3) void tile_nn_kernel(StripP p) {
         }
     }
     lds_barrier();
+    if constexpr (MAP) {
+        dx_encode_epilogue(*x, Os, mb0, mt, vid % nbn, n0, p.ldc);
+        return;
+    }
     bf16* C = reinterpret_cast<bf16*>(p.C);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int v = tid + i * G_NT, r = v >> 4, cpc = (v & 15) * 8;   // 128 rows x 16 pieces
         if (m0 + r < p.M) *reinterpret_cast<uint4*>(C + (long)(m0 + r) * p.ldc + n0 + cpc) = *reinterpret_cast<const uint4*>(Os + r * G_LDO + cpc);
     }
+#undef G_AROW
 #undef G_LOAD_ONE
 #undef G_LOAD
 #undef G_STORE_ONE
 #undef G_STORE
+}
+
+template <bool B_KC, bool EPI = false>
+__global__ __launch_bounds__(G_NT, EPI ? 2 : 3) void tile_nn_kernel(StripP p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int vid = xcd_virtual_id((int)blockIdx.x, (int)gridDim.x, ((p.M + G_BM - 1) / G_BM) * (p.N / G_BN));
+    if (vid < 0) return;
+    tile_nn_tile<B_KC, EPI, false>(p, vid, smem, nullptr);
+}
+
+// Epilogue of one mapped tile (128 samples at position mt, column third jn of dX0 = item | position | mark section), from the bf16
+// tile in Os — the values edgl_gemm would have stored.  LDS behind the tile: s_id, s_lead (int[128]), two float[128].
+constexpr int DXE_LDS = G_BM * G_LDO * (int)sizeof(bf16) + 4 * enc_scatter::SROWS * 4;
+__device__ __forceinline__ void dx_encode_epilogue(const DxEncP& x, bf16* Os, int mb0, int mt, int jn, int n0, int ldc) {
+    using namespace enc_scatter;
+    static_assert(G_LDO == 128 + 8 && G_BM == SROWS, "the output tile is the scatter's row image");
+    constexpr int C = 128;
+    const EncBwdP& e = x.e;
+    int* s_id = reinterpret_cast<int*>(Os + G_BM * G_LDO);
+    int* s_lead = s_id + SROWS;
+    float* s_nm = reinterpret_cast<float*>(s_lead + SROWS);
+    const int tid = threadIdx.x, T = x.mapT, B = x.mapB;
+    if (x.dx0_out) {      // (block-uniform) dX0 as edgl_gemm stores it, whole 256-byte row segments
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int v = tid + i * G_NT, r = v >> 4, cpc = (v & 15) * 8;
+            if (mb0 + r < B) *reinterpret_cast<uint4*>(x.dx0_out + ((long)(mb0 + r) * T + mt) * ldc + n0 + cpc) = *reinterpret_cast<const uint4*>(Os + r * G_LDO + cpc);
+        }
+        lds_barrier();
+    }
+    // thread = 4 consecutive channels x row lane rl: rows rl, rl + 8, ...
+    const int rl = tid >> 5, c0 = (tid & 31) * 4;
+    const DropKey dk = make_dropkey(e.rng, e.stream_id, e.rate);
+    if (jn == 0) {
+        // ---- item section: + residual rows, dropout keep bits, segmented sum over equal ids, atomics of the leaders -------------
+        if (tid < SROWS) s_id[tid] = mb0 + tid < B ? (int)e.ids[(long)(mb0 + tid) * T + mt] : 0;
+        const bool adds = e.add1 != nullptr;
+        Frag4<bf16> ga[16], gb[16];
+        if (adds) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const long row = (long)min(mb0 + rl + 8 * k, B - 1) * T + mt;
+                ga[k] = frag_ld<bf16>(reinterpret_cast<const bf16*>(e.add1) + row * C + c0);
+                gb[k] = frag_ld<bf16>(reinterpret_cast<const bf16*>(e.add2) + row * C + c0);
+            }
+        }
+        lds_barrier();
+        if (tid < SROWS) {
+            const int lead = scatter_leader(s_id, tid);
+            s_lead[tid] = s_id[tid] == 0 ? -1 : lead;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int r = rl + 8 * k;
+            const long row = (long)(mb0 + r) * T + mt;      // (rows past the batch: id 0, their values are never summed)
+            Frag4<bf16> v;
+            *reinterpret_cast<uint2*>(&v) = *reinterpret_cast<const uint2*>(Os + r * G_LDO + c0);
+            if (adds) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v.v[j] = from_f32<bf16>(to_f32(v.v[j]) + to_f32(ga[k].v[j]) + to_f32(gb[k].v[j]));
+            }
+            if (dk.thresh != 0u) {
+                const uint32_t keep = drop_keep4(dk, (uint64_t)row * 3 * C + c0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (!((keep >> j) & 1u)) v.v[j] = from_f32<bf16>(0.f);
+            }
+            *reinterpret_cast<uint2*>(Os + r * G_LDO + c0) = *reinterpret_cast<const uint2*>(&v);
+        }
+        lds_barrier();
+        scatter_onehot_sum<8>(Os, s_id, s_lead, e.d_item, C, 0, e.sq * dk.scale);
+        return;
+    }
+    // ---- position / mark section: masked column sums over the valid samples, fixed order --------------------------------------
+    if (jn == 2) {
+        if (mb0 == 0 && mt == 0 && e.d_mark_zero)
+            for (int i = tid; i < e.E * C; i += G_NT) e.d_mark_zero[i] = 0.f;
+        if (tid < SROWS) {
+            int nm = 0;
+            if (mb0 + tid < B) {
+                const uint8_t* mrow = e.marks + ((long)(mb0 + tid) * T + mt) * e.E;
+                for (int q = 0; q < e.E; ++q) nm += mrow[q];
+            }
+            s_nm[tid] = (float)nm;
+        }
+        lds_barrier();
+    }
+    // (f64 inside the tile — 64 adds per thread: a tile's 128 rows leave ONE rounding in its f32 partial, where the unfused kernels'
+    // chunks of 8 samples leave one per 8 rows: the sums of this form are then no further from the exact ones than the old form's)
+    double a[4] = {0., 0., 0., 0.};
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int r = rl + 8 * k;
+        if (mb0 + r < B) {
+            const long row = (long)(mb0 + r) * T + mt;
+            Frag4<bf16> g;
+            *reinterpret_cast<uint2*>(&g) = *reinterpret_cast<const uint2*>(Os + r * G_LDO + c0);
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = to_f32(g.v[j]);
+            drop_apply4(dk, (uint64_t)row * 3 * C + jn * C + c0, v);
+            const double w = jn == 2 ? (double)s_nm[r] : 1.;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] += w * (double)v[j];
+        }
+    }
+    lds_barrier();      // every read of the tile is done: the row lanes' sums go over it
+    double* sm = reinterpret_cast<double*>(Os);      // [8][C]
+    *reinterpret_cast<double2*>(sm + rl * C + c0) = make_double2(a[0], a[1]);
+    *reinterpret_cast<double2*>(sm + rl * C + c0 + 2) = make_double2(a[2], a[3]);
+    lds_barrier();
+    if (tid < C) {
+        double s = 0.;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s += sm[i * C + tid];
+        float* part = jn == 1 ? e.part_pos : e.part_mk;
+        part[((long)(mb0 / G_BM) * T + mt) * C + tid] = (float)s;
+    }
+}
+
+// The mapped QKVT dX GEMM with the embedding backward in its epilogue; behind the GEMM's workgroups (block-uniform branch): the label
+// job of the scatter (x.lab_blocks workgroups), then the riding reduction list (rb.blocks).
+__global__ __launch_bounds__(G_NT, 3) void dx_encode_kernel(StripP p, DxEncP x, RedBatch rb) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int bid = (int)blockIdx.x;
+    if (bid >= x.gemm_blocks) {
+        const int e = bid - x.gemm_blocks;
+        bf16* Gs = reinterpret_cast<bf16*>(smem);
+        int* s_id = reinterpret_cast<int*>(Gs + G_BM * G_LDO);
+        if (e < x.lab_blocks)
+            enc_scatter::scatter_block<8>(x.e, x.e.lab_blk0 + e, 0, Gs, s_id, s_id + 128, reinterpret_cast<float*>(s_id + 256), reinterpret_cast<float*>(s_id + 384));
+        else
+            reduce_rows_vec_block(rb, e - x.lab_blocks, reinterpret_cast<float4(*)[9]>(smem));
+        return;
+    }
+    const int vid = xcd_virtual_id(bid, x.gemm_blocks, (x.mapB + G_BM - 1) / G_BM * x.mapT * (p.N / G_BN));
+    if (vid < 0) return;
+    tile_nn_tile<true, false, true>(p, vid, smem, &x);
 }
 
 template <bool B_KC, bool EPI = false>
@@ -947,6 +1108,70 @@ int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int
     EDGL_LAUNCH_CHECK();
     const int rc = tn_reduce(workspace, splits, C, Kf, N, dbias, accumulate, st);
     return rc ? rc : 1;
+}
+
+// ---- QKVT dX GEMM of the first block + embedding backward + label term in one launch -----------------------------------------------
+// 1 iff the fused form exists for the shape: bf16, C = 128, at most 16 chunks of 128 samples, and the padding of the last chunk
+// (samples past the batch, computed and dropped) at most B / 8 rows
+extern "C" int edgl_dx_encode_supported(int B, int T, int C, int dtype) {
+    if (dtype != EDGL_BF16 || C != 128 || B <= 0 || T <= 0) return 0;
+    const int chunks = (B + G_BM - 1) / G_BM;
+    return chunks <= enc_scatter::ENC_NCHUNK && (long)(chunks * G_BM - B) * 8 <= B ? 1 : 0;
+}
+
+// dX0[B*T, 3C] = dqkvt[B*T, 4C] . W[3C, 4C]^T (edgl_gemm's dX call of the QKVT projection: A = dqkvt, lda; Bm = W, k-contiguous, ldb)
+// consumed in the GEMM's epilogue by what edgl_encode_bwd_add_label computes from it: d_item (+ add1 / add2, dropout, label term,
+// d_bias), d_pos, d_mark_emb.  dX0 is written only when dx0_out != NULL ([B*T, 3C], bit-identical to edgl_gemm).  The thread's queued
+// reductions ride as extra workgroups (edgl_reduce_ride); the call's own two follow in one launch (queued in deferred mode without riding).
+extern "C" int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int lda, int ldb, void* dx0_out, const int64_t* ids,
+                                        const uint8_t* marks, const void* add1, const void* add2, int B, int T, int C, int E, int I,
+                                        float drop_rate, const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos,
+                                        float* d_mark_emb, float* workspace, int c_true, const void* lab_rows, const int64_t* lab_ids,
+                                        const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias, int dtype, void* stream) {
+    using namespace enc_scatter;
+    EDGL_REQUIRE(dqkvt && W && ids && marks && d_item && d_pos && d_mark_emb && workspace, EDGL_ERR_NULL, "edgl_dx_encode_bwd_label: null pointer");
+    EDGL_REQUIRE(lab_rows && lab_ids && lab_coef && d_bias && lab_R > 0, EDGL_ERR_NULL, "edgl_dx_encode_bwd_label: null label operands");
+    EDGL_REQUIRE((add1 == nullptr) == (add2 == nullptr), EDGL_ERR_NULL, "edgl_dx_encode_bwd_label: add1 / add2 go together");
+    EDGL_REQUIRE(dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_dx_encode_bwd_label: bf16 only (dtype %d): f32 takes edgl_gemm + edgl_encode_bwd_add_ct", dtype);
+    EDGL_REQUIRE(B > 0 && T > 0 && E >= 1 && I > 1 && edgl_dx_encode_supported(B, T, C, dtype), EDGL_ERR_SHAPE,
+                 "edgl_dx_encode_bwd_label: needs bf16, C = 128, <= 16 chunks of 128 samples with at most B / 8 padded (B=%d T=%d C=%d E=%d I=%d)", B, T, C, E, I);
+    EDGL_REQUIRE(c_true >= 0 && c_true <= C, EDGL_ERR_SHAPE, "edgl_dx_encode_bwd_label: true width %d exceeds C=%d", c_true, C);
+    EDGL_REQUIRE(lda >= 4 * C && ldb >= 4 * C && lda % 8 == 0 && ldb % 8 == 0, EDGL_ERR_SHAPE,
+                 "edgl_dx_encode_bwd_label: bad leading dimensions lda=%d ldb=%d", lda, ldb);
+    EDGL_REQUIRE((((uintptr_t)dqkvt | (uintptr_t)W | (uintptr_t)dx0_out) & 15) == 0 &&
+                 (((uintptr_t)lab_rows | (uintptr_t)add1 | (uintptr_t)add2) & 7) == 0, EDGL_ERR_SHAPE,
+                 "edgl_dx_encode_bwd_label: operands must be 16-byte (GEMM) / 8-byte (rows) aligned");
+    EDGL_REQUIRE(drop_rate == 0.f || rng_state, EDGL_ERR_NULL, "edgl_dx_encode_bwd_label: dropout without rng_state");
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = (B + G_BM - 1) / G_BM, nbn = 3;
+    float* part_pos = workspace;
+    float* part_mk = workspace + (long)ENC_NCHUNK * T * C;
+    DxEncP x;
+    x.e = EncBwdP{ids, marks, nullptr, B, T, C, E, I, drop_rate, rng_state, stream_id, d_item, part_pos, part_mk, chunks, SROWS, add1, add2,
+                  sqrtf((float)(c_true > 0 ? c_true : C)), lab_rows, lab_ids, lab_coef, lab_nvalid, lab_R, 1, d_bias, 0, d_mark_emb};
+    x.mapT = T; x.mapB = B;
+    x.gemm_blocks = xcd_grid(chunks * T * nbn);
+    x.lab_blocks = (lab_R + SROWS - 1) / SROWS;
+    x.dx0_out = reinterpret_cast<bf16*>(dx0_out);
+    RedBatch rb;
+    rb.n = rb.blocks = 0;
+    int first = 0;
+    const int nred = edgl_reduce_ride_take(nullptr, 0, d_item, d_item + (long)I * C, d_bias, d_bias + (I - 1), &rb, &first, st);
+    if (nred < 0) return nred;
+    StripP p{(const bf16*)dqkvt, (const bf16*)W, dx0_out, B * T, 3 * C, 4 * C, lda, ldb, 3 * C, EpiP{nullptr, nullptr, 0}};
+    const size_t smem = std::max((size_t)2 * G_BM * G_LDK * sizeof(bf16), (size_t)DXE_LDS);
+    hipFuncSetAttribute((const void*)dx_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipLaunchKernelGGL(dx_encode_kernel, dim3((unsigned)(x.gemm_blocks + x.lab_blocks + nred)), dim3(G_NT), smem, st, p, x, rb);
+    EDGL_LAUNCH_CHECK();
+    // the two reductions of this call (only row 1 of the mark-embedding table is ever indexed: EasyDGL.py:87-88)
+    const RedJob own[2] = {{part_pos, d_pos, (long)T * C, chunks, T * C, 0, 1}, {part_mk, E > 1 ? d_mark_emb + C : d_mark_emb, (long)C, chunks * T, C, 0, 1}};
+    const int nown = E > 1 ? 2 : 1;
+    if (nred > 0) return edgl_reduce_rows_now(own, nown, st);
+    for (int i = 0; i < nown; ++i) {
+        const int rc = edgl_reduce_rows_f64(own[i].part, own[i].P, own[i].N, own[i].ld, own[i].out, st);
+        if (rc) return rc;
+    }
+    return EDGL_OK;
 }
 
 #ifdef EDGL_PHASE_TIMING

@@ -799,7 +799,7 @@ inline int grid_for(long n) { return (int)std::min<long>((n + 255) / 256, 4096);
 // alive (distinct workspaces) until the flush.  Jobs that accumulate into `out` flush first and run immediately, so the
 // order of read-modify-write updates is preserved.
 static inline int red_blocks_scalar(const RedJob& j) { return (j.N + 31) / 32; }
-static inline int red_blocks_vec(const RedJob& j) { return j.P <= RED_COL_P ? (j.N + 1023) / 1024 : (j.N + 31) / 32; }
+static inline int red_blocks_vec(const RedJob& j) { return j.P <= RED_COL_P && !j.f64 ? (j.N + 1023) / 1024 : (j.N + 31) / 32; }
 static inline bool red_job_vec(const RedJob& j) {
     return (j.N & 3) == 0 && (j.ld & 3) == 0 && (((uintptr_t)j.part | (uintptr_t)j.out) & 15) == 0;
 }
@@ -882,7 +882,7 @@ int edgl_reduce_rows(const float* part, int P, int N, long ld, float* out, int a
             if (rc) return rc;
         }
         RedJob& j = g_red_batch.j[g_red_batch.n++];
-        j.part = part; j.out = out; j.ld = ld; j.P = P; j.N = N; j.blk0 = g_red_batch.blocks;
+        j.part = part; j.out = out; j.ld = ld; j.P = P; j.N = N; j.blk0 = g_red_batch.blocks; j.f64 = 0;
         g_red_batch.blocks += (N + 31) / 32;
         return EDGL_OK;
     }
@@ -929,6 +929,44 @@ int edgl_reduce_ride_take(const RedJob* own, int nown, const float* lo0, const f
     g_red_batch.n = 0;
     g_red_batch.blocks = 0;
     return blocks;
+}
+
+int edgl_reduce_rows_now(const RedJob* jobs, int n, hipStream_t st) {
+    if (n <= 0) return EDGL_OK;
+    bool vec = n <= RED_MAX_JOBS;
+    for (int i = 0; i < n && vec; ++i) vec = red_job_vec(jobs[i]);
+    if (!vec) {
+        for (int i = 0; i < n; ++i) {
+            const int rc = edgl_reduce_rows(jobs[i].part, jobs[i].P, jobs[i].N, jobs[i].ld, jobs[i].out, 0, st);
+            if (rc) return rc;
+        }
+        return EDGL_OK;
+    }
+    RedBatch b;
+    b.n = n;
+    b.blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        b.j[i] = jobs[i];
+        b.j[i].blk0 = b.blocks;
+        b.blocks += red_blocks_vec(jobs[i]);
+    }
+    hipLaunchKernelGGL(reduce_rows_multi_vec_kernel, dim3(b.blocks), dim3(256), 0, st, b);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
+int edgl_reduce_rows_f64(const float* part, int P, int N, long ld, float* out, hipStream_t st) {
+    const RedJob j{part, out, ld, P, N, g_red_batch.blocks, 1};
+    if (!red_job_vec(j)) return edgl_reduce_rows(part, P, N, ld, out, 0, st);
+    if (!g_red_defer) return edgl_reduce_rows_now(&j, 1, st);
+    if (g_red_batch.n == RED_MAX_JOBS) {
+        const int rc = edgl_reduce_flush_impl(st);
+        if (rc) return rc;
+    }
+    g_red_batch.j[g_red_batch.n] = j;
+    g_red_batch.j[g_red_batch.n++].blk0 = g_red_batch.blocks;
+    g_red_batch.blocks += (N + 31) / 32;
+    return EDGL_OK;
 }
 
 extern "C" int edgl_reduce_ride(int on) {

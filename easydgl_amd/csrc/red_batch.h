@@ -5,12 +5,19 @@
 
 constexpr int RED_MAX_JOBS = 24;
 constexpr int RED_COL_P = 32;      // jobs with at most this many partial rows run in the column form of the vector kernel
-struct RedJob { const float* part; float* out; long ld; int P, N, blk0; };
+struct RedJob { const float* part; float* out; long ld; int P, N, blk0, f64; };      // f64: the sums of the job in double precision (vector form only)
 struct RedBatch { RedJob j[RED_MAX_JOBS]; int n, blocks; };
 
 // k_misc.hip: hand the calling thread's queue (+ the caller's own jobs) to the scatter launch; 0 = nothing rides, nothing changed; < 0 = a launch failed
 int edgl_reduce_ride_take(const RedJob* own, int nown, const float* lo0, const float* hi0, const float* lo1, const float* hi1,
                           RedBatch* out, int* first_blocks, hipStream_t st);
+
+// k_misc.hip: the vector-form jobs `jobs` as ONE launch on `st` now, whatever the deferred mode holds (the reductions of a launch that
+// carried the queue itself: its own partials cannot ride with it); jobs outside the vector form go through edgl_reduce_rows
+int edgl_reduce_rows_now(const RedJob* jobs, int n, hipStream_t st);
+// k_misc.hip: edgl_reduce_rows (overwrite) with the sums formed in double precision and rounded once: for partials that are themselves
+// long sums (the 128-sample column sums of dx_encode_kernel).  Queued in deferred mode; a job outside the vector form runs in f32.
+int edgl_reduce_rows_f64(const float* part, int P, int N, long ld, float* out, hipStream_t st);
 
 // Workgroup `bid` (256 threads) of a list whose blk0 were laid out in the vector form; sm: 32 x 9 float4 (4.6 KB) of LDS.
 __device__ __forceinline__ void reduce_rows_vec_block(const RedBatch& b, int bid, float4 (*sm)[9]) {
@@ -20,6 +27,30 @@ __device__ __forceinline__ void reduce_rows_vec_block(const RedBatch& b, int bid
     const RedJob& jb = b.j[ji];
     const int P = jb.P, N = jb.N;
     const long ld = jb.ld;
+    if (jb.f64) {      // (block-uniform) row-lane layout for any P, double accumulators, two components per pass through the scratch
+        const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
+        const int n = (bid - jb.blk0) * 32 + 4 * tx;
+        double a[4] = {0., 0., 0., 0.};
+        if (n < N)
+            for (int p = ty; p < P; p += 32) {
+                const float4 v = *reinterpret_cast<const float4*>(jb.part + n + (long)p * ld);
+                a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w;
+            }
+        double2 (*sd)[9] = reinterpret_cast<double2(*)[9]>(sm);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            sd[ty][tx] = make_double2(a[2 * h], a[2 * h + 1]);
+            __syncthreads();
+            if (ty < 2 && n < N) {
+                double s = 0.;
+#pragma unroll
+                for (int i = 0; i < 32; ++i) s += ty == 0 ? sd[i][tx].x : sd[i][tx].y;
+                jb.out[n + 2 * h + ty] = (float)s;
+            }
+            __syncthreads();
+        }
+        return;
+    }
     if (P <= RED_COL_P) {
         // few partial rows (the row splits of a weight-gradient GEMM: 2-24 slabs of up to 3 M elements): a thread owns one
         // float4 column and adds its P values — 4 KB of consecutive bytes per row and workgroup, 32x fewer workgroups than the

@@ -47,6 +47,8 @@ class TrainEngine:
         EDGL_REDUCE_RIDE=0       the queued partial reductions of the backward as a launch of their own behind the embedding scatter
                                  instead of extra workgroups of its launch (edgl_reduce_ride); 2: the workgroups behind the
                                  scatter's instead of in front of them (the measured alternative, DESIGN rule 76)
+        EDGL_DX_ENCODE=0         the QKVT dX GEMM of the first block, then the embedding backward as launches of their own, instead of
+                                 the GEMM with the embedding backward in its epilogue (edgl_dx_encode_bwd_label, DESIGN rule 78)
 
     EDGL_SCORE_STRIP belongs to the library (csrc/k_score_strip.hip latches it once per process); the engine reads it at the same
     place because only the strip passes leave the one-hot term of the table gradient to the embedding scatter (`_label_fused`)."""
@@ -65,6 +67,7 @@ class TrainEngine:
         self.sw_adam_ex = env("EDGL_ADAM_EX", "1") != "0"
         self.sw_reduce_ride = env("EDGL_REDUCE_RIDE", "1") != "0"
         self.sw_reduce_ride_behind = env("EDGL_REDUCE_RIDE", "1") == "2"
+        self.sw_dx_encode = env("EDGL_DX_ENCODE", "1") != "0"
         self.sw_score_strip = env("EDGL_SCORE_STRIP", "1") != "0"      # (the library's: csrc/k_score_strip.hip latches it per process)
         self.m = model
         self.B = batch
@@ -723,6 +726,21 @@ class TrainEngine:
             if self.fused_tail:
                 check(lib.edgl_gemm_dw_defer(0, st), "edgl_gemm_dw_defer")
             d_in = self.G3c if i == 0 else self.G3
+            if i == 0 and self._label_fused and self.sw_dx_encode and not self.deterministic and cin == 3 * C and \
+                    lib.edgl_dx_encode_supported(B, T, C, code):
+                # dX0 is consumed in the epilogue of the GEMM that produces it and never written (G3c stays untouched)
+                self._issue_backward_end()
+                if self.reduce_ride:
+                    check(lib.edgl_reduce_ride(2 if self.sw_reduce_ride_behind else 1), "edgl_reduce_ride")
+                d0 = drop(hd, 1)
+                check(lib.edgl_dx_encode_bwd_label(_ptr(self.G4c), _ptr(self.m.compute(att.dense_kernel)), 4 * C, 4 * C, None,
+                                                   _ptr(self.ids), _ptr(self.marks), _ptr(self.G1), _ptr(self.G2), B, T, C, E, I,
+                                                   float(d0.rate), d0.ptr(), d0.stream_id, _ptr(tab.grad),
+                                                   _ptr(m.pcoding.pembs.lookup_table.grad), _ptr(m.mark_embs.lookup_table.grad),
+                                                   _ptr(self._ws(lib.edgl_encode_bwd_workspace(B, T, C))), self.c_true,
+                                                   _ptr(self.hrows_c), _ptr(lab), _ptr(self.coef), _ptr(self.nvalid), R,
+                                                   _ptr(m.output_bias.grad), code, st), "edgl_dx_encode_bwd_label")
+                return
             self._dense_dx(self.G4c, att.dense_kernel, d_in, cin, 4 * C)
             if i == 0:
                 self._issue_backward_end()

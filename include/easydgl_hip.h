@@ -158,6 +158,21 @@ int edgl_encode_bwd_add_label(const int64_t* ids, const uint8_t* marks, const vo
                               float* d_item, float* d_pos, float* d_mark_emb, float* workspace, int c_true, const void* lab_rows,
                               const int64_t* lab_ids, const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias,
                               int dtype, void* stream);
+/* The QKVT dX GEMM of the first block with edgl_encode_bwd_add_label as its epilogue (csrc/k_gemm2.hip: dx_encode_kernel; DESIGN
+ * rule 78): dX0[B*T, 3C] = dqkvt[B*T, 4C] . W[3C, 4C]^T — edgl_gemm's dX call (A = dqkvt with row stride lda, Bm = W k-contiguous
+ * with row stride ldb) — is consumed tile by tile where it is produced and never written: a row tile holds 128 samples at one
+ * position, so d_pos / d_mark_emb are column sums inside the tile and the item section of the tile is the row image of the scatter.
+ * The label job and the thread's queued reductions (edgl_reduce_ride) are extra workgroups of the same launch; the call's own two
+ * reductions follow in one launch (deferred mode without riding: queued).  dx0_out (NULL in the engine): when given, [B*T, 3C]
+ * receives dX0, bit-identical to edgl_gemm.  The other arguments are those of edgl_encode_bwd_add_label, same workspace.
+ * edgl_dx_encode_supported(B, T, C, dtype) = 1 for EDGL_BF16, C = 128, B <= 2048 and at most B / 8 padded samples in the last
+ * chunk of 128 (B = 120, 128, 250, 512: yes; 4, 129: no), else 0: the unfused pair remains the path for everything else. */
+int edgl_dx_encode_supported(int B, int T, int C, int dtype);
+int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int lda, int ldb, void* dx0_out, const int64_t* ids,
+                             const uint8_t* marks, const void* add1, const void* add2, int B, int T, int C, int E, int I,
+                             float drop_rate, const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos,
+                             float* d_mark_emb, float* workspace, int c_true, const void* lab_rows, const int64_t* lab_ids,
+                             const float* lab_coef, const int32_t* lab_nvalid, int lab_R, float* d_bias, int dtype, void* stream);
 
 /* ---- Deterministic item-table scatter (csrc/k_segsum.hip) — coding.py:60-64, EasyDGL.py:177-185 ---------------------
  * The f32 atomics of the embedding scatter and of the one-hot term of the scoring gradient make the item-table gradient differ in
