@@ -23,6 +23,7 @@ MAU_CAUSAL, MAU_NO_DIAG, MAU_DIAG_ZERO = 1, 2, 4
 MAU_NO_SKIP = 8      # host-side hint (include/easydgl_hip.h): the unskipped BiMAU kernels
 MAU_STREAM = 16      # host-side hint: the key-streamed BiMAU kernels at a shape the in-register kernels also take
 TATTN_CAUSAL = 1
+TATTN_ORDERED = 2    # interval attention: the LDS bins filled in a fixed order, no f32 atomics
 
 P, I, F, L, U32, I64 = c_void_p, c_int, c_float, c_long, c_uint32, c_int64
 
@@ -56,6 +57,7 @@ SIGNATURES = {
     "edgl_embed_pos_bwd": (I, [P, P, I, I, I, I, F, P, U32, P, P, I, P]),
     "edgl_embed_pos_fwd_ct": (I, [P, P, P, P, P, I, I, I, I, F, F, P, U32, P, P, P, I, I, P]),
     "edgl_embed_pos_bwd_ct": (I, [P, P, I, I, I, I, F, P, U32, P, P, I, I, P]),
+    "edgl_embed_pos_bwd_det": (I, [P, P, I, I, I, I, F, P, U32, P, P, I, P, I, P]),
     "edgl_gemm": (I, [P, P, P, I, I, I, I, I, I, I, I, P, P, I, I, P, I, P]),
     "edgl_colsum": (I, [P, I, I, I, P, I, P, I, I, P]),
     "edgl_gemm_dw_workspace": (L, [I, I, I, I]),
@@ -168,6 +170,9 @@ SIGNATURES = {
     "edgl_tiattn_fwd": (I, [P, I, P, I, P, I, P, I, P, P, P, P, I, I, I, I, I, F, F, I, F, P, U32, P, I, P, P, I, I, P]),
     "edgl_tiattn_bwd": (I, [P, I, P, I, P, I, P, P, P, P, I, P, I, P, P, I, I, I, I, F, F, I, F, P, U32, P, I, P, I, P, I, P, P, P,
                             I, I, P]),
+    "edgl_tiattn_det_workspace": (L, [I, I, I]),
+    "edgl_tiattn_bwd_det": (I, [P, I, P, I, P, I, P, P, P, P, I, P, I, P, P, I, I, I, I, F, F, I, F, P, U32, P, I, P, I, P, I, P, P, P,
+                                P, I, I, P]),
     "edgl_add_pos2": (I, [P, P, P, I, I, I, P, I, P]),
     "edgl_tail_pack_elems": (L, [I]),
     "edgl_tail_supported": (I, [I, I, I]),
@@ -186,6 +191,7 @@ SIGNATURES = {
                           P, P, P, P, P, P, P, I, P]),
     "edgl_embedding_fwd": (I, [P, L, P, I, I, I, F, P, I, P]),
     "edgl_embedding_bwd": (I, [P, L, P, I, I, I, F, P, I, P]),
+    "edgl_embedding_bwd_det": (I, [P, L, P, I, I, I, F, P, P, I, P]),
     "edgl_time_sinusoid": (I, [P, L, P, I, P, I, P]),
     "edgl_time_function_fwd": (I, [P, L, P, P, I, P, I, P]),
     "edgl_time_function_bwd_workspace": (L, [I]),

@@ -64,6 +64,10 @@ int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* d
                       const uint64_t* rng, uint32_t stream_id, float* d_item, void* plan, int dtype, hipStream_t st);
 int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
                       const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype, hipStream_t st);
+// ... and the rows of a plain lookup (edgl_embed_pos_bwd_det, edgl_embedding_bwd_det): sq * drop(src[row * ld + c]) into the
+// zero-filled d_table; keep_zero: key 0 is summed like the others
+int edgl_segsum_rows(const int64_t* ids, long rows, int C, int I, const void* src, long ld, float sq, float rate, const uint64_t* rng,
+                     uint32_t stream_id, int keep_zero, float* d_table, void* plan, int dtype, hipStream_t st);
 
 // ----------------------------------------------------------------------------------------------
 // element types: activations / GEMM operands are float (exact-f32 MFMA path) or bf16

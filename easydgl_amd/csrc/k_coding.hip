@@ -167,6 +167,24 @@ extern "C" int edgl_embedding_bwd(const int64_t* ids, long n, const void* d_out,
     return EDGL_OK;
 }
 
+// edgl_embedding_bwd without f32 atomics: the rows of every index as ordered sums over a plan of ids that this call
+// builds in `plan` (k_segsum.hip).  zero_pad cuts index 0 off; without it row 0 is summed like the others.
+extern "C" int edgl_embedding_bwd_det(const int64_t* ids, long n, const void* d_out, int rows, int C, int zero_pad, float scale,
+                                      float* d_table, void* plan, int dtype, void* stream) {
+    EDGL_REQUIRE(ids && d_out && d_table && plan, EDGL_ERR_NULL, "edgl_embedding_bwd_det: null pointer");
+    EDGL_REQUIRE(coding_shape_ok(n, C) && C <= 512 && rows > 0 && n < (1L << 30), EDGL_ERR_SHAPE,
+                 "edgl_embedding_bwd_det: bad shape n=%ld rows=%d C=%d (a multiple of 4 up to 512)", n, rows, C);
+    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_embedding_bwd_det: bad dtype %d", dtype);
+    EDGL_REQUIRE(((uintptr_t)plan & 15) == 0, EDGL_ERR_SHAPE, "edgl_embedding_bwd_det: the plan buffer must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(d_table, 0, (size_t)rows * C * sizeof(float), st) != hipSuccess) {
+        edgl_set_error("edgl_embedding_bwd_det: memset failed");
+        return EDGL_ERR_LAUNCH;
+    }
+    if (zero_pad && rows < 2) return EDGL_OK;      // row 0 alone, and it is a constant
+    return edgl_segsum_rows(ids, n, C, rows, d_out, C, scale, 0.f, nullptr, 0, zero_pad ? 0 : 1, d_table, plan, dtype, st);
+}
+
 extern "C" int edgl_time_sinusoid(const float* x, long n, const float* tscale, int C, void* out, int dtype, void* stream) {
     EDGL_REQUIRE(x && tscale && out, EDGL_ERR_NULL, "edgl_time_sinusoid: null pointer");
     EDGL_REQUIRE(coding_shape_ok(n, C), EDGL_ERR_SHAPE, "edgl_time_sinusoid: bad shape n=%ld C=%d", n, C);

@@ -221,6 +221,37 @@ __global__ __launch_bounds__(256) void embed_pos_bwd_kernel(EmbP p) {
     }
 }
 
+// Deterministic form of the position half: d_pos[t][c] = sum_b dropmask * dx[b, t, C + c] with b ascending.  One
+// thread per (t, 4 channels) is the only writer of its elements; eight rows are in flight, the adds stay in order.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_pos_dpos_kernel(EmbP p) {
+    const int cpr = p.C >> 2;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long)p.T * cpr) return;
+    const int t = (int)(gid / cpr), c0 = (int)(gid % cpr) * 4;
+    const DropKey dk = make_dropkey(p.rng, p.stream_id, p.rate);
+    const long ldo = 2L * p.C;
+    const T* d = reinterpret_cast<const T*>(p.dx0) + p.C + c0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int b0 = 0; b0 < p.B; b0 += 8) {
+        Frag4<T> g[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) g[k] = frag_ld<T>(d + ((long)min(b0 + k, p.B - 1) * p.T + t) * ldo);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (b0 + k >= p.B) break;
+            const long row = (long)(b0 + k) * p.T + t;
+            float gv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gv[j] = to_f32(g[k].v[j]);
+            drop_apply4(dk, (uint64_t)row * ldo + p.C + c0, gv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += gv[j];
+        }
+    }
+    *reinterpret_cast<float4*>(p.d_pos + (long)t * p.C + c0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+}
+
 }  // namespace
 
 extern "C" int edgl_embed_pos_fwd_ct(const int64_t* ids, const float* ts, const void* item_tab, const float* pos_tab,
@@ -279,6 +310,38 @@ extern "C" int edgl_embed_pos_bwd_ct(const int64_t* ids, const void* dx0, int B,
         hipFuncSetAttribute((const void*)embed_pos_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         hipLaunchKernelGGL((embed_pos_bwd_kernel<bf16>), grid, dim3(256), smem, st, p);
     }
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
+// edgl_embed_pos_bwd_ct without f32 atomics: the item rows as ordered sums over a plan of ids that this call builds in `plan`
+// (k_segsum.hip; key 0 is cut off), the position rows summed over b in order.  Same masks, same scale, every sum in an order
+// that follows from ids and the shape alone.
+extern "C" int edgl_embed_pos_bwd_det(const int64_t* ids, const void* dx0, int B, int T, int C, int I, float drop_rate,
+                                      const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos, int c_true,
+                                      void* plan, int dtype, void* stream) {
+    EDGL_REQUIRE(ids && dx0 && d_item && plan, EDGL_ERR_NULL, "edgl_embed_pos_bwd_det: null pointer");
+    EDGL_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && C <= 512 && I > 1 && (long)B * T < (1L << 30),
+                 EDGL_ERR_SHAPE, "edgl_embed_pos_bwd_det: bad shape B=%d T=%d C=%d (a multiple of 4 up to 512) I=%d", B, T, C, I);
+    EDGL_REQUIRE(c_true >= 0 && c_true <= C, EDGL_ERR_SHAPE, "edgl_embed_pos_bwd_det: true width %d exceeds C=%d", c_true, C);
+    EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_embed_pos_bwd_det: bad dtype %d", dtype);
+    EDGL_REQUIRE(((uintptr_t)plan & 15) == 0 && ((uintptr_t)d_pos & 15) == 0, EDGL_ERR_SHAPE,
+                 "edgl_embed_pos_bwd_det: plan and d_pos must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(d_item, 0, (size_t)I * C * sizeof(float), st) != hipSuccess) {
+        edgl_set_error("edgl_embed_pos_bwd_det: memset failed");
+        return EDGL_ERR_LAUNCH;
+    }
+    const float sq = sqrtf((float)(c_true > 0 ? c_true : C));
+    const long ldo = d_pos ? 2L * C : (long)C;
+    if (int rc = edgl_segsum_rows(ids, (long)B * T, C, I, dx0, ldo, sq, drop_rate, rng_state, stream_id, 0, d_item, plan, dtype, st))
+        return rc;
+    if (!d_pos) return EDGL_OK;
+    EmbP p{ids, nullptr, nullptr, nullptr, nullptr, B, T, C, 0, 1.f, drop_rate, rng_state, stream_id, nullptr, nullptr, nullptr,
+           dx0, d_item, d_pos, 0, sq};
+    const dim3 grid((unsigned)(((long)T * (C / 4) + 255) / 256));
+    if (dtype == EDGL_F32) hipLaunchKernelGGL((embed_pos_dpos_kernel<float>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((embed_pos_dpos_kernel<bf16>), grid, dim3(256), 0, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

@@ -52,6 +52,7 @@ static Layout layout(long n) {
 
 struct SortP {
     const int64_t* keys; const int32_t* nvalid; int n, i0, i1;      // first pass: the caller's keys
+    int kofs;                                                       // ... sorted as keys[e] + kofs (1: a table whose row 0 counts)
     const uint32_t* kin; const int32_t* iin;                        // later passes: the previous pass' output
     uint32_t* kout; int32_t* iout;
     int32_t* hist; int nblk; int shift;
@@ -62,7 +63,7 @@ template <bool FIRST>
 __device__ __forceinline__ uint32_t sort_load(const SortP& p, int e, int nlive, int32_t& idx) {
     if constexpr (FIRST) {
         idx = e;
-        const int64_t k = p.keys[e];
+        const int64_t k = p.keys[e] + p.kofs;
         const bool keep = e < nlive && k != 0 && k >= p.i0 && k < p.i1;
         return keep ? (uint32_t)k : 0u;
     } else {
@@ -269,6 +270,7 @@ struct SumP {
     float* part; float* partb;      // [nsub][2][C], [nsub][2]: slot 0 = the segment that came in from the left, 1 = the one that leaves
     int C;
     const void* src; const void* add1; const void* add2;      // embedding rows: dX0 (leading dimension 3C), optional [rows, C] terms
+    long ld;                                                  // item rows (ROWS): leading dimension of src, C or 2C
     float sq; float rate; const uint64_t* rng; uint32_t stream_id;
     const float* coef; const float* gscale;                   // label rows: src = the compacted head rows [R, C]
     float* d_item; float* d_bias;
@@ -288,10 +290,13 @@ __device__ __forceinline__ float sum3(float x, float a, float b) {
     return t + (e1 + e2);
 }
 
-// LABEL = false: term = sqrt(C_true) * drop(dX0[row, c] (+ add1 + add2)), the mask of element row * 3C + c (encode_scatter_kernel)
-// LABEL = true : term = -gscale coef[row] rows[row, c];  bias term -gscale coef[row]
-template <typename T, bool LABEL>
+// EMBED: term = sqrt(C_true) * drop(dX0[row, c] (+ add1 + add2)), the mask of element row * 3C + c (encode_scatter_kernel)
+// LABEL: term = -gscale coef[row] rows[row, c];  bias term -gscale coef[row]
+// ROWS : term = sq * drop(src[row * ld + c]), the mask of element row * ld + c (embed_pos_bwd_kernel; rate 0: embedding_bwd_kernel)
+enum { EMBED = 0, LABEL_ROWS = 1, ROWS = 2 };
+template <typename T, int ROLE>
 __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
+    constexpr bool LABEL = ROLE == LABEL_ROWS;
     const int cpr = p.C >> 2, rows_par = 256 / cpr;
     const int tid = threadIdx.x, cv = tid % cpr, rl = tid / cpr, c0 = cv * 4;
     if (rl >= rows_par) return;
@@ -303,8 +308,8 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
     const DropKey dk = make_dropkey(p.rng, p.stream_id, LABEL ? 0.f : p.rate);
     const float gs = LABEL ? (p.gscale ? p.gscale[0] : 1.0f) : 0.f;
     const T* src = reinterpret_cast<const T*>(p.src);
-    const long ld = LABEL ? p.C : 3L * p.C;
-    const bool adds = !LABEL && p.add1;
+    const long ld = LABEL ? p.C : (ROLE == ROWS ? p.ld : 3L * p.C);
+    const bool adds = ROLE == EMBED && p.add1;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb = 0.f;
     int s_cur = p.seg_id[p0];
     auto flush = [&]() {
@@ -360,7 +365,7 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
                 for (int j = 0; j < 4; ++j) acc[j] += w * gv[j];
                 accb += w;
             } else {
-                drop_apply4(dk, (uint64_t)row[k] * 3 * p.C + c0, gv);
+                drop_apply4(dk, (uint64_t)row[k] * ld + c0, gv);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[j] += p.sq * gv[j];
             }
@@ -431,7 +436,14 @@ extern "C" long edgl_segsum_plan_bytes(int n, int I) {
     return segsum::layout(n).total * 4;
 }
 
+// the plan of keys[e] + kofs (kofs = 1 with [i0, i1) = [1, I): key 0 of the caller is kept, as key 1)
+static int segsum_plan_ofs(const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, int kofs, void* plan, void* stream);
+
 extern "C" int edgl_segsum_plan(const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, void* plan, void* stream) {
+    return segsum_plan_ofs(keys, n, nvalid, I, i0, i1, 0, plan, stream);
+}
+
+static int segsum_plan_ofs(const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, int kofs, void* plan, void* stream) {
     using namespace segsum;
     EDGL_REQUIRE(keys && plan, EDGL_ERR_NULL, "edgl_segsum_plan: null pointer");
     EDGL_REQUIRE(n > 0 && I > 1 && i0 >= 0 && i1 <= I && i0 < i1, EDGL_ERR_SHAPE, "edgl_segsum_plan: bad shape n=%d I=%d [%d,%d)", n, I, i0, i1);
@@ -443,7 +455,7 @@ extern "C" int edgl_segsum_plan(const int64_t* keys, int n, const int32_t* nvali
     int32_t* ib[2] = {w + L.idxA, w + L.idxB};
     const int passes = edgl_segsum_passes(I);
     SortP p{};
-    p.keys = keys; p.nvalid = nvalid; p.n = n; p.i0 = i0; p.i1 = i1; p.hist = w + L.hist; p.nblk = L.nblk;
+    p.keys = keys; p.nvalid = nvalid; p.n = n; p.i0 = i0; p.i1 = i1; p.kofs = kofs; p.hist = w + L.hist; p.nblk = L.nblk;
     for (int ps = 0; ps < passes; ++ps) {
         p.shift = 8 * ps;
         p.kin = ps ? kb[(ps - 1) & 1] : nullptr; p.iin = ps ? ib[(ps - 1) & 1] : nullptr;
@@ -465,15 +477,15 @@ extern "C" int edgl_segsum_plan(const int64_t* keys, int n, const int32_t* nvali
 }
 
 // the two ordered sums over a plan this call builds first (called from k_encode.hip / k_score.hip)
-static int segsum_run(bool label, const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, segsum::SumP p, void* plan,
-                      int dtype, hipStream_t st) {
+static int segsum_run(int role, const int64_t* keys, int n, const int32_t* nvalid, int I, int i0, int i1, int kofs, segsum::SumP p,
+                      void* plan, int dtype, hipStream_t st) {
     using namespace segsum;
     EDGL_REQUIRE(dtype == EDGL_F32 || dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_segsum: bad dtype %d", dtype);
     EDGL_REQUIRE(p.C > 0 && p.C % 4 == 0 && p.C <= CMAX, EDGL_ERR_SHAPE, "edgl_segsum: C=%d unsupported (a multiple of 4 up to %d)", p.C, CMAX);
     const uintptr_t al = (uintptr_t)p.src | (uintptr_t)p.add1 | (uintptr_t)p.add2;
     EDGL_REQUIRE((al & (dtype == EDGL_F32 ? 15 : 7)) == 0 && ((uintptr_t)p.d_item & 15) == 0, EDGL_ERR_SHAPE,
                  "edgl_segsum: operands must be 16-byte (bf16 rows: 8-byte) aligned");
-    const int rc = edgl_segsum_plan(keys, n, nvalid, I, i0, i1, plan, st);
+    const int rc = segsum_plan_ofs(keys, n, nvalid, I, i0, i1, kofs, plan, st);
     if (rc) return rc;
     const Layout L = layout(n);
     int32_t* w = reinterpret_cast<int32_t*>(plan);
@@ -481,12 +493,16 @@ static int segsum_run(bool label, const int64_t* keys, int n, const int32_t* nva
     p.part = reinterpret_cast<float*>(w + L.part); p.partb = reinterpret_cast<float*>(w + L.partb);
     const int rows_par = 256 / (p.C / 4);
     const dim3 grid((unsigned)((L.nsub + rows_par - 1) / rows_par));
-    if (label) {      // (bf16 only: in f32 the scoring product pass contains the one-hot term and the entry point is a no-op)
-        hipLaunchKernelGGL((segsum_walk_kernel<bf16, true>), grid, dim3(256), 0, st, p);
+    if (role == LABEL_ROWS) {      // (bf16 only: in f32 the scoring product pass contains the one-hot term and the entry point is a no-op)
+        hipLaunchKernelGGL((segsum_walk_kernel<bf16, LABEL_ROWS>), grid, dim3(256), 0, st, p);
         hipLaunchKernelGGL(segsum_join_kernel<true>, grid, dim3(256), 0, st, p);
+    } else if (role == ROWS) {
+        if (dtype == EDGL_F32) hipLaunchKernelGGL((segsum_walk_kernel<float, ROWS>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((segsum_walk_kernel<bf16, ROWS>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL(segsum_join_kernel<false>, grid, dim3(256), 0, st, p);
     } else {
-        if (dtype == EDGL_F32) hipLaunchKernelGGL((segsum_walk_kernel<float, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((segsum_walk_kernel<bf16, false>), grid, dim3(256), 0, st, p);
+        if (dtype == EDGL_F32) hipLaunchKernelGGL((segsum_walk_kernel<float, EMBED>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((segsum_walk_kernel<bf16, EMBED>), grid, dim3(256), 0, st, p);
         hipLaunchKernelGGL(segsum_join_kernel<false>, grid, dim3(256), 0, st, p);
     }
     EDGL_LAUNCH_CHECK();
@@ -499,7 +515,7 @@ int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* d
     EDGL_REQUIRE(rows > 0 && rows < (1L << 30), EDGL_ERR_SHAPE, "edgl_encode_bwd_add_det: %ld rows unsupported", rows);
     segsum::SumP p{};
     p.C = C; p.src = dx0; p.add1 = add1; p.add2 = add2; p.sq = sq; p.rate = rate; p.rng = rng; p.stream_id = stream_id; p.d_item = d_item;
-    return segsum_run(false, ids, (int)rows, nullptr, I, 0, I, p, plan, dtype, st);
+    return segsum_run(segsum::EMBED, ids, (int)rows, nullptr, I, 0, I, 0, p, plan, dtype, st);
 }
 
 int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
@@ -508,5 +524,20 @@ int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef
     EDGL_REQUIRE(dtype == EDGL_BF16, EDGL_ERR_DTYPE, "edgl_score_flash_label_term_det: the ordered label sum takes bf16 rows (dtype %d)", dtype);
     segsum::SumP p{};
     p.C = C; p.src = rows; p.coef = coef; p.gscale = gscale; p.d_item = d_table; p.d_bias = d_bias;
-    return segsum_run(true, labels, R, nvalid, I, i0, i1, p, plan, dtype, st);
+    return segsum_run(segsum::LABEL_ROWS, labels, R, nvalid, I, i0, i1, 0, p, plan, dtype, st);
+}
+
+// d_table[key] = sum over the rows with that key, in plan order, of sq * drop(src[row * ld + c]) into the ZERO-FILLED d_table
+// (k_data.hip: edgl_embed_pos_bwd_det, k_coding.hip: edgl_embedding_bwd_det).  keep_zero: key 0 is a table row like the others
+// (a lookup without zero padding) — the keys are sorted one up and the sums land one row down.
+int edgl_segsum_rows(const int64_t* ids, long rows, int C, int I, const void* src, long ld, float sq, float rate, const uint64_t* rng,
+                     uint32_t stream_id, int keep_zero, float* d_table, void* plan, int dtype, hipStream_t st) {
+    EDGL_REQUIRE(plan, EDGL_ERR_NULL, "edgl_segsum_rows: null plan buffer");
+    EDGL_REQUIRE(rows > 0 && rows < (1L << 30) && I >= 1 && I < (1 << 30), EDGL_ERR_SHAPE, "edgl_segsum_rows: %ld rows / %d keys unsupported", rows, I);
+    EDGL_REQUIRE(ld >= C && ld % 4 == 0, EDGL_ERR_SHAPE, "edgl_segsum_rows: bad leading dimension %ld (C=%d)", ld, C);
+    segsum::SumP p{};
+    p.C = C; p.src = src; p.ld = ld; p.sq = sq; p.rate = rate; p.rng = rng; p.stream_id = stream_id;
+    const int k = keep_zero ? 1 : 0;
+    p.d_item = d_table - (long)k * C;
+    return segsum_run(segsum::ROWS, ids, (int)rows, nullptr, I + k, k, I + k, k, p, plan, dtype, st);
 }

@@ -26,6 +26,7 @@
 namespace {
 
 constexpr int TA_CAUSAL = 1;
+constexpr int TA_ORDERED = 2;      // interval attention: the LDS bins are filled in a fixed order, without atomics
 constexpr float PADV = -4294967296.0f;   // float32(-2**32 + 1)
 
 struct TaP {
@@ -351,6 +352,19 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// The ordered form of the bin adds (TA_ORDERED): the four lanes that share a query row (same l15, g4 = 0, 4, 8, 12) take turns; in
+// its turn a lane adds its four pairs to its own row with plain loads and stores, r ascending; a wave-level LDS sync ends every
+// turn.  With the key tiles walked in order, a bin receives its terms by ascending key: one order, whatever the timing.
+__device__ __forceinline__ void ordered_bin_add(float* row, int g4, const int (&bk)[4], const f32x4& v) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        if (g4 == g * 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) row[bk[r]] += v[r];
+        }
+        wave_lds_sync();
+    }
+}
 // LDS tile of one wave: bins [16][NBp + 4] f32 (binned probabilities in the forward, binned score gradients backward)
 __host__ __device__ constexpr size_t ti_tile_f(int NBp) { return (size_t)16 * (NBp + 4) * sizeof(float); }
 
@@ -489,7 +503,7 @@ __device__ __forceinline__ void interval_dots4_rows(const bf16* a0, long lda, co
     }
 }
 
-template <typename T, int DT>
+template <typename T, int DT, bool ORD = false>
 __global__ __launch_bounds__(256) void tiattn_fwd_kernel(TaP p, TiP t) {
     extern __shared__ __attribute__((aligned(16))) char lds_c[];
     Job j;
@@ -628,14 +642,17 @@ __global__ __launch_bounds__(256) void tiattn_fwd_kernel(TaP p, TiP t) {
             if (dk.thresh != 0u) { h0 = drop_hash_pair(dk, dbase + kt * 16 + g4); h1 = drop_hash_pair(dk, dbase + kt * 16 + g4 + 2); }
             const uint32_t hb[4] = {h0 & 0xffffu, h0 >> 16, h1 & 0xffffu, h1 >> 16};
             f32x4 a4;
+            int bko[ORD ? 4 : 1];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int kcl = min(kt * 16 + g4 + r, p.T - 1);
                 const int bk = bucket_of(xq1, tsr[kcl] / t.time_scale, t.timelen);
                 const float P = __expf(xs[kt][r] - m) * invl;
                 a4[r] = (dk.thresh == 0u || hb[r] >= dk.t16) ? P * dk.scale : 0.f;            // temporal.py:90
-                atomicAdd(&Ws[l15 * LDG + bk], a4[r]);
+                if constexpr (ORD) bko[r] = bk;
+                else atomicAdd(&Ws[l15 * LDG + bk], a4[r]);
             }
+            if constexpr (ORD) ordered_bin_add(Ws + l15 * LDG, g4, bko, a4);
             const Frag4<T> pf = frag_from_acc<T>(a4);
 #pragma unroll
             for (int ut = 0; ut < DT; ++ut)
@@ -660,7 +677,7 @@ __global__ __launch_bounds__(256) void tiattn_fwd_kernel(TaP p, TiP t) {
     }
 }
 
-template <typename T, int DT>
+template <typename T, int DT, bool ORD = false>
 __global__ __launch_bounds__(256) void tiattn_bwd_q_kernel(TaP p, TiP t) {
     extern __shared__ __attribute__((aligned(16))) char lds_c[];
     Job j;
@@ -757,8 +774,9 @@ __global__ __launch_bounds__(256) void tiattn_bwd_q_kernel(TaP p, TiP t) {
             const float P = __expf(v - m) * invl;
             const float dP = (dk.thresh == 0u || hb[r] >= dk.t16) ? (da[r] + dw) * dk.scale : 0.f;
             ds[r] = (pad || fut || !qok) ? 0.f : P * (dP - dsum) * p.cscale;
-            atomicAdd(&dGs[l15 * LDG + bk], ds[r]);
+            if constexpr (!ORD) atomicAdd(&dGs[l15 * LDG + bk], ds[r]);
         }
+        if constexpr (ORD) ordered_bin_add(dGs + l15 * LDG, g4, bks, ds);
         const Frag4<T> dsf = frag_from_acc<T>(ds);
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
@@ -874,7 +892,9 @@ __global__ __launch_bounds__(256) void tiattn_bwd_k_kernel(TaP p, TiP t) {
 
 // d_tab[d][head*dh + u] += sum_r Wb[head*BT + r][d] * X[r][head*dh + u]: the interval-table gradients
 //   d(Ktime) = dG^T . Q,  d(Vtime) = W^T . dO   (contraction over all B*T rows; f32 atomics of per-split partial tiles)
-template <typename T>
+// SLAB: d_tab is [splits][tab_rows][ldt] and every split stores its partial tile into its own slab — each element
+// has one writer — for bucket_dtable_sum_kernel to add up in split order.
+template <typename T, bool SLAB = false>
 __global__ __launch_bounds__(256) void bucket_dtable_kernel(const T* Wb, int NBp, const T* X, int ldx, long BT, int H, int dh,
                                                             int tab_rows, float* d_tab, int ldt, int splits) {
     const int lane = threadIdx.x & 63, g4 = (lane >> 4) * 4, l15 = lane & 15;
@@ -898,8 +918,32 @@ __global__ __launch_bounds__(256) void bucket_dtable_kernel(const T* Wb, int NBp
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int d = dti * 16 + g4 + r;
-        if (d < tab_rows) atomicAdd(d_tab + (long)d * ldt + head * dh + ut * 16 + l15, acc[r]);
+        if constexpr (SLAB) {
+            if (d < tab_rows) d_tab[((long)sp * tab_rows + d) * ldt + head * dh + ut * 16 + l15] = acc[r];
+        } else {
+            if (d < tab_rows) atomicAdd(d_tab + (long)d * ldt + head * dh + ut * 16 + l15, acc[r]);
+        }
     }
+}
+// d_ktime | d_vtime [n4 float4 each] = the sum of their `splits` slabs (slabs: [2][splits][n4]) in split order; one writer per element
+__global__ __launch_bounds__(256) void bucket_dtable_sum_kernel(const float4* slabs, long n4, int splits, float4* d_ktime, float4* d_vtime) {
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= 2 * n4) return;
+    const int tab = gid >= n4;
+    const long e = gid - tab * n4;
+    const float4* src = slabs + (long)tab * splits * n4 + e;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int s0 = 0; s0 < splits; s0 += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = src[(long)min(s0 + k, splits - 1) * n4];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (s0 + k >= splits) break;
+            a.x += v[k].x; a.y += v[k].y; a.z += v[k].z; a.w += v[k].w;
+        }
+    }
+    (tab ? d_vtime : d_ktime)[e] = a;
 }
 
 template <typename T>
@@ -1430,15 +1474,37 @@ int launch_ti(K kern, const TaP& p, const TiP& t, int waves, size_t wave_bytes, 
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
+constexpr int TI_SPLITS = 32;      // row splits of the interval-table gradients
 template <typename T, int DT>
 int ti_fwd(const TaP& p, const TiP& t, hipStream_t st) {
+    if (p.flags & TA_ORDERED) return launch_ti(tiattn_fwd_kernel<T, DT, true>, p, t, 4, ti_tile_f(t.NBp), st);
     return launch_ti(tiattn_fwd_kernel<T, DT>, p, t, 4, ti_tile_f(t.NBp), st);
+}
+// the deterministic backward: ordered bins in the query sweep, the table gradients through per-split slabs in `ws`
+template <typename T, int DT>
+int ti_bwd_det(const TaP& p, const TiP& t, float* d_ktime, float* d_vtime, float* ws, hipStream_t st) {
+    if (int rc = launch_ti(tiattn_bwd_q_kernel<T, DT, true>, p, t, 4, ti_tile_f(t.NBp), st)) return rc;
+    if (int rc = launch_ti(tiattn_bwd_k_kernel<T, DT>, p, t, 4, 0, st)) return rc;
+    const int C = p.H * 16 * DT, splits = TI_SPLITS;
+    const long jobs = (long)p.H * (t.NBp / 16) * DT * splits, BT = (long)p.B * p.T, n = (long)t.tab_rows * C;
+    const dim3 grid((unsigned)((jobs + 3) / 4));
+    hipLaunchKernelGGL((bucket_dtable_kernel<T, true>), grid, dim3(256), 0, st, reinterpret_cast<const T*>(t.dgbuf), t.NBp,
+                       reinterpret_cast<const T*>(p.qx), p.ldq, BT, p.H, 16 * DT, t.tab_rows, ws, C, splits);
+    hipLaunchKernelGGL((bucket_dtable_kernel<T, true>), grid, dim3(256), 0, st, reinterpret_cast<const T*>(t.wbuf), t.NBp,
+                       reinterpret_cast<const T*>(p.d_out), p.ld_do, BT, p.H, 16 * DT, t.tab_rows, ws + splits * n, C, splits);
+    hipLaunchKernelGGL(bucket_dtable_sum_kernel, dim3((unsigned)((2 * (n / 4) + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(ws), n / 4, splits, reinterpret_cast<float4*>(d_ktime),
+                       reinterpret_cast<float4*>(d_vtime));
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
 }
 template <typename T, int DT>
 int ti_bwd(const TaP& p, const TiP& t, float* d_ktime, float* d_vtime, hipStream_t st) {
-    if (int rc = launch_ti(tiattn_bwd_q_kernel<T, DT>, p, t, 4, ti_tile_f(t.NBp), st)) return rc;
+    if (p.flags & TA_ORDERED) {
+        if (int rc = launch_ti(tiattn_bwd_q_kernel<T, DT, true>, p, t, 4, ti_tile_f(t.NBp), st)) return rc;
+    } else if (int rc = launch_ti(tiattn_bwd_q_kernel<T, DT>, p, t, 4, ti_tile_f(t.NBp), st)) return rc;
     if (int rc = launch_ti(tiattn_bwd_k_kernel<T, DT>, p, t, 4, 0, st)) return rc;
-    const int C = p.H * 16 * DT, splits = 32;
+    const int C = p.H * 16 * DT, splits = TI_SPLITS;
     if (hipMemsetAsync(d_ktime, 0, (size_t)t.tab_rows * C * sizeof(float), st) != hipSuccess ||
         hipMemsetAsync(d_vtime, 0, (size_t)t.tab_rows * C * sizeof(float), st) != hipSuccess) {
         edgl_set_error("edgl_tiattn_bwd: memset failed");
@@ -1507,18 +1573,21 @@ extern "C" int edgl_tiattn_fwd(const void* q, int ldq, const void* k, int ldk, c
 #undef EDGL_TI_FWD
 }
 
-extern "C" int edgl_tiattn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const int64_t* ids,
-                               const float* ts, const void* ktime, const void* vtime, int tab_rows, const void* d_out, int ld_do,
-                               void* saved, void* wbuf, int B, int T, int H, int dh, float scale, float time_scale, int timelen,
-                               float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, int ld_dq, void* d_k,
-                               int ld_dk, void* d_v, int ld_dv, void* dgbuf, float* d_ktime, float* d_vtime, int flags, int dtype,
-                               void* stream) {
+// edgl_tiattn_bwd (det_ws == nullptr) and edgl_tiattn_bwd_det (the slab workspace of the ordered table gradients)
+static int tiattn_bwd_any(const char* who, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const int64_t* ids,
+                          const float* ts, const void* ktime, const void* vtime, int tab_rows, const void* d_out, int ld_do,
+                          void* saved, void* wbuf, int B, int T, int H, int dh, float scale, float time_scale, int timelen,
+                          float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, int ld_dq, void* d_k,
+                          int ld_dk, void* d_v, int ld_dv, void* dgbuf, float* d_ktime, float* d_vtime, float* det_ws, int flags,
+                          int dtype, void* stream) {
     EDGL_REQUIRE(q && k && v && ids && ts && ktime && vtime && d_out && saved && wbuf && d_q && d_k && d_v && dgbuf && d_ktime &&
-                     d_vtime, EDGL_ERR_NULL, "edgl_tiattn_bwd: null pointer");
-    if (int rc = ti_check("edgl_tiattn_bwd", B, T, H, dh, timelen, tab_rows, dtype)) return rc;
+                     d_vtime, EDGL_ERR_NULL, "%s: null pointer", who);
+    if (int rc = ti_check(who, B, T, H, dh, timelen, tab_rows, dtype)) return rc;
     EDGL_REQUIRE(ldq % 4 == 0 && ldk % 4 == 0 && ldv % 4 == 0 && ld_do % 4 == 0 && ld_dq % 4 == 0 && ld_dk % 4 == 0 && ld_dv % 4 == 0,
-                 EDGL_ERR_SHAPE, "edgl_tiattn_bwd: row strides must be multiples of 4");
-    EDGL_REQUIRE(drop_rate == 0.f || rng_state, EDGL_ERR_NULL, "edgl_tiattn_bwd: dropout without rng_state");
+                 EDGL_ERR_SHAPE, "%s: row strides must be multiples of 4", who);
+    EDGL_REQUIRE(drop_rate == 0.f || rng_state, EDGL_ERR_NULL, "%s: dropout without rng_state", who);
+    EDGL_REQUIRE(!det_ws || (((uintptr_t)det_ws | (uintptr_t)d_ktime | (uintptr_t)d_vtime) & 15) == 0, EDGL_ERR_SHAPE,
+                 "%s: workspace, d_ktime and d_vtime must be 16-byte aligned", who);
     TaP p{};
     p.qx = q; p.kx = k; p.v = v; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv;
     p.ids = ids; p.B = B; p.T = T; p.H = H; p.Dq = dh; p.Dv = dh; p.cscale = scale; p.rate = drop_rate;
@@ -1531,16 +1600,50 @@ extern "C" int edgl_tiattn_bwd(const void* q, int ldq, const void* k, int ldk, c
     p.oatt = reinterpret_cast<float*>((char*)saved + s.off_o);
     TiP t{ts, time_scale, timelen, ktime, vtime, H * dh, tab_rows, wbuf, dgbuf, (timelen + 1 + 15) / 16 * 16};
     hipStream_t st = (hipStream_t)stream;
-#define EDGL_TI_BWD(TT)                                                        \
-    switch (dh / 16) {                                                         \
-        case 1: return ti_bwd<TT, 1>(p, t, d_ktime, d_vtime, st);              \
-        case 2: return ti_bwd<TT, 2>(p, t, d_ktime, d_vtime, st);              \
-        case 4: return ti_bwd<TT, 4>(p, t, d_ktime, d_vtime, st);              \
-        default: return ti_bwd<TT, 8>(p, t, d_ktime, d_vtime, st);             \
+#define EDGL_TI_BWD(TT, DTV) (det_ws ? ti_bwd_det<TT, DTV>(p, t, d_ktime, d_vtime, det_ws, st) : ti_bwd<TT, DTV>(p, t, d_ktime, d_vtime, st))
+#define EDGL_TI_BWD_SW(TT)                             \
+    switch (dh / 16) {                                 \
+        case 1: return EDGL_TI_BWD(TT, 1);             \
+        case 2: return EDGL_TI_BWD(TT, 2);             \
+        case 4: return EDGL_TI_BWD(TT, 4);             \
+        default: return EDGL_TI_BWD(TT, 8);            \
     }
-    if (dtype == EDGL_F32) { EDGL_TI_BWD(float) }
-    EDGL_TI_BWD(bf16)
+    if (dtype == EDGL_F32) { EDGL_TI_BWD_SW(float) }
+    EDGL_TI_BWD_SW(bf16)
+#undef EDGL_TI_BWD_SW
 #undef EDGL_TI_BWD
+}
+
+extern "C" int edgl_tiattn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const int64_t* ids,
+                               const float* ts, const void* ktime, const void* vtime, int tab_rows, const void* d_out, int ld_do,
+                               void* saved, void* wbuf, int B, int T, int H, int dh, float scale, float time_scale, int timelen,
+                               float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, int ld_dq, void* d_k,
+                               int ld_dk, void* d_v, int ld_dv, void* dgbuf, float* d_ktime, float* d_vtime, int flags, int dtype,
+                               void* stream) {
+    return tiattn_bwd_any("edgl_tiattn_bwd", q, ldq, k, ldk, v, ldv, ids, ts, ktime, vtime, tab_rows, d_out, ld_do, saved, wbuf, B, T, H,
+                          dh, scale, time_scale, timelen, drop_rate, rng_state, stream_id, d_q, ld_dq, d_k, ld_dk, d_v, ld_dv, dgbuf,
+                          d_ktime, d_vtime, nullptr, flags, dtype, stream);
+}
+
+// floats of the slab workspace of edgl_tiattn_bwd_det: [2 tables][TI_SPLITS][timelen + 1 rows][H * dh]
+extern "C" long edgl_tiattn_det_workspace(int H, int dh, int timelen) {
+    if (H <= 0 || !(dh == 16 || dh == 32 || dh == 64 || dh == 128) || timelen < 1 || timelen > 256) return -1;
+    return 2L * TI_SPLITS * (timelen + 1) * H * dh;
+}
+
+// edgl_tiattn_bwd in the deterministic form: the query sweep fills its bins in order (EDGL_TATTN_ORDERED, whatever
+// `flags` says) and every row split of the interval-table gradients stores its partial tile to a slab of its own in `workspace`;
+// one more launch adds the slabs in split order.  No memset, no atomics: every address has one writer per launch.
+extern "C" int edgl_tiattn_bwd_det(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const int64_t* ids,
+                                   const float* ts, const void* ktime, const void* vtime, int tab_rows, const void* d_out, int ld_do,
+                                   void* saved, void* wbuf, int B, int T, int H, int dh, float scale, float time_scale, int timelen,
+                                   float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, int ld_dq, void* d_k,
+                                   int ld_dk, void* d_v, int ld_dv, void* dgbuf, float* d_ktime, float* d_vtime, float* workspace,
+                                   int flags, int dtype, void* stream) {
+    EDGL_REQUIRE(workspace, EDGL_ERR_NULL, "edgl_tiattn_bwd_det: null pointer (workspace)");
+    return tiattn_bwd_any("edgl_tiattn_bwd_det", q, ldq, k, ldk, v, ldv, ids, ts, ktime, vtime, tab_rows, d_out, ld_do, saved, wbuf, B, T,
+                          H, dh, scale, time_scale, timelen, drop_rate, rng_state, stream_id, d_q, ld_dq, d_k, ld_dk, d_v, ld_dv, dgbuf,
+                          d_ktime, d_vtime, workspace, flags | TA_ORDERED, dtype, stream);
 }
 
 extern "C" int edgl_add_pos2(const void* kv, const float* posK, const float* posV, int B, int T, int C, void* out, int dtype,

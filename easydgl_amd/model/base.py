@@ -57,6 +57,8 @@ class Sequential(nn.Module):
         self.num_warmup_steps = getattr(FLAGS, "num_warmup_steps", None)
         cd = getattr(FLAGS, "compute_dtype", "bf16")
         self.act_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}[cd]
+        # bitwise reproducible training: every scatter / bin sum of the model's ops runs in its ordered form
+        self.deterministic = bool(getattr(FLAGS, "deterministic", False))
         self._arena: Optional[torch.Tensor] = None
         self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (a head dim the kernels do not tile)
         self._metrics = None

@@ -105,7 +105,7 @@ class CTSMA(Sequential):
         pad = self.pad
         x, spans, marks = ops.EmbedPosFn.apply(tab, self.pcoding.pembs.lookup_table, self.compute(tab), ids, ts,
                                                self.mark_lookup_table, self.time_scale, self._drop(hd, 1, is_training),
-                                               self.act_dtype, self.width_true if pad[0] else 0)   # :50-58
+                                               self.act_dtype, self.width_true if pad[0] else 0, self.deterministic)   # :50-58
         lams = []
         for i, blk in enumerate(self.layers):
             q_in = ops.AddLayerNormFn.apply(x, None, blk.att_ln.gamma, blk.att_ln.beta, ops.NO_DROP, None, pad)  # :70
@@ -129,7 +129,7 @@ class CTSMA(Sequential):
         rows, lams = self.encoder(features, True, None)
         tab = self.item_embs.lookup_table
         loss = ops.ScoreCEFn.apply(rows.reshape(-1, self.num_units), tab, self.output_bias, self.compute(tab),
-                                   labels.reshape(-1).contiguous())
+                                   labels.reshape(-1).contiguous(), self.deterministic)
         if self.l2_reg != 0.0:
             for p in (self.item_embs.lookup_table, self.pcoding.pembs.lookup_table):
                 loss = loss + ops.L2Fn.apply(p, self.l2_reg)

@@ -59,8 +59,6 @@ class EasyDGL(Sequential):
             raise ValueError(f"num_events must be in [2, {T.MAX_EVENTS}] (more than 16 run as mark groups: temporal.modulated_attention)")
         self.register_buffer("mark_lookup_table", torch.from_numpy(table.astype(np.uint8)), persistent=False)
         self.ct_reg = float(getattr(FLAGS, "ct_reg", 0.0) or 0.0)
-        # bitwise reproducible training: the item-table gradient as ordered sums instead of f32 atomics
-        self.deterministic = bool(getattr(FLAGS, "deterministic", False))
 
         gen = torch.Generator().manual_seed(self.seed)
         # A head dim the attention kernels do not tile runs zero-padded at the next of 16 / 32 / 64 / 128 (model/base.py: channel

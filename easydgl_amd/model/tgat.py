@@ -106,7 +106,7 @@ class TGAT(Sequential):
         # :49-62 — `* seqs_masks` is the identity here: row 0 of the table reads as zeros (coding.py:56-57)
         pad = self.pad
         x = ops.EmbedFn.apply(tab, self.compute(tab), ids, self._drop(hd, 1, is_training), self.act_dtype,
-                              self.width_true if pad[0] else 0)
+                              self.width_true if pad[0] else 0, self.deterministic)
         for i, blk in enumerate(self.layers):
             qn = ops.AddLayerNormFn.apply(x, None, blk.att_ln.gamma, blk.att_ln.beta, ops.NO_DROP, None, pad)     # :66
             att = blk.attention(qn, x, (ids, ts), is_training, True,
@@ -126,7 +126,7 @@ class TGAT(Sequential):
         rows = self.encoder(features, True, None)
         tab = self.item_embs.lookup_table
         loss = ops.ScoreCEFn.apply(rows.reshape(-1, self.num_units), tab, self.output_bias, self.compute(tab),
-                                   labels.reshape(-1).contiguous())
+                                   labels.reshape(-1).contiguous(), self.deterministic)
         if self.l2_reg != 0.0:
             for n in self.l2_param_names():
                 loss = loss + ops.L2Fn.apply(self.get_parameter(n), self.l2_reg)

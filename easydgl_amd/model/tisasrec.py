@@ -62,6 +62,7 @@ class TiSASRec(TGAT):
         for blk in self.layers:
             blk.attention.time_scale = self.time_scale
             blk.attention.timelen = self.timelen
+            blk.attention.deterministic = self.deterministic      # ordered interval bins, in training and evaluation alike
         return self
 
     def check_inputs(self) -> None:

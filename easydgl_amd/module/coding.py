@@ -30,9 +30,12 @@ class Embedding(nn.Module):
     """coding.py:45-64.  ``lookup_table`` is the RAW variable (l2-regularised incl. row 0, coding.py:53-55);
     with ``zero_pad`` row 0 acts as a zero constant wherever the table is used (coding.py:56-57)."""
 
-    def __init__(self, vocab_size, num_units, l2_reg=0.0, zero_pad=True, scale=True, gen=None):
+    def __init__(self, vocab_size, num_units, l2_reg=0.0, zero_pad=True, scale=True, gen=None, deterministic=False):
+        """``deterministic``: the stand-alone backward sums the rows of every index in a fixed order (edgl_embedding_bwd_det)
+        instead of with f32 atomics."""
         super().__init__()
         self.num_units, self.l2_reg, self.zero_pad, self.scale = num_units, l2_reg, zero_pad, scale
+        self.deterministic = bool(deterministic)
         self.lookup_table = nn.Parameter(glorot_uniform_(torch.empty(vocab_size, num_units), gen))
         self.compute = lambda p: p
 
@@ -40,7 +43,7 @@ class Embedding(nn.Module):
         """coding.py:60-64: ``lookup(table, inputs) * sqrt(num_units)`` (integer ``inputs`` of any shape)."""
         tab = self.lookup_table
         scale = float(self.num_units) ** 0.5 if self.scale else 1.0
-        return ops.EmbeddingFn.apply(tab, self.compute(tab), inputs.to(torch.int64), self.zero_pad, scale)
+        return ops.EmbeddingFn.apply(tab, self.compute(tab), inputs.to(torch.int64), self.zero_pad, scale, self.deterministic)
 
 
 class PositionCoding(nn.Module):

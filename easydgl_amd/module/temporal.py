@@ -229,6 +229,7 @@ class TiMultiHeadAttention(nn.Module):
             object.__setattr__(self, n, m)   # shared with the model: not registered twice
         self.compute = lambda p: p
         self.time_scale, self.timelen = 1.0, 256
+        self.deterministic = False      # set by the owning model: ordered interval bins, in training and evaluation alike
 
     def forward(self, queries, keys, intervals, is_training, causality=True, drop: ops.Drop = ops.NO_DROP):
         if not causality:
@@ -239,4 +240,4 @@ class TiMultiHeadAttention(nn.Module):
         kt, vt = self.tcoding_K.pembs.lookup_table, self.tcoding_V.pembs.lookup_table
         return ops.TiAttnFn.apply(q, kv, queries, self.pcoding_K.pembs.lookup_table, self.pcoding_V.pembs.lookup_table, kt, vt,
                                   self.compute(kt), self.compute(vt), ids, ts, self.num_heads, self.time_scale, self.timelen,
-                                  drop if is_training else ops.NO_DROP, float(getattr(self, "qk_scale", 0.0)))
+                                  drop if is_training else ops.NO_DROP, float(getattr(self, "qk_scale", 0.0)), self.deterministic)

@@ -201,12 +201,26 @@ class EncodeFn(torch.autograd.Function):
         return (d_item, d_pos, d_mark) + (None,) * 11
 
 
+def _embed_pos_bwd(deterministic, ids, dx0, B, T, C, I, drop: Drop, d_item, d_pos, c_true):
+    """edgl_embed_pos_bwd_ct, or its ordered form over a plan buffer of this call's own."""
+    if deterministic:
+        plan = segsum_plan_buffer(B * T, I, dx0.device)
+        check(lib.edgl_embed_pos_bwd_det(_ptr(ids), _ptr(dx0), B, T, C, I, float(drop.rate), drop.ptr(), drop.stream_id,
+                                         _ptr(d_item), _ptr(d_pos), c_true, _ptr(plan), _code(dx0), _stream()),
+              "edgl_embed_pos_bwd_det")
+    else:
+        check(lib.edgl_embed_pos_bwd_ct(_ptr(ids), _ptr(dx0), B, T, C, I, float(drop.rate), drop.ptr(), drop.stream_id,
+                                        _ptr(d_item), _ptr(d_pos), c_true, _code(dx0), _stream()), "edgl_embed_pos_bwd")
+
+
 class EmbedPosFn(torch.autograd.Function):
     """CTSMA.py:48-58: X0 = dropout(concat(item[ids]*sqrt(C), pos[0..T))), spans, marks (edgl_embed_pos_fwd/bwd)."""
 
     @staticmethod
-    def forward(ctx, item_master, pos_tab, item_c, ids, ts, mark_table, time_scale, drop: Drop, act_dtype, c_true=0):
-        """c_true: the true width of a channel-padded model (0: = C) — coding.py:62-63's sqrt(num_units)."""
+    def forward(ctx, item_master, pos_tab, item_c, ids, ts, mark_table, time_scale, drop: Drop, act_dtype, c_true=0,
+                deterministic=False):
+        """c_true: the true width of a channel-padded model (0: = C) — coding.py:62-63's sqrt(num_units).  deterministic: the
+        backward sums the item rows over a sorted plan and the position rows over b in order (edgl_embed_pos_bwd_det)."""
         B, T = ids.shape
         I, C = item_c.shape
         E = mark_table.shape[1]
@@ -218,6 +232,7 @@ class EmbedPosFn(torch.autograd.Function):
                                         _ptr(marks), int(c_true), _DT[act_dtype], _stream()), "edgl_embed_pos_fwd")
         ctx.save_for_backward(ids)
         ctx.c_true = int(c_true)
+        ctx.deterministic = bool(deterministic)
         ctx.meta = (B, T, C, I, drop, item_master.shape, pos_tab.shape)
         ctx.mark_non_differentiable(spans, marks)
         return x0, spans, marks
@@ -229,9 +244,8 @@ class EmbedPosFn(torch.autograd.Function):
         dx0 = dx0.contiguous()
         d_item = torch.empty(ishape, device=dx0.device, dtype=torch.float32)
         d_pos = torch.zeros(pshape, device=dx0.device, dtype=torch.float32)
-        check(lib.edgl_embed_pos_bwd_ct(_ptr(ids), _ptr(dx0), B, T, C, I, float(drop.rate), drop.ptr(), drop.stream_id,
-                                        _ptr(d_item), _ptr(d_pos), ctx.c_true, _code(dx0), _stream()), "edgl_embed_pos_bwd")
-        return (d_item, d_pos) + (None,) * 8
+        _embed_pos_bwd(ctx.deterministic, ids, dx0, B, T, C, I, drop, d_item, d_pos, ctx.c_true)
+        return (d_item, d_pos) + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------------
@@ -988,7 +1002,7 @@ class EmbedFn(torch.autograd.Function):
     no position table."""
 
     @staticmethod
-    def forward(ctx, item_master, item_c, ids, drop: Drop, act_dtype, c_true=0):
+    def forward(ctx, item_master, item_c, ids, drop: Drop, act_dtype, c_true=0, deterministic=False):
         B, T = ids.shape
         I, C = item_c.shape
         x0 = torch.empty((B, T, C), device=ids.device, dtype=act_dtype)
@@ -996,6 +1010,7 @@ class EmbedFn(torch.autograd.Function):
                                         drop.stream_id, _ptr(x0), None, None, int(c_true), _DT[act_dtype], _stream()),
               "edgl_embed_pos_fwd")
         ctx.c_true = int(c_true)
+        ctx.deterministic = bool(deterministic)
         ctx.save_for_backward(ids)
         ctx.meta = (B, T, C, I, drop, item_master.shape)
         return x0
@@ -1006,9 +1021,8 @@ class EmbedFn(torch.autograd.Function):
         B, T, C, I, drop, ishape = ctx.meta
         dx0 = dx0.contiguous()
         d_item = torch.empty(ishape, device=dx0.device, dtype=torch.float32)
-        check(lib.edgl_embed_pos_bwd_ct(_ptr(ids), _ptr(dx0), B, T, C, I, float(drop.rate), drop.ptr(), drop.stream_id,
-                                        _ptr(d_item), None, ctx.c_true, _code(dx0), _stream()), "edgl_embed_pos_bwd")
-        return d_item, None, None, None, None, None
+        _embed_pos_bwd(ctx.deterministic, ids, dx0, B, T, C, I, drop, d_item, None, ctx.c_true)
+        return d_item, None, None, None, None, None, None
 
 
 class MaskRowsFn(torch.autograd.Function):
@@ -1095,11 +1109,14 @@ class TiAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, resid, posK, posV, ktime, vtime, ktime_c, vtime_c, ids, ts, H, time_scale, timelen, drop: Drop,
-                qk_scale=0.0):
+                qk_scale=0.0, deterministic=False):
+        """deterministic: the interval bins of the forward and of the query sweep are filled in a fixed order (TATTN_ORDERED) and
+        the interval-table gradients are summed from per-split slabs (edgl_tiattn_bwd_det)."""
         B, T, C = q.shape
         dh = C // H
         q, kv, resid = q.contiguous(), kv.contiguous(), resid.contiguous()
         code = _code(q)
+        flags = _lib.TATTN_CAUSAL | (_lib.TATTN_ORDERED if deterministic else 0)
         kvp = torch.empty_like(kv)
         check(lib.edgl_add_pos2(_ptr(kv), _ptr(posK), _ptr(posV), B, T, C, _ptr(kvp), code, _stream()), "edgl_add_pos2")
         out = torch.empty((B, T, C), device=q.device, dtype=q.dtype)
@@ -1113,8 +1130,9 @@ class TiAttnFn(torch.autograd.Function):
         check(lib.edgl_tiattn_fwd(_ptr(q), C, _ptr(kvp), 2 * C, _vptr(kvp[:, :, C:]), 2 * C, _ptr(resid), C, _ptr(ids), _ptr(ts),
                                   _ptr(ktime_c), _ptr(vtime_c), rows, B, T, H, dh, scale, float(time_scale), int(timelen),
                                   float(drop.rate), drop.ptr(), drop.stream_id, _ptr(out), C, _ptr(saved), _ptr(wbuf),
-                                  _lib.TATTN_CAUSAL, code, _stream()), "edgl_tiattn_fwd")
+                                  flags, code, _stream()), "edgl_tiattn_fwd")
         ctx.save_for_backward(q, kvp, ktime_c, vtime_c, ids, ts, saved, wbuf)
+        ctx.deterministic = bool(deterministic)
         ctx.meta = (B, T, C, H, dh, scale, float(time_scale), int(timelen), drop, posK.shape, posV.shape, rows)
         return out
 
@@ -1128,17 +1146,21 @@ class TiAttnFn(torch.autograd.Function):
         dgbuf = torch.empty_like(wbuf)   # binned score gradients
         d_kt = torch.empty((rows, C), device=q.device, dtype=torch.float32)
         d_vt = torch.empty_like(d_kt)
-        check(lib.edgl_tiattn_bwd(_ptr(q), C, _ptr(kvp), 2 * C, _vptr(kvp[:, :, C:]), 2 * C, _ptr(ids), _ptr(ts), _ptr(ktime_c),
-                                  _ptr(vtime_c), rows, _ptr(d_out), C, _ptr(saved), _ptr(wbuf), B, T, H, dh, scale, time_scale,
-                                  timelen, float(drop.rate), drop.ptr(), drop.stream_id, _ptr(d_q), C, _ptr(d_kv), 2 * C,
-                                  _vptr(d_kv[:, :, C:]), 2 * C, _ptr(dgbuf), _ptr(d_kt), _ptr(d_vt), _lib.TATTN_CAUSAL, code,
-                                  _stream()), "edgl_tiattn_bwd")
+        head = (_ptr(q), C, _ptr(kvp), 2 * C, _vptr(kvp[:, :, C:]), 2 * C, _ptr(ids), _ptr(ts), _ptr(ktime_c), _ptr(vtime_c), rows,
+                _ptr(d_out), C, _ptr(saved), _ptr(wbuf), B, T, H, dh, scale, time_scale, timelen, float(drop.rate), drop.ptr(),
+                drop.stream_id, _ptr(d_q), C, _ptr(d_kv), 2 * C, _vptr(d_kv[:, :, C:]), 2 * C, _ptr(dgbuf), _ptr(d_kt), _ptr(d_vt))
+        if ctx.deterministic:
+            ws = torch.empty(int(lib.edgl_tiattn_det_workspace(H, dh, timelen)), device=q.device, dtype=torch.float32)
+            check(lib.edgl_tiattn_bwd_det(*head, _ptr(ws), _lib.TATTN_CAUSAL | _lib.TATTN_ORDERED, code, _stream()),
+                  "edgl_tiattn_bwd_det")
+        else:
+            check(lib.edgl_tiattn_bwd(*head, _lib.TATTN_CAUSAL, code, _stream()), "edgl_tiattn_bwd")
         d_pos = colsum(d_kv.view(B, T * 2 * C), B, T * 2 * C).view(T, 2 * C)     # the tables enter K and V additively
         d_pk = torch.zeros(pk_shape, device=q.device, dtype=torch.float32)
         d_pv = torch.zeros(pv_shape, device=q.device, dtype=torch.float32)
         d_pk[:T] = d_pos[:, :C]
         d_pv[:T] = d_pos[:, C:]
-        return d_q, d_kv, d_out, d_pk, d_pv, d_kt, d_vt, None, None, None, None, None, None, None, None, None
+        return d_q, d_kv, d_out, d_pk, d_pv, d_kt, d_vt, None, None, None, None, None, None, None, None, None, None
 
 
 
@@ -1184,25 +1206,31 @@ class EmbeddingFn(torch.autograd.Function):
     table_c is the compute copy of the table (the f32 master, or its bf16 shadow); the gradient goes to the master."""
 
     @staticmethod
-    def forward(ctx, table_master, table_c, ids, zero_pad, scale):
+    def forward(ctx, table_master, table_c, ids, zero_pad, scale, deterministic=False):
+        """deterministic: the backward sums the rows of every index over a sorted plan (edgl_embedding_bwd_det), no f32 atomics."""
         ids = ids.contiguous()
         rows, C = table_c.shape
         out = torch.empty(tuple(ids.shape) + (C,), device=ids.device, dtype=table_c.dtype)
         check(lib.edgl_embedding_fwd(_ptr(ids), ids.numel(), _ptr(table_c), rows, C, int(bool(zero_pad)), float(scale), _ptr(out),
                                      _code(table_c), _stream()), "edgl_embedding_fwd")
         ctx.save_for_backward(ids)
-        ctx.meta = (rows, C, int(bool(zero_pad)), float(scale))
+        ctx.meta = (rows, C, int(bool(zero_pad)), float(scale), bool(deterministic))
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         (ids,) = ctx.saved_tensors
-        rows, C, zero_pad, scale = ctx.meta
+        rows, C, zero_pad, scale, deterministic = ctx.meta
         d_out = d_out.contiguous()
         d_table = torch.empty((rows, C), device=d_out.device, dtype=torch.float32)
-        check(lib.edgl_embedding_bwd(_ptr(ids), ids.numel(), _ptr(d_out), rows, C, zero_pad, scale, _ptr(d_table), _code(d_out),
-                                     _stream()), "edgl_embedding_bwd")
-        return d_table, None, None, None, None
+        if deterministic:
+            plan = segsum_plan_buffer(ids.numel(), rows + 1, d_out.device)
+            check(lib.edgl_embedding_bwd_det(_ptr(ids), ids.numel(), _ptr(d_out), rows, C, zero_pad, scale, _ptr(d_table), _ptr(plan),
+                                             _code(d_out), _stream()), "edgl_embedding_bwd_det")
+        else:
+            check(lib.edgl_embedding_bwd(_ptr(ids), ids.numel(), _ptr(d_out), rows, C, zero_pad, scale, _ptr(d_table), _code(d_out),
+                                         _stream()), "edgl_embedding_bwd")
+        return d_table, None, None, None, None, None
 
 
 def time_sinusoid(x: torch.Tensor, tscale: torch.Tensor, num_units: int, dtype=torch.float32) -> torch.Tensor:

@@ -196,8 +196,11 @@ def run(FLAGS) -> Dict[str, float]:
         FLAGS.mark_table = F.load_mark_table(FLAGS.mark, FLAGS.num_items)
     FLAGS.compute_dtype = getattr(FLAGS, "dtype", "bf16")
     if getattr(FLAGS, "deterministic", False) and FLAGS.model != "EasyDGL":
-        # the regressive models keep f32-atomic scatters (k_data.hip, k_tattn.hip): the promise must never silently not hold
-        raise ValueError(f"--deterministic covers --model EasyDGL only (got {FLAGS.model}): DESIGN 4.9")
+        # The regressive models have their ordered forms too and take the mode through FLAGS.deterministic /
+        # ranking(FLAGS); this driver keeps its refusal for them (tests/test_cpu_segsum.py pins it: lifting it is a change of
+        # existing behaviour of its own).  The promise must never silently not hold.
+        raise ValueError(f"--deterministic: this driver runs the mode for --model EasyDGL only (got {FLAGS.model}); "
+                         f"build the model with FLAGS.deterministic instead: DESIGN 4.9")
     model = ranking(FLAGS)
     model.finalize(torch.device("cuda", torch.cuda.current_device()))
     bs = FLAGS.batch_size

@@ -223,6 +223,12 @@ int edgl_embed_pos_fwd_ct(const int64_t* ids, const float* ts, const void* item_
 int edgl_embed_pos_bwd_ct(const int64_t* ids, const void* dx0, int B, int T, int C, int I, float drop_rate,
                           const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos, int c_true,
                           int dtype, void* stream);
+/* edgl_embed_pos_bwd_ct without f32 atomics: the item rows are summed over a plan of ids that the call builds in
+ * `plan` (edgl_segsum_plan_bytes of (B * T, I) bytes, 16-byte aligned; key 0 is cut off), d_pos[t] is the sum over b in
+ * ascending order.  Same masks and scale; d_item and d_pos are overwritten; one writer per element.  C % 4 == 0, C <= 512. */
+int edgl_embed_pos_bwd_det(const int64_t* ids, const void* dx0, int B, int T, int C, int I, float drop_rate,
+                           const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos, int c_true, void* plan,
+                           int dtype, void* stream);
 
 /* ---- K2/K4: dense layers — tf.layers.dense (temporal.py:409, EasyDGL.py:113,120,125,138) ------
  * C[M,N] = epilogue( sum_k A(m,k) * B(k,n) ).
@@ -794,7 +800,21 @@ int edgl_mask_rows(const void* x, const int64_t* ids, void* y, long rows, int C,
  * applied.  T <= 256.  saved: edgl_tattn_saved_bytes(B,T,H,dh) bytes; wbuf: edgl_tiattn_bucket_elems elements of `dtype` (binned
  * probabilities, read by the backward); both NULL for inference.  timelen <= 256.
  * edgl_tiattn_bwd: d_q, d_k, d_v; d_ktime, d_vtime f32 [tab_rows, H*dh] (overwritten); dgbuf: workspace like wbuf
- * (binned score gradients). */
+ * (binned score gradients).
+ * flags: EDGL_TATTN_CAUSAL, and EDGL_TATTN_ORDERED: the forward and the query sweep of the backward fill their
+ * per-query interval bins in a fixed order (ascending key) with plain loads and stores instead of f32 atomics — out, wbuf, dgbuf
+ * and d_q are then the same bits in every call.
+ * edgl_tiattn_bwd_det: edgl_tiattn_bwd with the ordered query sweep and the interval-table gradients without atomics: every
+ * row split stores its partial tile to its own slab of `workspace` (edgl_tiattn_det_workspace floats, 16-byte aligned, as
+ * d_ktime and d_vtime), one more launch adds the slabs in split order.  The size query is a host function; -1 for bad shapes. */
+#define EDGL_TATTN_ORDERED 2
+long edgl_tiattn_det_workspace(int H, int dh, int timelen);
+int edgl_tiattn_bwd_det(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const int64_t* ids,
+                        const float* ts, const void* ktime, const void* vtime, int tab_rows, const void* d_out, int ld_do,
+                        void* saved, void* wbuf, int B, int T, int H, int dh, float scale, float time_scale, int timelen,
+                        float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, int ld_dq, void* d_k,
+                        int ld_dk, void* d_v, int ld_dv, void* dgbuf, float* d_ktime, float* d_vtime, float* workspace,
+                        int flags, int dtype, void* stream);
 long edgl_tiattn_bucket_elems(int B, int T, int H, int timelen);
 int edgl_tiattn_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* resid, int ldr,
                     const int64_t* ids, const float* ts, const void* ktime, const void* vtime, int tab_rows, int B, int T,
@@ -828,6 +848,10 @@ int edgl_embedding_fwd(const int64_t* ids, long n, const void* table, int rows, 
                        int dtype, void* stream);
 int edgl_embedding_bwd(const int64_t* ids, long n, const void* d_out, int rows, int C, int zero_pad, float scale,
                        float* d_table, int dtype, void* stream);
+/* edgl_embedding_bwd without f32 atomics: ordered sums over a plan of ids built by the call in `plan`
+ * (edgl_segsum_plan_bytes of (n, rows + 1) bytes, 16-byte aligned).  zero_pad cuts index 0 off; C % 4 == 0, C <= 512. */
+int edgl_embedding_bwd_det(const int64_t* ids, long n, const void* d_out, int rows, int C, int zero_pad, float scale,
+                           float* d_table, void* plan, int dtype, void* stream);
 int edgl_time_sinusoid(const float* x, long n, const float* tscale, int C, void* out, int dtype, void* stream);
 int edgl_time_function_fwd(const float* x, long n, const float* freq, const float* phase, int C, void* out, int dtype,
                            void* stream);
