@@ -17,7 +17,9 @@
 #include <cstdlib>
 
 #include "edgl_common.h"
+#include <cstring>
 #include "encode_scatter.h"
+#include "tn_group.h"
 
 typedef __attribute__((ext_vector_type(4))) short tr_s16x4;
 
@@ -715,11 +717,34 @@ __device__ __forceinline__ void dx_encode_epilogue(const DxEncP& x, bf16* Os, in
     }
 }
 
-// The mapped QKVT dX GEMM with the embedding backward in its epilogue; behind the GEMM's workgroups (block-uniform branch): the label
-// job of the scatter (x.lab_blocks workgroups), then the riding reduction list (rb.blocks).
-__global__ __launch_bounds__(G_NT, 3) void dx_encode_kernel(StripP p, DxEncP x, RedBatch rb) {
+template <int TM>
+__device__ __forceinline__ void tn_body(const TnP& p, int bx, int by, int bz, bf16* Xs, bf16* Ys);
+
+// The mapped QKVT dX GEMM with the embedding backward in its epilogue.  In front of the GEMM's workgroups (block-uniform branch):
+// tn_blocks workgroups (a multiple of 8, 0 = none) with the tiles of a grouped weight-gradient launch (edgl_gemm_dw_ride, DESIGN rule
+// 79) on the same 36 KB of dynamic LDS; behind them: the label job of the scatter (x.lab_blocks workgroups), then the riding reduction
+// list (rb.blocks).
+__global__ __launch_bounds__(G_NT, 3) void dx_encode_kernel(StripP p, DxEncP x, RedBatch rb, TnGroupP g, int tn_blocks) {
+    static_assert(sizeof(StripP) + sizeof(DxEncP) + sizeof(RedBatch) + sizeof(TnGroupP) + sizeof(int) < 4096, "kernel arguments: 4 KB");
+    static_assert(T_NT == G_NT && 2 * T_BR * T_LD * (int)sizeof(bf16) <= DXE_LDS, "the TN tiles run in this kernel's workgroup shape and LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int bid = (int)blockIdx.x;
+    const int bid0 = (int)blockIdx.x;
+    const int bid = bid0 - tn_blocks;
+    if (bid0 < tn_blocks) {
+        // The long workgroups first: the dX tiles fill the slots they leave (measured against dX tiles first and against the two
+        // interleaved at their fixed ratio: only this order gains, profiles/dw_ride.txt section 1).
+        // (the tiles of one row split are consecutive ids: with the XCD-aware order they share one L2)
+        const int vid = xcd_virtual_id(bid0, tn_blocks, g.blk0[g.n]);
+        if (vid < 0) return;
+        int j = 0;
+        for (int i = 1; i < g.n; ++i)
+            if (vid >= g.blk0[i]) j = i;
+        const int local = vid - g.blk0[j];
+        const int tn = g.tiles_n[j], tk = g.tiles_k[j];
+        bf16* Xs = reinterpret_cast<bf16*>(smem);
+        tn_body<128>(g.job[j], local % tn, (local / tn) % tk, local / (tn * tk), Xs, Xs + T_BR * T_LD);
+        return;
+    }
     if (bid >= x.gemm_blocks) {
         const int e = bid - x.gemm_blocks;
         bf16* Gs = reinterpret_cast<bf16*>(smem);
@@ -750,16 +775,7 @@ static int launch_tile_nn(const StripP& p, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // TN GEMM (dW / db)
 // ------------------------------------------------------------------------------------------------
-constexpr int T_NT = 256, T_BR = 64, T_LD = 128 + 16;   // T_BR rows per step (128-row steps measured: grouped dW 70 -> 81 us)
-
-struct TnP {
-    const bf16* X; const bf16* Y; int R, Kf, N, ldx, ldy;
-    int rows_per_split;
-    float* partial;   // [splits][Kf + 1][N]  (row Kf = column sums of Y)
-    int with_colsum;
-    int tiles_n, tiles_k, nblocks;   // tn_gemm_kernel: 1-D grid (padded to a multiple of 8 with the XCD-aware order)
-};
-
+// (T_NT, T_BR, TnP, TnGroupP and the layout of a group: tn_group.h)
 // TM = output tile edge of a workgroup (4 waves in a 2 x 2 arrangement).  64-tiles quarter the partial slabs of the 128 x 128 layers
 // but every operand column block is then read by twice as many workgroups: measured +18 us in the GEMMs for -12 us in the slab
 // reduction.
@@ -878,8 +894,6 @@ __global__ __launch_bounds__(T_NT) void tn_gemm_kernel(TnP p) {
 // Several weight-gradient GEMMs in ONE launch (edgl_gemm_dw_defer): the dW products of a block are independent of each
 // other and individually too small for the chip — the 128 x 128 layers run two 64-row steps per workgroup and leave 25 MB of
 // partial slabs each.  Grouped, they share the launch with the wide QKVT product and get row splits of similar length.
-constexpr int TN_MAX_JOBS = 8;
-struct TnGroupP { TnP job[TN_MAX_JOBS]; int tiles_n[TN_MAX_JOBS], tiles_k[TN_MAX_JOBS], blk0[TN_MAX_JOBS + 1]; int n; };
 __global__ __launch_bounds__(T_NT) void tn_gemm_group_kernel(TnGroupP g) {
     extern __shared__ __attribute__((aligned(16))) char tn_smem[];
     bf16* Xs = reinterpret_cast<bf16*>(tn_smem);
@@ -976,32 +990,16 @@ int edgl_gemm2_try_strip(const void* A, const void* B, void* C, int M, int N, in
 
 // C[Kf,N] = X^T . Y (f32, overwritten or accumulated); if dbias != nullptr also dbias[N] = colsum(Y).
 // workspace floats: edgl_gemm2_tn_workspace(R, Kf, N).
-// Row splits of a TN product (or of a group of them: `tiles` output tiles in all, `out_elems` f32 of output in all, `flop` =
-// 2 R sum(Kf N)).  The chip takes workgroups in rounds of its CU count: 192 tiles x 2 splits = 384 workgroups run as TWO
-// rounds (the 512-unit QKVT weight gradient: 229 us), x 4 = 768 as three of half the length (143 us) — but every split
-// leaves a [Kf+1, N] f32 slab that a second kernel sums (384 workgroups over a 128 x 128 output meant 25 MB of partials for a
-// 64 KB result).  Both sides priced (rates measured on the part: ~0.6 PFLOP/s of this kernel when every round is full, 3 us
-// of prologue / slab write per workgroup, x1.25 below two resident workgroups per CU, ~4 TB/s of slab reduction), the
-// cheapest split count wins: 4 for that product (768 workgroups), 28 for the headline's grouped launch (504, as before).
-static int tn_choose_splits(int R, int tiles, double flop, double out_elems, int cap) {
-    const int smax = std::max(1, std::min(cap, R / 128));
+// (row splits: tn_choose_splits_on, tn_group.h)
+static int tn_cus() {
     static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         return n;
     }();
-    int best = 1;
-    double best_t = 1e30;
-    for (int sp = 1; sp <= smax; ++sp) {
-        const long wg = (long)tiles * sp;
-        const long rounds = (wg + cus - 1) / cus;
-        double t = (double)rounds * (flop / (double)wg / (0.6e15 / cus) + 3e-6);   // + a workgroup's fixed part (its 64 KB slab)
-        if (4 * wg < 7L * cus) t *= 1.25;   // fewer than ~two workgroups per CU: nothing hides a workgroup's barriers
-        if (sp > 1) t += (double)sp * out_elems * 4.0 / 4e12 + 3e-6;
-        if (t < best_t * 0.999) { best_t = t; best = sp; }
-    }
-    return best;
+    return cus;
 }
+static int tn_choose_splits(int R, int tiles, double flop, double out_elems, int cap) { return tn_choose_splits_on(tn_cus(), R, tiles, flop, out_elems, cap); }
 static int tn_splits(int R, int Kf, int N) {
     const int tiles = ((Kf + 127) / 128) * ((N + 127) / 128);
     return tn_choose_splits(R, tiles, 2.0 * R * Kf * N, (double)(Kf + 1) * N, 1 << 20);
@@ -1019,46 +1017,18 @@ static int tn_reduce(const float* workspace, int splits, float* C, int Kf, int N
 }
 
 // ---- deferred / grouped mode -------------------------------------------------------------------------------------------
-struct TnQueued { TnP p; float* C; float* dbias; int accumulate, max_splits; };
 thread_local bool g_tn_defer = false;
 thread_local int g_tn_n = 0;
 thread_local TnQueued g_tn_q[TN_MAX_JOBS];
+thread_local bool g_tn_ride = false;    // edgl_gemm_dw_ride: the queue may leave with the launch of edgl_dx_encode_bwd_label
 
 static int tn_flush(hipStream_t st) {
     const int n = g_tn_n;
     g_tn_n = 0;
     if (n == 0) return EDGL_OK;
     TnGroupP g;
-    g.n = n;
-    int total_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        g.tiles_n[i] = (g_tn_q[i].p.N + 127) / 128;
-        g.tiles_k[i] = (g_tn_q[i].p.Kf + 127) / 128;
-        total_tiles += g.tiles_n[i] * g.tiles_k[i];
-    }
-    // one split count for the whole group (row ranges of similar length), capped by what each job's workspace was sized for
-    double flop = 0.0, elems = 0.0;
-    int rmin = 1 << 30;
-    for (int i = 0; i < n; ++i) {
-        const TnP& q = g_tn_q[i].p;
-        flop += 2.0 * q.R * q.Kf * q.N;
-        elems += (double)(q.Kf + 1) * q.N;
-        rmin = std::min(rmin, q.R);
-    }
-    const int group_splits = tn_choose_splits(rmin, total_tiles, flop, elems, 1 << 20);
-    int splits[TN_MAX_JOBS], blocks = 0;
-    for (int i = 0; i < n; ++i) {
-        TnP& p = g_tn_q[i].p;
-        int sp = std::max(1, std::min(std::min(group_splits, g_tn_q[i].max_splits), p.R / 128));
-        const int rps = ((p.R + sp - 1) / sp + T_BR - 1) / T_BR * T_BR;
-        sp = (p.R + rps - 1) / rps;
-        p.rows_per_split = rps;
-        splits[i] = sp;
-        g.job[i] = p;
-        g.blk0[i] = blocks;
-        blocks += g.tiles_n[i] * g.tiles_k[i] * sp;
-    }
-    g.blk0[n] = blocks;
+    int splits[TN_MAX_JOBS];
+    const int blocks = tn_group_layout(g_tn_q, n, tn_cus(), &g, splits);
     const size_t tn_lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
     hipFuncSetAttribute((const void*)tn_gemm_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn_lds);
     hipLaunchKernelGGL(tn_gemm_group_kernel, dim3(xcd_grid(blocks)), dim3(T_NT), tn_lds, st, g);
@@ -1075,6 +1045,7 @@ static int tn_flush(hipStream_t st) {
 // followed by their slab reductions; on < 0: forget the queue.  The operands and workspaces of queued calls must stay
 // untouched until the flush; a full queue flushes itself.
 int edgl_gemm2_tn_defer(int on, hipStream_t st) {
+    if (on <= 0) g_tn_ride = false;      // (a riding request ends with the grouped mode it belongs to)
     if (on < 0) { g_tn_n = 0; g_tn_defer = false; return EDGL_OK; }
     if (!on && g_tn_defer) {
         g_tn_defer = false;
@@ -1110,6 +1081,14 @@ int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int
     return rc ? rc : 1;
 }
 
+// on = 1, in grouped mode: the next edgl_dx_encode_bwd_label call of this thread takes the queue along as workgroups of its own launch
+// (DESIGN rule 79); on = 0, or leaving / aborting the grouped mode, withdraws the request.
+extern "C" int edgl_gemm_dw_ride(int on) {
+    EDGL_REQUIRE(on == 0 || on == 1, EDGL_ERR_SHAPE, "edgl_gemm_dw_ride: on = %d (0: off, 1: the queued products ride in the launch of edgl_dx_encode_bwd_label)", on);
+    g_tn_ride = on != 0;
+    return EDGL_OK;
+}
+
 // ---- QKVT dX GEMM of the first block + embedding backward + label term in one launch -----------------------------------------------
 // 1 iff the fused form exists for the shape: bf16, C = 128, at most 16 chunks of 128 samples, and the padding of the last chunk
 // (samples past the batch, computed and dropped) at most B / 8 rows
@@ -1123,6 +1102,9 @@ extern "C" int edgl_dx_encode_supported(int B, int T, int C, int dtype) {
 // consumed in the GEMM's epilogue by what edgl_encode_bwd_add_label computes from it: d_item (+ add1 / add2, dropout, label term,
 // d_bias), d_pos, d_mark_emb.  dX0 is written only when dx0_out != NULL ([B*T, 3C], bit-identical to edgl_gemm).  The thread's queued
 // reductions ride as extra workgroups (edgl_reduce_ride); the call's own two follow in one launch (queued in deferred mode without riding).
+// With edgl_gemm_dw_ride(1) a non-empty queue of the grouped weight-gradient mode leaves with this launch as well: its tiles are
+// workgroups in front of the GEMM's, its slab reductions go with the call's own two — never into the riding list, which is taken
+// first and holds only partials of earlier launches.  A queue that cannot ride (tn_ride_plan) is flushed in front of the call.
 extern "C" int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int lda, int ldb, void* dx0_out, const int64_t* ids,
                                         const uint8_t* marks, const void* add1, const void* add2, int B, int T, int C, int E, int I,
                                         float drop_rate, const uint64_t* rng_state, uint32_t stream_id, float* d_item, float* d_pos,
@@ -1153,6 +1135,22 @@ extern "C" int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int ld
     x.gemm_blocks = xcd_grid(chunks * T * nbn);
     x.lab_blocks = (lab_R + SROWS - 1) / SROWS;
     x.dx0_out = reinterpret_cast<bf16*>(dx0_out);
+    // the two reductions of this call (only row 1 of the mark-embedding table is ever indexed: EasyDGL.py:87-88)
+    const RedJob own[2] = {{part_pos, d_pos, (long)T * C, chunks, T * C, 0, 1}, {part_mk, E > 1 ? d_mark_emb + C : d_mark_emb, (long)C, chunks * T, C, 0, 1}};
+    const int nown = E > 1 ? 2 : 1;
+    TnRidePlan tn;
+    std::memset(&tn.g, 0, sizeof(tn.g));
+    int tn_n = 0, tn_blocks = 0;
+    if (g_tn_ride && g_tn_defer && g_tn_n > 0) {
+        if (tn_ride_plan(g_tn_q, g_tn_n, tn_cus(), nown, &tn)) {
+            tn_n = g_tn_n;
+            tn_blocks = xcd_grid(tn.blocks);
+        } else {
+            std::memset(&tn.g, 0, sizeof(tn.g));
+            const int rc = tn_flush(st);
+            if (rc) return rc;
+        }
+    }
     RedBatch rb;
     rb.n = rb.blocks = 0;
     int first = 0;
@@ -1161,14 +1159,20 @@ extern "C" int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int ld
     StripP p{(const bf16*)dqkvt, (const bf16*)W, dx0_out, B * T, 3 * C, 4 * C, lda, ldb, 3 * C, EpiP{nullptr, nullptr, 0}};
     const size_t smem = std::max((size_t)2 * G_BM * G_LDK * sizeof(bf16), (size_t)DXE_LDS);
     hipFuncSetAttribute((const void*)dx_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(dx_encode_kernel, dim3((unsigned)(x.gemm_blocks + x.lab_blocks + nred)), dim3(G_NT), smem, st, p, x, rb);
+    g_tn_n -= tn_n;      // (the queue has left: a later edgl_gemm_dw_defer(0) finds it empty)
+    hipLaunchKernelGGL(dx_encode_kernel, dim3((unsigned)(tn_blocks + x.gemm_blocks + x.lab_blocks + nred)), dim3(G_NT), smem, st, p, x, rb, tn.g, tn_blocks);
     EDGL_LAUNCH_CHECK();
-    // the two reductions of this call (only row 1 of the mark-embedding table is ever indexed: EasyDGL.py:87-88)
-    const RedJob own[2] = {{part_pos, d_pos, (long)T * C, chunks, T * C, 0, 1}, {part_mk, E > 1 ? d_mark_emb + C : d_mark_emb, (long)C, chunks * T, C, 0, 1}};
-    const int nown = E > 1 ? 2 : 1;
-    if (nred > 0) return edgl_reduce_rows_now(own, nown, st);
+    if (nred > 0) {      // the list rode: the call's own reductions and the slabs of the riding products in ONE launch behind this one
+        for (int i = 0; i < nown; ++i) tn.red[i] = own[i];
+        return edgl_reduce_rows_now(tn_n ? tn.red : own, tn_n ? tn.nred : nown, st);
+    }
     for (int i = 0; i < nown; ++i) {
         const int rc = edgl_reduce_rows_f64(own[i].part, own[i].P, own[i].N, own[i].ld, own[i].out, st);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < tn_n; ++i) {      // queued in deferred mode, as tn_flush queues them
+        const TnP& q = tn.g.job[i];
+        const int rc = tn_reduce(q.partial, tn.splits[i], g_tn_q[i].C, q.Kf, q.N, g_tn_q[i].dbias, 0, st);
         if (rc) return rc;
     }
     return EDGL_OK;

@@ -49,6 +49,8 @@ class TrainEngine:
                                  scatter's instead of in front of them (the measured alternative, DESIGN rule 76)
         EDGL_DX_ENCODE=0         the QKVT dX GEMM of the first block, then the embedding backward as launches of their own, instead of
                                  the GEMM with the embedding backward in its epilogue (edgl_dx_encode_bwd_label, DESIGN rule 78)
+        EDGL_DW_RIDE=0           the grouped weight-gradient launch of the first block in front of that launch instead of its tiles as
+                                 workgroups of it (edgl_gemm_dw_ride, DESIGN rule 79)
 
     EDGL_SCORE_STRIP belongs to the library (csrc/k_score_strip.hip latches it once per process); the engine reads it at the same
     place because only the strip passes leave the one-hot term of the table gradient to the embedding scatter (`_label_fused`)."""
@@ -68,6 +70,7 @@ class TrainEngine:
         self.sw_reduce_ride = env("EDGL_REDUCE_RIDE", "1") != "0"
         self.sw_reduce_ride_behind = env("EDGL_REDUCE_RIDE", "1") == "2"
         self.sw_dx_encode = env("EDGL_DX_ENCODE", "1") != "0"
+        self.sw_dw_ride = env("EDGL_DW_RIDE", "1") != "0"
         self.sw_score_strip = env("EDGL_SCORE_STRIP", "1") != "0"      # (the library's: csrc/k_score_strip.hip latches it per process)
         self.m = model
         self.B = batch
@@ -232,6 +235,9 @@ class TrainEngine:
         # (bf16, C = 64 / 128, every job in the vector form, no output inside the scatter's targets); what does not is flushed as
         # before.  Deterministic mode keeps its launch sequence (the ordered sums are not this launch).
         self.reduce_ride = self.sw_reduce_ride and not self.deterministic
+        # The grouped weight-gradient tiles of the first block leave with the launch of edgl_dx_encode_bwd_label (DESIGN rule 79); the
+        # library runs a group that cannot ride in front of the call, as before.  Deterministic mode keeps its launch sequence.
+        self.dw_ride = self.sw_dw_ride and not self.deterministic
         self._rng_alt, self._adam_alt = torch.zeros_like(m._rng_state), torch.zeros_like(m._adam_state)
         self._slabs = None          # (table slabs ptr, bias slabs ptr, nslab) left by the scoring backward of the current step
         self._slab_info = None
@@ -723,15 +729,21 @@ class TrainEngine:
                                              _ptr(self._ws(lib.edgl_bimau_bwd_workspace(B, T, C, H, E, code), torch.uint8)),
                                              _ptr(self.job_order), self.mau_flags, code, st), "edgl_bimau_bwd_ord")
             self._dense_dw(x_in, self.G4c, att.dense_kernel, att.dense_bias, cin, 4 * C)
-            if self.fused_tail:
+            dx_encode = i == 0 and self._label_fused and self.sw_dx_encode and not self.deterministic and cin == 3 * C and \
+                bool(lib.edgl_dx_encode_supported(B, T, C, code))
+            # the block's grouped weight-gradient tiles as workgroups of the dX GEMM's launch (edgl_gemm_dw_ride, DESIGN rule 79): the
+            # fused entry is then called BEFORE the grouped mode is left, which finds its queue empty
+            dw_ride = dx_encode and self.dw_ride and self.fused_tail and not self.mgroups
+            if self.fused_tail and not dw_ride:
                 check(lib.edgl_gemm_dw_defer(0, st), "edgl_gemm_dw_defer")
             d_in = self.G3c if i == 0 else self.G3
-            if i == 0 and self._label_fused and self.sw_dx_encode and not self.deterministic and cin == 3 * C and \
-                    lib.edgl_dx_encode_supported(B, T, C, code):
+            if dx_encode:
                 # dX0 is consumed in the epilogue of the GEMM that produces it and never written (G3c stays untouched)
                 self._issue_backward_end()
                 if self.reduce_ride:
                     check(lib.edgl_reduce_ride(2 if self.sw_reduce_ride_behind else 1), "edgl_reduce_ride")
+                if dw_ride:
+                    check(lib.edgl_gemm_dw_ride(1), "edgl_gemm_dw_ride")
                 d0 = drop(hd, 1)
                 check(lib.edgl_dx_encode_bwd_label(_ptr(self.G4c), _ptr(self.m.compute(att.dense_kernel)), 4 * C, 4 * C, None,
                                                    _ptr(self.ids), _ptr(self.marks), _ptr(self.G1), _ptr(self.G2), B, T, C, E, I,
@@ -740,6 +752,8 @@ class TrainEngine:
                                                    _ptr(self._ws(lib.edgl_encode_bwd_workspace(B, T, C))), self.c_true,
                                                    _ptr(self.hrows_c), _ptr(lab), _ptr(self.coef), _ptr(self.nvalid), R,
                                                    _ptr(m.output_bias.grad), code, st), "edgl_dx_encode_bwd_label")
+                if dw_ride:
+                    check(lib.edgl_gemm_dw_defer(0, st), "edgl_gemm_dw_defer")
                 return
             self._dense_dx(self.G4c, att.dense_kernel, d_in, cin, 4 * C)
             if i == 0:

@@ -251,6 +251,13 @@ int edgl_gemm_dw(const void* X, const void* dY, float* dW, float* dbias, int R, 
  * their slab reductions.  Operands and workspaces of queued calls must stay untouched until then.  on < 0: drop the queue
  * without launching (error exit). */
 int edgl_gemm_dw_defer(int on, void* stream);
+/* edgl_gemm_dw_ride(1), in grouped mode: the next edgl_dx_encode_bwd_label call of this thread takes the queued products along as
+ * workgroups of ITS launch (DESIGN rule 79) — the two are independent and each runs far below the chip's limits by itself — and issues
+ * their slab reductions with its own two, behind that launch; a following edgl_gemm_dw_defer(0) finds the queue empty.  Same dW / db
+ * bits as the grouped launch.  A queue that cannot ride (an accumulating product, outputs the vector-form reduction does not take,
+ * more reduction jobs than one list holds) is run in front of the call as edgl_gemm_dw_defer(0) would.  edgl_gemm_dw_ride(0), or
+ * edgl_gemm_dw_defer(0 | -1), withdraws the request. */
+int edgl_gemm_dw_ride(int on);
 
 /* out[n] (+)= sum_m X[m, n]  — bias gradients.  X `dtype` (or f32 if x_f32) [M, ld]; out f32[N]. */
 int edgl_colsum(const void* X, int M, int N, int ld, float* out, int accumulate, float* workspace,
