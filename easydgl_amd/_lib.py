@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_long, c_uint32, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_int64, c_long, c_uint32, c_uint64, c_void_p
 
 # PyTorch-ROCm bundles its own libamdhip64; it must be in the process BEFORE our library is loaded so that both bind to
 # ONE HIP runtime (same device context, streams and allocations).  Loading libeasydgl_hip.so first pulls in /opt/rocm's
@@ -25,7 +25,7 @@ MAU_STREAM = 16      # host-side hint: the key-streamed BiMAU kernels at a shape
 TATTN_CAUSAL = 1
 TATTN_ORDERED = 2    # interval attention: the LDS bins filled in a fixed order, no f32 atomics
 
-P, I, F, L, U32, I64 = c_void_p, c_int, c_float, c_long, c_uint32, c_int64
+P, I, F, L, U32, I64, U64 = c_void_p, c_int, c_float, c_long, c_uint32, c_int64, c_uint64
 
 # name -> (restype, argtypes) — must list EVERY symbol include/easydgl_hip.h declares
 SIGNATURES = {
@@ -129,6 +129,10 @@ SIGNATURES = {
     "edgl_label_value_tile": (I, [P, I, I, I, P, I, P, P, P]),
     "edgl_rank_count_tile": (I, [P, I, I, I, P, I, P, P, P, P]),
     "edgl_rank_metrics_from_rank": (I, [P, I, P, I, P, P]),
+    "edgl_score_candidates_chunk": (I, [I, I, I, I]),
+    "edgl_score_candidates": (I, [P, P, P, P, P, I, P, I, I, I, I, P, P, P, I, P]),
+    "edgl_sample_negatives": (I, [P, I, P, I, I, I, I, I, U64, U64, I, P, P]),
+    "edgl_rank_metrics_from_rank_rows": (I, [P, I, P, I, P, P]),
     "edgl_topk_merge": (I, [P, P, I, I, I, P, P, P]),
     "edgl_rank_metrics": (I, [P, I, I, P, P, P]),
     "edgl_tpp_workspace": (I, []),

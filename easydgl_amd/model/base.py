@@ -448,6 +448,39 @@ class Sequential(nn.Module):
         logits = self.forward(features, False)
         return ops.rank_from_logits(logits, 0, features["seqs_i"] if mask_seen else None, self._last_labels(labels))
 
+    # ---- evaluation on candidate lists (DESIGN 4.12): sampled negatives and re-ranking -------------------------------------
+    def _last_rows(self, features):
+        """[B, C] rows of the last position: what every evaluation scores."""
+        out = self.encoder(features, False, self._last_pos(features["seqs_i"]))
+        rows = out[0] if isinstance(out, tuple) else out
+        return rows.reshape(-1, self.num_units).contiguous()
+
+    def _negatives_hi(self) -> int:
+        """Negatives are drawn from [1, hi): every item id (a model with a MASK row excludes it)."""
+        return self.num_items
+
+    @torch.no_grad()
+    def score_candidates(self, features, candidates, mask_seen=True):
+        """f32 [B, N]: the logits of each sequence's own candidate list (int32 [B, N]; -1 = empty slot) — re-ranking.  -inf at an
+        empty slot and, with mask_seen, at the ids of the sequence's history.  The item table is read at the listed rows only."""
+        tab = self.item_embs.lookup_table
+        return ops.score_candidates(self._last_rows(features), self.compute(tab), self.output_bias, candidates,
+                                    features["seqs_i"] if mask_seen else None)[0]
+
+    @torch.no_grad()
+    def eval_candidates(self, features, labels, candidates=None, num_negatives=100, mask_seen=True, seed=0, step=0, row0=0):
+        """int32 [B]: the label's place among its candidates in the (logit desc, item id asc) order.  `candidates` int32 [B, N], or
+        None: `num_negatives` ids per sequence drawn from the catalogue by ops.sample_negatives(seed, step, row0) — never an id of
+        the sequence's history and never the label, whatever mask_seen says; mask_seen decides whether seen ids of a caller's list
+        and a seen label read -inf."""
+        lab = self._last_labels(labels)
+        seen = features["seqs_i"]
+        if candidates is None:
+            candidates = ops.sample_negatives(seen, lab, num_negatives, 1, self._negatives_hi(), seed, step, row0)
+        tab = self.item_embs.lookup_table
+        return ops.score_candidates(self._last_rows(features), self.compute(tab), self.output_bias, candidates,
+                                    seen if mask_seen else None, lab, want_scores=False)[2]
+
     def reset_metrics(self, ks=None):
         """`ks`: the cut-offs of the by-rank metrics (eval_step(by_rank=True)); default (10, 50, 100), at most 8."""
         dev = self._arena.device
@@ -461,13 +494,19 @@ class Sequential(nn.Module):
         self._rank_count = 0
 
     @torch.no_grad()
-    def eval_step(self, features, labels, mask_seen=True, by_rank=False):
+    def eval_step(self, features, labels, mask_seen=True, by_rank=False, *, candidates=None, negatives=0, neg_seed=0, row0=0):
+        """`candidates` (int32 [B, N]) or `negatives` > 0: the label is ranked inside the list / among that many sampled negatives
+        (eval_candidates; `row0` = index of the batch's first sequence in its split) and the step accumulates like a by-rank step."""
         if self._metrics is None:
             self.reset_metrics()
-        if by_rank:
+        on_list = candidates is not None or negatives > 0
+        if by_rank or on_list:
             if self._metric_count != self._rank_count:
                 raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
-            ops.rank_metrics_from_rank(self.eval_rank(features, labels, mask_seen), self._rank_ks_dev, self._rank_sums)
+            rank = (self.eval_candidates(features, labels, candidates, negatives, mask_seen, neg_seed, 0, row0) if on_list
+                    else self.eval_rank(features, labels, mask_seen))
+            # (steps on lists add row by row: with `row0` a split gives the same sums whatever the batch size)
+            ops.rank_metrics_from_rank(rank, self._rank_ks_dev, self._rank_sums, row_order=on_list)
             self._rank_count += labels.shape[0]
         else:
             if self._rank_count:

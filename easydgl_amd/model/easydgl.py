@@ -243,6 +243,12 @@ class EasyDGL(Sequential):
     def _gather_pos(self, features, is_training):
         return features["masked_positions"].contiguous() if is_training else self._last_pos(features["seqs_i"])
 
+    def _last_rows(self, features):
+        return self.encoder(features, False, self._gather_pos(features, False))[0].contiguous()
+
+    def _negatives_hi(self) -> int:
+        return self.mask      # (the MASK row is not an item)
+
     # ---- EasyDGL.__call__ ------------------------------------------------------------------------------
     def forward(self, features: Dict[str, torch.Tensor], is_training: bool):
         """Returns logits [B*M, I] (training) / [B, I] (eval), materialised like the reference (:149-151)."""

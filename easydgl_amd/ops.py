@@ -935,12 +935,74 @@ def rank_from_logits(logits: torch.Tensor, i0: int, seen: Optional[torch.Tensor]
     return count
 
 
-def rank_metrics_from_rank(rank: torch.Tensor, ks: torch.Tensor, sums: torch.Tensor) -> None:
-    """sums f32 [2 nk + 1] += (H@k.., N@k.., MRR) of the int32 ranks; ks int32 [nk <= 8] on the device."""
+def rank_metrics_from_rank(rank: torch.Tensor, ks: torch.Tensor, sums: torch.Tensor, row_order: bool = False) -> None:
+    """sums f32 [2 nk + 1] += (H@k.., N@k.., MRR) of the int32 ranks; ks int32 [nk <= 8] on the device.  `row_order`: the rows are
+    added one by one instead of as the batch's tree — the sums of a split then do not depend on how it is cut into batches."""
     if rank.dtype != torch.int32 or ks.dtype != torch.int32 or sums.dtype != torch.float32 or sums.numel() != 2 * ks.numel() + 1:
         raise _lib.EdglError("rank_metrics_from_rank: rank int32 [R], ks int32 [nk], sums f32 [2 nk + 1]")
+    if row_order:
+        check(lib.edgl_rank_metrics_from_rank_rows(_ptr(rank), rank.shape[0], _ptr(ks), ks.numel(), _ptr(sums), _stream()),
+              "edgl_rank_metrics_from_rank_rows")
+        return
     check(lib.edgl_rank_metrics_from_rank(_ptr(rank), rank.shape[0], _ptr(ks), ks.numel(), _ptr(sums), _stream()),
           "edgl_rank_metrics_from_rank")
+
+
+# ---- K6c: evaluation on candidate lists (csrc/k_eval_cand.hip, DESIGN 4.12) — sampled negatives and re-ranking -------------------
+def sample_negatives(seen, labels, n, lo, hi, seed, step=0, row0=0):
+    """int32 [R, n]: per row n ids drawn uniformly from [lo, hi) (with replacement between slots), never one of the row's seen ids
+    (int64 [R, T] or None) and never labels[r] (int64 [R]).  Counter-based on (seed, step, row0 + r, slot): `row0` is the index of the
+    batch's first sequence in its split, so a sequence's list does not depend on the batch size.  Needs 2 (T + 1) <= hi - lo."""
+    _ptr(labels)                                             # (GPU tensors only: refused before anything else)
+    R = labels.shape[0]
+    labels = _rank_labels(labels, R, "sample_negatives")
+    if seen is not None:
+        if seen.dtype != torch.int64 or seen.dim() != 2 or seen.shape[0] != R:
+            raise _lib.EdglError(f"sample_negatives: seen ids must be int64 [{R}, T] (got {seen.dtype} {tuple(seen.shape)})")
+        seen = seen.contiguous()
+    T = 0 if seen is None else seen.shape[1]
+    cand = torch.empty((R, int(n)), device=labels.device, dtype=torch.int32)
+    mask64 = (1 << 64) - 1
+    check(lib.edgl_sample_negatives(_ptr(seen), T, _ptr(labels), R, int(n), int(lo), int(hi), int(hi), int(seed) & mask64,
+                                    int(step) & mask64, int(row0), _ptr(cand), _stream()), "edgl_sample_negatives")
+    return cand
+
+
+def score_candidates(rows, table_c, out_bias, cand, seen=None, labels=None, want_scores=True, count=None):
+    """(scores f32 [R, N] | None, label_val f32 [R] | None, rank int32 [R] | None) of every row's OWN candidate list cand int32 [R, N]:
+    scores[r, n] = rows[r] . table_c[c] + bias_used[c] for c = cand[r, n], -inf for an empty slot (c < 0) and for the row's seen ids
+    (int64 [R, T] or None).  With labels (int64 [R]): label_val = the label's value by the same arithmetic and rank = the number of
+    slots that come before the label in the (value desc, item id asc) order — the label's own slots are not counted, a repeated id
+    counts once per slot.  `count`: an int32 [R] buffer the counts are ADDED into (the lists of one row scored in parts) instead of a
+    fresh one.  A gather of R (N + 1) table rows: no sweep over the catalogue."""
+    _ptr(rows)                                               # (GPU tensors only: refused before anything else)
+    R, C = rows.shape
+    I = table_c.shape[0]
+    if table_c.dtype != rows.dtype or table_c.shape[1] != C:
+        raise _lib.EdglError(f"score_candidates: rows {rows.dtype} [{R}, {C}] against a table {table_c.dtype} {tuple(table_c.shape)}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != R:
+        raise _lib.EdglError(f"score_candidates: candidates must be int32 [{R}, N] (got {cand.dtype} {tuple(cand.shape)})")
+    if seen is not None and (seen.dtype != torch.int64 or seen.dim() != 2 or seen.shape[0] != R):
+        raise _lib.EdglError(f"score_candidates: seen ids must be int64 [{R}, T] (got {seen.dtype} {tuple(seen.shape)})")
+    dev, N = rows.device, cand.shape[1]
+    rows, cand = rows.contiguous(), cand.contiguous()
+    seen = None if seen is None else seen.contiguous()
+    T = 0 if seen is None else seen.shape[1]
+    scores = torch.empty((R, N), device=dev, dtype=torch.float32) if want_scores else None
+    label_val = None
+    if labels is None:
+        if count is not None:
+            raise _lib.EdglError("score_candidates: a count buffer without labels")
+    else:
+        labels = _rank_labels(labels, R, "score_candidates")
+        label_val = torch.empty(R, device=dev, dtype=torch.float32)
+        if count is None:
+            count = torch.zeros(R, device=dev, dtype=torch.int32)
+        elif count.dtype != torch.int32 or count.shape != (R,):
+            raise _lib.EdglError(f"score_candidates: count must be int32 [{R}] (got {count.dtype} {tuple(count.shape)})")
+    check(lib.edgl_score_candidates(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(seen), T, _ptr(labels), R, C, I, N,
+                                    _ptr(scores), _ptr(label_val), _ptr(count), _code(rows), _stream()), "edgl_score_candidates")
+    return scores, label_val, count
 
 
 def adam_step(param, grad, m, v, lr, state, l2, seg, shadow, beta1=0.9, beta2=0.999, eps=1e-8):

@@ -73,6 +73,11 @@ def args(argv=None):
     p.add_argument("--eval_by_rank", action="store_true",
                    help="evaluate by the label's rank (one counting sweep over the item table, ops.score_label_rank) instead of a top-K "
                         "list; same H / N metrics plus MRR")
+    p.add_argument("--eval_negatives", type=int, default=0,
+                   help="N > 0: the sampled-negative protocol — rank the true next item among N items drawn from the catalogue that the "
+                        "user has not interacted with (ops.sample_negatives; the same N for every epoch), report H / N at 1, 5, 10 and "
+                        "MRR, select the model on H10.  0: rank against the whole catalogue")
+    p.add_argument("--eval_neg_seed", type=int, default=0, help="seed of the sampled negatives")
     a = p.parse_args(argv)
     return a
 
@@ -152,19 +157,33 @@ def regressive_batch(tok, tim, is_training: bool):
     return {"seqs_i": tok[:, :-1].contiguous(), "seqs_t": tim}, (tok[:, 1:].contiguous() if is_training else tok)
 
 
-def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False) -> Dict[str, float]:
+def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False, negatives: int = 0,
+             neg_seed: int = 0) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
     prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
     (--device_data) — the batches are then assembled on the device, in file order.  `by_rank`: the metrics from the label's rank
-    (model.eval_step(by_rank=True)) — the same H / N values plus "MRR"."""
+    (model.eval_step(by_rank=True)) — the same H / N values plus "MRR".  `negatives` > 0: the sampled-negative protocol —
+    the label ranked among that many negatives per sequence, keyed by (neg_seed, step 0, the sequence's index in the split): every
+    pass over a split ranks against the same lists, whatever the batch size; cut-offs (1, 5, 10)."""
     import torch
     from . import data as D
-    model.reset_metrics()
+    if negatives > 0:
+        model.reset_metrics((1, 5, 10))
+        row0 = [0]      # running sequence offset of the split
+
+        def step(feats, labels):
+            model.eval_step(feats, labels, mask_seen=mask_seen, negatives=negatives, neg_seed=neg_seed, row0=row0[0])
+            row0[0] += labels.shape[0]
+    else:
+        model.reset_metrics()
+
+        def step(feats, labels):
+            model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
     if loader is not None:
         loader.set_epoch(None)
         for _ in range(len(loader)):
             feats, labels = loader.next()
-            model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
+            step(feats, labels)
         return model.metrics()
     n = ids.shape[0]
     masked = hasattr(model, "mask")
@@ -172,7 +191,7 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_r
         tok = torch.as_tensor(ids[lo:lo + batch_size]).cuda()
         tim = torch.as_tensor(ts[lo:lo + batch_size]).cuda()
         feats, labels = D.device_mask_last(tok, tim, model.mask) if masked else regressive_batch(tok, tim, False)
-        model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
+        step(feats, labels)
     return model.metrics()
 
 
@@ -211,6 +230,8 @@ def run(FLAGS) -> Dict[str, float]:
                 raise ValueError(f"{name}: timestamps decrease inside a sequence; TGAT needs time-sorted records")
     device_data = bool(getattr(FLAGS, "device_data", False))
     by_rank = bool(getattr(FLAGS, "eval_by_rank", False))     # (the default cut-offs keep "H100": early stopping reads it either way)
+    negatives, neg_seed = int(getattr(FLAGS, "eval_negatives", 0) or 0), int(getattr(FLAGS, "eval_neg_seed", 0) or 0)
+    select_on = "H10" if negatives > 0 else "H100"            # (H100 of N + 1 <= 101 candidates is constant)
     # --device_data --graph: the batch no longer arrives from the host, so the EasyDGL step can be replayed as one graph
     engine_graph = device_data and bool(getattr(FLAGS, "graph", False))
     engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs) else None
@@ -295,10 +316,10 @@ def run(FLAGS) -> Dict[str, float]:
             break
         if epoch % FLAGS.eval_per_steps:
             continue
-        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank)
+        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed)
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
-        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank)
-        if stopper.step(running_loss, vl["H100"], vl, te):
+        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed)
+        if stopper.step(running_loss, vl[select_on], vl, te):
             break
     return stopper.summary()
 

@@ -526,6 +526,38 @@ int edgl_rank_count_tile(const float* logits, int R, int n, int i0, const int64_
  * sums f32 [2 nk + 1] += H@k.., N@k.., MRR with H = [rank < k], N = H / log2(rank + 2), MRR = 1 / (rank + 1); fixed summation order. */
 int edgl_rank_metrics_from_rank(const int32_t* rank, int R, const int32_t* ks, int nk, float* sums, void* stream);
 
+/* ---- K6c: evaluation on candidate lists (k_eval_cand.hip): the sampled-negative protocol and re-ranking.
+ * Every row scores its OWN list cand int32 [R, N] — a gather of R (N + 1) table rows, no sweep over the catalogue.  The order and the
+ * used table are those of the rank sweep above (Base.py:150-201: item 0 is the zero row with bias -1000):
+ *   v(r, c) = -inf for c < 0 (an empty slot), for c >= I (a caller error: nothing is read out of bounds) and for c in seen[r, :];
+ *           = rows[r] . table[c] + bias_used[c] otherwise, f32 accumulation;
+ *   count[r] += #{ n : c = cand[r, n] >= 0, c != y, v(r, c) > v(r, y) or (v(r, c) == v(r, y) and c < y) },  y = labels[r].
+ * v(r, c) is a pure function of rows[r], table[c] and the bias — the same bits whatever the slot, N, R or the other candidates — and
+ * v(r, y) comes out of the same code: ties between items with identical table rows and biases resolve by id alone.  The label need
+ * not be in the list; its own slots are not counted; a repeated id is counted once per slot.
+ * rows [R, C] and table [I, C] in `dtype` (f32 or bf16; 16-byte aligned), out_bias f32 [I - 1], seen int64 [R, T] (NULL with T = 0),
+ * labels int64 [R] (NULL when neither label_val nor count is wanted).  Outputs, each may be NULL: scores f32 [R, N], label_val f32
+ * [R], count int32 [R] (ADDED into: the caller zeroes it).  16 <= C <= 512 and C % 16 == 0; R >= 1; N >= 1 with R (N + 1) < 2^31;
+ * 0 <= T <= 1024; anything else is EDGL_ERR_SHAPE with the bound in the text.  No workspace.  edgl_score_candidates_chunk: the
+ * slots one workgroup takes for this shape (host arithmetic; -1 for a shape not taken) — the values do not depend on it. */
+int edgl_score_candidates_chunk(int R, int C, int N, int dtype);
+int edgl_score_candidates(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* seen,
+                          int T, const int64_t* labels, int R, int C, int I, int N, float* scores, float* label_val,
+                          int32_t* count, int dtype, void* stream);
+/* cand int32 [R, n]: per row n ids drawn uniformly from [lo, hi), with replacement between slots, never one of seen[r, :] (int64
+ * [R, T], NULL with T = 0) and never labels[r] (int64 [R], may be NULL).  Counter-based (all arithmetic mod 2^32, mix32 = the
+ * murmur3 finaliser of the dropout generator):
+ *   k = mix32((u32)seed ^ 0xC4ED1DA7); k = mix32(k + (u32)(seed >> 32)); k = mix32(k ^ (u32)step)
+ *   h = mix32(k ^ mix32((u32)(row0 + r))); h = mix32(h + slot * 0x9E3779B1); h = mix32(h ^ (att * 0x85EBCA6B))
+ *   id = lo + (((u64)h * (u64)(hi - lo)) >> 32);  the slot takes the first att in 0..31 whose id is accepted, else -1.
+ * row0 = index of the batch's first sequence in its split: a sequence's list does not depend on the batch size.  Needs
+ * 1 <= lo < hi <= I and 2 (T + 1) <= hi - lo (a draw is then rejected with probability <= 1/2), 0 <= T <= 1024, else EDGL_ERR_SHAPE. */
+int edgl_sample_negatives(const int64_t* seen, int T, const int64_t* labels, int R, int n, int lo, int hi, int I,
+                          uint64_t seed, uint64_t step, int row0, int32_t* cand, void* stream);
+/* edgl_rank_metrics_from_rank with the rows added to every sum one by one, in row order: the f32 sums of a split do not depend on
+ * how it is cut into batches (the steps on candidate lists use it; a batch costs one lane-loop over its rows). */
+int edgl_rank_metrics_from_rank_rows(const int32_t* rank, int R, const int32_t* ks, int nk, float* sums, void* stream);
+
 /* ---- K5, "flash" form (used by the static training engine): the forward scoring pass already accumulates the row
  * gradients, so the [R, I] logits are computed twice per step instead of three times.
  * edgl_score_flash_fwd: one pass over the item rows [i0, i1) gives row_lse (as edgl_score_lse_fwd), label_logit, and keeps
