@@ -1,20 +1,14 @@
 // Batch preparation of a training step — the row compaction map of the scoring and the slot data of the TPP regulariser: both read
 // labels / masked positions / timestamps only.  As device functions, so that they run either as kernels of their own
-// (edgl_compact_scan_labels: k_ce.hip; edgl_tpp_prep: k_misc.hip) or as extra workgroups of the encoder's launch
+// (edgl_compact_scan_labels: k_ce.hip; edgl_tpp_prep: k_tpp.hip) or as extra workgroups of the encoder's launch
 // (edgl_encode_fwd_prep: k_encode.hip) — on the main stream, in front of everything that reads them, without a side stream whose
 // join the first attention kernel would wait for.
 #pragma once
 #include "bimau_common.h"
 #include "edgl_common.h"
+#include "tpp_math.h"
 
 namespace batch_prep {
-
-__device__ __forceinline__ float raw_span(const float* ts_row, int pos, int T) {
-    // EasyDGL.py:161-162 on RAW seconds: span[t] = clip(ts[t]-ts[t-1], 0, 100), span[0] := span[1]
-    if (T < 2) return 0.f;
-    const int t1 = pos == 0 ? 1 : pos;
-    return fminf(fmaxf(ts_row[t1] - ts_row[t1 - 1], 0.f), 100.f);
-}
 
 // slot data of sample b (256 threads; tpp_smem: T * 16 + 2 * 256 * 4 bytes, 16-byte aligned) — see edgl_tpp_prep
 __device__ __forceinline__ void tpp_prep_sample(const int64_t* mpos, const int64_t* labels, const float* ts, const uint8_t* mtab, int B,
@@ -39,7 +33,7 @@ __device__ __forceinline__ void tpp_prep_sample(const int64_t* mpos, const int64
         int c = 0;
         if (m < M) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) c += (int)((ws[q] & 0xffu) + ((ws[q] >> 8) & 0xffu) + ((ws[q] >> 16) & 0xffu) + (ws[q] >> 24));
+            for (int q = 0; q < 4; ++q) c += (int)tpp_math::mark_word_count(ws[q]);
         }
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
         if ((m & 63) == 0) ovf_s[m >> 6] = c;     // (ovf_s is written for real behind the next barrier)
@@ -57,7 +51,7 @@ __device__ __forceinline__ void tpp_prep_sample(const int64_t* mpos, const int64
     for (int t = m; t < T; t += 256) {
         const uint4 w = nm_s[t];
         nmw[t] = w;
-        spr[t] = (w.x | w.y | w.z | w.w) != 0u ? raw_span(ts + (long)b * T, t, T) : -1.0f;
+        spr[t] = (w.x | w.y | w.z | w.w) != 0u ? tpp_math::raw_span(ts + (long)b * T, t, T) : -1.0f;
     }
     int rank = 0, total = 0;
     for (int q = 0; q < M; ++q) { rank += q < m ? ovf_s[q] : 0; total += ovf_s[q]; }

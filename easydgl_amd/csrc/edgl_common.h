@@ -38,13 +38,15 @@ extern "C" void edgl_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int edgl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride kernel over n elements, 256 threads per workgroup
+static inline int grid_for(long n) { const long g = (n + 255) / 256; return (int)(g < 4096 ? g : 4096); }
 
 // The environment switches of the library (table in DESIGN.md, "Environment variables") are read through these and nowhere else.
 inline const char* edgl_env(const char* name) { return getenv(name); }
 inline int edgl_env_int(const char* name, int dflt) { const char* e = edgl_env(name); return e ? atoi(e) : dflt; }
 inline bool edgl_env_on(const char* name) { const char* e = edgl_env(name); return !(e && e[0] == '0'); }   // on unless the value starts with '0'
 
-// out[n] (+)= sum_{p<P} part[p*ld + n], fixed summation order (k_misc.hip).  Used for every
+// out[n] (+)= sum_{p<P} part[p*ld + n], fixed summation order (k_reduce.hip).  Used for every
 // "per-workgroup partials -> parameter gradient" reduction.
 int edgl_reduce_rows(const float* part, int P, int N, long ld, float* out, int accumulate, hipStream_t st);
 // one-shot HIP-event bracket around a single kernel launch (edgl_profile_next); ids in easydgl_hip.h

@@ -1,4 +1,4 @@
-// The deferred partial reductions (k_misc.hip): the job list of one launch and the body of its vector-form kernel.  Shared with
+// The deferred partial reductions (k_reduce.hip): the job list of one launch and the body of its vector-form kernel.  Shared with
 // the embedding backward's MFMA scatter launch (k_encode.hip), which can carry the list as extra workgroups (edgl_reduce_ride).
 #pragma once
 #include "edgl_common.h"
@@ -8,14 +8,14 @@ constexpr int RED_COL_P = 32;      // jobs with at most this many partial rows r
 struct RedJob { const float* part; float* out; long ld; int P, N, blk0, f64; };      // f64: the sums of the job in double precision (vector form only)
 struct RedBatch { RedJob j[RED_MAX_JOBS]; int n, blocks; };
 
-// k_misc.hip: hand the calling thread's queue (+ the caller's own jobs) to the scatter launch; 0 = nothing rides, nothing changed; < 0 = a launch failed
+// k_reduce.hip: hand the calling thread's queue (+ the caller's own jobs) to the scatter launch; 0 = nothing rides, nothing changed; < 0 = a launch failed
 int edgl_reduce_ride_take(const RedJob* own, int nown, const float* lo0, const float* hi0, const float* lo1, const float* hi1,
                           RedBatch* out, int* first_blocks, hipStream_t st);
 
-// k_misc.hip: the vector-form jobs `jobs` as ONE launch on `st` now, whatever the deferred mode holds (the reductions of a launch that
+// k_reduce.hip: the vector-form jobs `jobs` as ONE launch on `st` now, whatever the deferred mode holds (the reductions of a launch that
 // carried the queue itself: its own partials cannot ride with it); jobs outside the vector form go through edgl_reduce_rows
 int edgl_reduce_rows_now(const RedJob* jobs, int n, hipStream_t st);
-// k_misc.hip: edgl_reduce_rows (overwrite) with the sums formed in double precision and rounded once: for partials that are themselves
+// k_reduce.hip: edgl_reduce_rows (overwrite) with the sums formed in double precision and rounded once: for partials that are themselves
 // long sums (the 128-sample column sums of dx_encode_kernel).  Queued in deferred mode; a job outside the vector form runs in f32.
 int edgl_reduce_rows_f64(const float* part, int P, int N, long ld, float* out, hipStream_t st);
 

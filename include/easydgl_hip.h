@@ -754,7 +754,8 @@ int edgl_adam_apply_l2p(float* param, const float* grad, float* m, float* v, lon
  * learning rate) into step_next / rng_next, buffers OTHER than step_state / rng_cur, which the launch reads: no single-thread launch at
  * the end of a step and no last-workgroup ticket; the caller swaps the buffer pairs behind the launch.  With slabs given, the two ranges
  * of `grad` are ZEROED behind their use: the next step's embedding scatter / one-hot term add into them (no zero-fill launch).  slabs_* / the three counter
- * pointers may be NULL (then that part is left out); l2_part may be NULL.  Base.py:142-144. */
+ * pointers may be NULL (then that part is left out); l2_part may be NULL.  A non-NULL slabs_a or slabs_b needs nslab >= 1
+ * (EDGL_ERR_SHAPE otherwise).  Base.py:142-144. */
 int edgl_adam_apply_ex(float* param, float* grad, float* m, float* v, long n, float beta1, float beta2, float eps,
                        const uint64_t* step_state, float l2, const int64_t* seg, int nseg, void* shadow, float* l2_part,
                        const float* slabs_a, long stride_a, long lo_a, long hi_a, long zero_first_a,

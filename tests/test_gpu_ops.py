@@ -605,11 +605,12 @@ def test_tpp_fused_launch_matches_the_reference(repeat):
     assert_close(dlam.cpu().numpy(), lr.grad.numpy(), 1e-5, "tpp dlam (dense)")
 
 
-@pytest.mark.parametrize("E,M,repeat", [(5, 4, False), (5, 4, True), (16, 20, True), (16, 300, False)])
+@pytest.mark.parametrize("E,M,repeat", [(5, 4, False), (5, 4, True), (16, 20, True), (16, 300, False), (20, 4, False), (20, 4, True)])
 def test_tpp_rows_launch_matches_the_reference(E, M, repeat):
     """edgl_tpp_norm + edgl_tpp_fwd_bwd_rows (the engine's form: one thread per masked slot, d lambda pre-zeroed by
     edgl_bimau_fwd_zr — here by the test) against the fp64 oracle: rows of unmasked positions stay zero, a position drawn into two
-    slots gets the sum of its slots' gradients exactly once (EasyDGL.py:157-175), M = 300 slots per sample crosses workgroups."""
+    slots gets the sum of its slots' gradients exactly once (EasyDGL.py:157-175), M = 300 slots per sample crosses workgroups,
+    E = 20 marks takes the plain-loop kernel for more than 16 marks."""
     from easydgl_amd import _lib
     lib = _lib.lib
     rng = np.random.default_rng(12 + E + M)
@@ -840,6 +841,96 @@ def test_adam_matches_tf_form():
     assert int(st[0]) == 4
     assert_close(w.cpu().numpy(), wn, 2e-6, "adam w")
     assert_close(shadow.float().cpu().numpy(), wn, 5e-3, "adam shadow")
+
+
+@pytest.mark.parametrize("E", [16, 5])
+def test_tpp_norm_counts_the_marks_of_a_large_batch_exactly(E):
+    """edgl_tpp_norm at B * M = 258 * 255 = 65 790 labels (more than one workgroup's 65 536: memset + integer atomics): sums[4], read
+    as an int, is the numpy sum of the labels' mark bytes — exactly, and again on a second call (the count is formed from zero)."""
+    from easydgl_amd import _lib
+    lib = _lib.lib
+    rng = np.random.default_rng(40 + E)
+    B, M, NI = 258, 255, 40
+    mt = O.synthetic_mark_table(NI, E, multi_hot=True).astype(np.uint8)
+    labels = rng.integers(0, NI, size=(B, M))
+    want = int(mt[labels].astype(np.int64).sum())
+    assert want > 0
+    lab_t, mt_t = torch.tensor(labels).cuda(), torch.tensor(mt).cuda()
+    sums = torch.zeros(8, device="cuda")
+    for _ in range(2):
+        _lib.check(lib.edgl_tpp_norm(lab_t.data_ptr(), mt_t.data_ptr(), B, M, E, sums.data_ptr(), None), "edgl_tpp_norm")
+        torch.cuda.synchronize()
+        assert int(sums.view(torch.int32)[4]) == want
+
+
+@pytest.mark.parametrize("entry", ["apply", "apply_l2p", "apply_ex"])
+def test_adam_apply_forms_match_tf_form_with_l2_segments(entry):
+    """edgl_adam_apply / _l2p / _ex against O.adam_tf with the l2 term on five segments (more than the four the vector path of
+    edgl_adam_apply_ex keeps in registers), n = 4099 (not a multiple of 4), three steps, the bounds of test_adam_matches_tf_form.
+    _l2p / _ex: l2_part sums to the sum of squares of the updated weights over the segments.  _ex also: the gradient is
+    grad + the slabs of two ranges (one 4-aligned with zero_first, one of odd stride), the ranges are zero afterwards, and the next
+    step's counters land in the second pair of buffers."""
+    from easydgl_amd import _lib
+    lib = _lib.lib
+    rng = np.random.default_rng(16)
+    n, lr, l2, b1, b2, eps = 4099, 1e-2, 0.01, 0.9, 0.999, 1e-8
+    segs = np.array([[0, 500], [600, 601], [1000, 2047], [2050, 3000], [4000, 4099]])
+    in_seg = np.zeros(n, dtype=bool)
+    for lo, hi in segs:
+        in_seg[lo:hi] = True
+    w0, g0 = rng.standard_normal(n), rng.standard_normal(n) * 0.1
+    w = torch.tensor(w0, dtype=torch.float32).cuda()
+    m, v = torch.zeros(n).cuda(), torch.zeros(n).cuda()
+    shadow = torch.empty(n, dtype=torch.bfloat16).cuda()
+    seg = torch.tensor(segs).cuda()
+    l2p = torch.full((int(lib.edgl_adam_l2_parts(n)),), float("nan"), device="cuda")
+    state = [torch.zeros(2, dtype=torch.int64).cuda(), torch.zeros(2, dtype=torch.int64).cuda()]
+    rngs = [torch.tensor([1234, 7]).cuda(), torch.zeros(2, dtype=torch.int64).cuda()]
+    (lo_a, hi_a, zf), (lo_b, hi_b), ns = (1024, 1536, 4), (3001, 3078), 3
+    slab_a, slab_b = rng.standard_normal((ns, hi_a - lo_a)) * 0.1, rng.standard_normal((ns, hi_b - lo_b)) * 0.1
+    sa_t, sb_t = torch.tensor(slab_a, dtype=torch.float32).cuda(), torch.tensor(slab_b, dtype=torch.float32).cuda()
+    wn, mn, vn = np.float32(w0).astype(np.float64), np.zeros(n), np.zeros(n)
+    if entry == "apply_ex":
+        _lib.check(lib.edgl_step_begin(rngs[0].data_ptr(), state[0].data_ptr(), lr, b1, b2, None), "edgl_step_begin")
+    for t in range(1, 4):
+        gt = torch.tensor(g0 * t, dtype=torch.float32).cuda()
+        gr = np.float32(g0 * t).astype(np.float64)
+        if entry == "apply_ex":
+            gr[lo_a + zf:hi_a] += np.float32(slab_a).astype(np.float64).sum(0)[zf:]
+            gr[lo_b:hi_b] += np.float32(slab_b).astype(np.float64).sum(0)
+            _lib.check(lib.edgl_adam_apply_ex(w.data_ptr(), gt.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps, state[0].data_ptr(), l2,
+                                              seg.data_ptr(), len(segs), shadow.data_ptr(), l2p.data_ptr(),
+                                              sa_t.data_ptr(), hi_a - lo_a, lo_a, hi_a, zf, sb_t.data_ptr(), hi_b - lo_b, lo_b, hi_b, ns,
+                                              rngs[0].data_ptr(), state[1].data_ptr(), rngs[1].data_ptr(), lr, None), "edgl_adam_apply_ex")
+            torch.cuda.synchronize()
+            gz = gt.cpu().numpy()
+            assert not gz[lo_a:hi_a].any() and not gz[lo_b:hi_b].any()          # the consumed ranges start the next step at zero
+            keep = np.ones(n, dtype=bool); keep[lo_a:hi_a] = False; keep[lo_b:hi_b] = False
+            np.testing.assert_array_equal(gz[keep], np.float32(g0 * t)[keep])
+            # the next step's counters are in the second buffers; the pair this launch read is unchanged
+            assert rngs[1].tolist() == [1234, 7 + t + 1] and rngs[0].tolist() == [1234, 7 + t]
+            assert int(state[1][0]) == t + 1 and int(state[0][0]) == t
+            # (in double on the betas as the C ABI passes them, floats: 1 - b2^t magnifies the rounding of 0.999 to 7e-6)
+            fb1, fb2, flr = float(np.float32(b1)), float(np.float32(b2)), float(np.float32(lr))
+            lr_next = flr * math.sqrt(1 - fb2 ** (t + 1)) / (1 - fb1 ** (t + 1))
+            assert_close(float(state[1][1:].view(torch.float32)[0]), lr_next, 2e-6, "next step's learning rate")
+            state.reverse(); rngs.reverse()
+        else:
+            _lib.check(lib.edgl_step_begin(rngs[0].data_ptr(), state[0].data_ptr(), lr, b1, b2, None), "edgl_step_begin")
+            if entry == "apply":
+                _lib.check(lib.edgl_adam_apply(w.data_ptr(), gt.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps, state[0].data_ptr(), l2,
+                                               seg.data_ptr(), len(segs), shadow.data_ptr(), None), "edgl_adam_apply")
+            else:
+                _lib.check(lib.edgl_adam_apply_l2p(w.data_ptr(), gt.data_ptr(), m.data_ptr(), v.data_ptr(), n, b1, b2, eps,
+                                                   state[0].data_ptr(), l2, seg.data_ptr(), len(segs), shadow.data_ptr(), l2p.data_ptr(), None),
+                           "edgl_adam_apply_l2p")
+        gr[in_seg] += l2 * wn[in_seg]
+        wn, mn, vn = O.adam_tf(wn, gr, mn, vn, t, lr)
+    torch.cuda.synchronize()
+    assert_close(w.cpu().numpy(), wn, 2e-6, "adam w")
+    assert_close(shadow.float().cpu().numpy(), wn, 5e-3, "adam shadow")
+    if entry != "apply":
+        assert_close(float(l2p.double().sum()), float((wn[in_seg] ** 2).sum()), 2e-6, "sum of squares over the l2 segments")
 
 
 def test_dropout_is_consistent_between_forward_and_backward():

@@ -29,7 +29,7 @@ def _raw_span(ts_row, t):
 
 
 def _prep_reference(mpos, labels, ts, mtab, T):
-    """Slot data as csrc/k_misc.hip tpp_prep_kernel defines it, slot by slot."""
+    """Slot data as csrc/k_tpp.hip tpp_prep_kernel (csrc/batch_prep.h tpp_prep_sample) defines it, slot by slot."""
     B, M = mpos.shape
     nm = np.zeros((B, T, 16), np.uint8)
     spr = -np.ones((B, T), np.float32)
