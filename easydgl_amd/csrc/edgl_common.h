@@ -66,6 +66,9 @@ int edgl_segsum_embed(const int64_t* ids, long rows, int C, int I, const void* d
                       const uint64_t* rng, uint32_t stream_id, float* d_item, void* plan, int dtype, hipStream_t st);
 int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef, const float* gscale, int R, int C, int I, int i0, int i1,
                       const int32_t* nvalid, float* d_table, float* d_bias, void* plan, int dtype, hipStream_t st);
+// ... the slots of per-row candidate lists (edgl_cand_ce_table_det): dv[e] rows[e / np1] into d_table[keys[e]], dv[e] into d_bias
+int edgl_segsum_cand(const void* rows, const int64_t* keys, const float* dv, long n, int np1, int C, int I, float* d_table, float* d_bias,
+                     void* plan, int dtype, hipStream_t st);
 // ... and the rows of a plain lookup (edgl_embed_pos_bwd_det, edgl_embedding_bwd_det): sq * drop(src[row * ld + c]) into the
 // zero-filled d_table; keep_zero: key 0 is summed like the others
 int edgl_segsum_rows(const int64_t* ids, long rows, int C, int I, const void* src, long ld, float sq, float rate, const uint64_t* rng,

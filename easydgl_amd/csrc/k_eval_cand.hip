@@ -10,7 +10,8 @@
 //                        the row hold zeros; f32 rows longer than 1 KB: two pieces per lane).  One wave-instruction of
 //                        global_load_dwordx4 fetches 64 / G candidate rows, UNROLL = 4 of them are in flight before the first is used,
 //                        and the ids of the next step are fetched under the arithmetic of this one.
-//                        cand_value IS the arithmetic rule: per lane the FMAs of its pieces in ascending channel order from +0, a fixed
+//                        cand_value (cand_gather.h, shared with the training loss of k_cand_ce.hip) IS the arithmetic rule:
+//                        per lane the FMAs of its pieces in ascending channel order from +0, a fixed
 //                        xor butterfly over the lane group (offsets 1, 2, .. G / 2: both partners form a + b, so every lane of the group
 //                        ends with the same bits), then + bias.  It depends on rows[r], table_c[c] and the bias only — not on the slot, N,
 //                        R, the chunk or the other candidates — and the label is one more slot through the same function, formed by
@@ -24,10 +25,12 @@
 #include <algorithm>
 
 #include "edgl_common.h"
+#include "cand_gather.h"
 
 namespace evc {
 
-constexpr int UNROLL = 4;        // candidate-row loads in flight per wave before the first is consumed
+using candg::UNROLL; using candg::RowRegs; using candg::load_pieces; using candg::unpack; using candg::cand_value; using candg::group_of;
+
 constexpr int MAX_T = 1024;      // seen ids per row staged in LDS
 constexpr int MAX_CHUNK = 1024;  // slots of one workgroup
 constexpr int WG_TARGET = 1024;  // workgroups wanted on the chip (256 CUs x 4)
@@ -40,47 +43,6 @@ struct P {
 
 // an id that the int32 LDS image can hold, else one that equals no candidate
 __device__ __forceinline__ int seen_id32(int64_t v) { return (v < 0 || v > 0x7fffffffLL) ? -2 : (int)v; }
-
-template <typename T, int PPL>
-struct RowRegs { float x[PPL][16 / sizeof(T)]; };
-
-// this lane's pieces of row `row` as f32; pieces past the row (and every piece when `zero`) read as +0
-template <typename T, int G, int PPL>
-__device__ __forceinline__ void load_pieces(const T* base, long row, int C, int gl, uint4 (&w)[PPL]) {
-    constexpr int VEC = 16 / sizeof(T);
-    const int np = C / VEC;
-#pragma unroll
-    for (int pp = 0; pp < PPL; ++pp) {
-        const int piece = gl + pp * 64;
-        w[pp] = *reinterpret_cast<const uint4*>(base + row * C + (long)min(piece, np - 1) * VEC);      // (clamped: inside the row)
-    }
-}
-template <typename T>
-__device__ __forceinline__ void unpack(const uint4& w, bool keep, float (&f)[16 / sizeof(T)]) {
-    constexpr int VEC = 16 / sizeof(T);
-    Vec16<T> v;
-    *reinterpret_cast<uint4*>(&v) = w;
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) f[e] = keep ? to_f32(v.v[e]) : 0.0f;
-}
-
-// THE value of (query row in `xq`, item c whose pieces are in `w`): see the head of the file.  `b` = bias_used[c].
-template <typename T, int G, int PPL>
-__device__ __forceinline__ float cand_value(const RowRegs<T, PPL>& xq, const uint4 (&w)[PPL], int c, float b, int C, int gl) {
-    constexpr int VEC = 16 / sizeof(T);
-    const int np = C / VEC;
-    float acc = 0.0f;
-#pragma unroll
-    for (int pp = 0; pp < PPL; ++pp) {
-        float z[VEC];
-        unpack<T>(w[pp], c != 0 && gl + pp * 64 < np, z);      // item 0: the used table's zero row
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc = fmaf(xq.x[pp][e], z[e], acc);
-    }
-#pragma unroll
-    for (int o = 1; o < G; o <<= 1) acc += __shfl_xor(acc, o, 64);
-    return acc + b;
-}
 
 template <typename T, int G, int PPL>
 __global__ __launch_bounds__(256) void score_cand_kernel(P p) {
@@ -243,13 +205,6 @@ __global__ __launch_bounds__(256) void rank_metrics_rows_kernel(const int32_t* r
         __syncthreads();
     }
     if (owner) sums[i] = s;
-}
-
-// lane group of a row of `pieces` 16-byte pieces: the next power of two, at most 64
-inline int group_of(int pieces) {
-    int g = 2;
-    while (g < pieces && g < 64) g <<= 1;
-    return g;
 }
 
 template <typename T, int G, int PPL>

@@ -1,6 +1,7 @@
 // Deterministic scatter-add into the item table: the gradient of the embedding lookup (coding.py:60-64:
 // d_item[id] += sqrt(C) dX0[row, :C]) and the one-hot term of the tied table's scoring gradient (EasyDGL.py:177-185:
-// d_table[label] -= coef rows, d_bias[label - 1] -= coef) WITHOUT f32 atomics.
+// d_table[label] -= coef rows, d_bias[label - 1] -= coef) WITHOUT f32 atomics.  The table gradient of the sampled-softmax loss
+// (k_cand_ce.hip, DESIGN §4.13: one entry per list slot, d_table[c] += dv rows[r]) runs through the same plan and sums.
 //
 //   (a) the plan: a stable LSD radix sort of the row indices by item id — per pass a per-block digit histogram, one scan over
 //       [digit][block] and a scatter with stable in-block ranks (wave match + fixed (round, wave) order).  Integer LDS atomics
@@ -273,6 +274,7 @@ struct SumP {
     long ld;                                                  // item rows (ROWS): leading dimension of src, C or 2C
     float sq; float rate; const uint64_t* rng; uint32_t stream_id;
     const float* coef; const float* gscale;                   // label rows: src = the compacted head rows [R, C]
+    const float* dv; int np1;                                 // list slots (CAND_ROWS): entry e = slot e % np1 of row e / np1, src = rows [R, C]
     float* d_item; float* d_bias;
 };
 
@@ -293,10 +295,12 @@ __device__ __forceinline__ float sum3(float x, float a, float b) {
 // EMBED: term = sqrt(C_true) * drop(dX0[row, c] (+ add1 + add2)), the mask of element row * 3C + c (encode_scatter_kernel)
 // LABEL: term = -gscale coef[row] rows[row, c];  bias term -gscale coef[row]
 // ROWS : term = sq * drop(src[row * ld + c]), the mask of element row * ld + c (embed_pos_bwd_kernel; rate 0: embedding_bwd_kernel)
-enum { EMBED = 0, LABEL_ROWS = 1, ROWS = 2 };
+// CAND : the plan's entries are the slots of per-row candidate lists (k_cand_ce.hip): term = dv[e] rows[e / np1, c];
+//        bias term dv[e]
+enum { EMBED = 0, LABEL_ROWS = 1, ROWS = 2, CAND_ROWS = 3 };
 template <typename T, int ROLE>
 __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
-    constexpr bool LABEL = ROLE == LABEL_ROWS;
+    constexpr bool LABEL = ROLE == LABEL_ROWS, CAND = ROLE == CAND_ROWS, BIAS = LABEL || CAND;
     const int cpr = p.C >> 2, rows_par = 256 / cpr;
     const int tid = threadIdx.x, cv = tid % cpr, rl = tid / cpr, c0 = cv * 4;
     if (rl >= rows_par) return;
@@ -305,10 +309,10 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
     const long p0 = u * SUB;
     if (p0 >= nkept) return;
     const int p1 = (int)min(p0 + (long)SUB, (long)nkept);
-    const DropKey dk = make_dropkey(p.rng, p.stream_id, LABEL ? 0.f : p.rate);
+    const DropKey dk = make_dropkey(p.rng, p.stream_id, BIAS ? 0.f : p.rate);
     const float gs = LABEL ? (p.gscale ? p.gscale[0] : 1.0f) : 0.f;
     const T* src = reinterpret_cast<const T*>(p.src);
-    const long ld = LABEL ? p.C : (ROLE == ROWS ? p.ld : 3L * p.C);
+    const long ld = BIAS ? p.C : (ROLE == ROWS ? p.ld : 3L * p.C);
     const bool adds = ROLE == EMBED && p.add1;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb = 0.f;
     int s_cur = p.seg_id[p0];
@@ -317,12 +321,12 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
         if (a >= p0 && b <= p0 + SUB) {      // the whole segment lies in this window: its only writer
             const long key = p.seg_key[s_cur];
             add4(p.d_item + key * p.C + c0, acc);
-            if (LABEL && cv == 0) p.d_bias[key - 1] += accb;
+            if (BIAS && cv == 0) p.d_bias[key - 1] += accb;
         } else {
             const int slot = a < p0 ? 0 : 1;
             float* dst = p.part + (u * 2 + slot) * p.C + c0;
             *reinterpret_cast<float4*>(dst) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-            if (LABEL && cv == 0) p.partb[u * 2 + slot] = accb;
+            if (BIAS && cv == 0) p.partb[u * 2 + slot] = accb;
         }
     };
     for (int pb = (int)p0; pb < p1; pb += 8) {
@@ -337,6 +341,10 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
+            if (CAND) {      // (the entry's coefficient first: `row` then becomes the row the slot belongs to)
+                cf[k] = p.dv[row[k]];
+                row[k] /= p.np1;
+            }
             g[k] = frag_ld<T>(src + row[k] * ld + c0);
             if (adds) {
                 ga[k] = frag_ld<T>(reinterpret_cast<const T*>(p.add1) + (long)row[k] * p.C + c0);
@@ -359,8 +367,8 @@ __global__ __launch_bounds__(256) void segsum_walk_kernel(SumP p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) gv[j] = sum3(gv[j], to_f32(ga[k].v[j]), to_f32(gb[k].v[j]));
             }
-            if (LABEL) {
-                const float w = -(gs * cf[k]);
+            if (BIAS) {
+                const float w = CAND ? cf[k] : -(gs * cf[k]);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[j] += w * gv[j];
                 accb += w;
@@ -496,6 +504,10 @@ static int segsum_run(int role, const int64_t* keys, int n, const int32_t* nvali
     if (role == LABEL_ROWS) {      // (bf16 only: in f32 the scoring product pass contains the one-hot term and the entry point is a no-op)
         hipLaunchKernelGGL((segsum_walk_kernel<bf16, LABEL_ROWS>), grid, dim3(256), 0, st, p);
         hipLaunchKernelGGL(segsum_join_kernel<true>, grid, dim3(256), 0, st, p);
+    } else if (role == CAND_ROWS) {
+        if (dtype == EDGL_F32) hipLaunchKernelGGL((segsum_walk_kernel<float, CAND_ROWS>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((segsum_walk_kernel<bf16, CAND_ROWS>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL(segsum_join_kernel<true>, grid, dim3(256), 0, st, p);
     } else if (role == ROWS) {
         if (dtype == EDGL_F32) hipLaunchKernelGGL((segsum_walk_kernel<float, ROWS>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((segsum_walk_kernel<bf16, ROWS>), grid, dim3(256), 0, st, p);
@@ -525,6 +537,17 @@ int edgl_segsum_label(const void* rows, const int64_t* labels, const float* coef
     segsum::SumP p{};
     p.C = C; p.src = rows; p.coef = coef; p.gscale = gscale; p.d_item = d_table; p.d_bias = d_bias;
     return segsum_run(segsum::LABEL_ROWS, labels, R, nvalid, I, i0, i1, 0, p, plan, dtype, st);
+}
+
+// the table gradient of the sampled-softmax loss (k_cand_ce.hip: edgl_cand_ce_table_det): keys int64 [n = R np1], one per list slot
+// (0: a dead slot); d_table[key] += sum in plan order of dv[e] rows[e / np1], d_bias[key - 1] += sum dv[e]
+int edgl_segsum_cand(const void* rows, const int64_t* keys, const float* dv, long n, int np1, int C, int I, float* d_table, float* d_bias,
+                     void* plan, int dtype, hipStream_t st) {
+    EDGL_REQUIRE(plan, EDGL_ERR_NULL, "edgl_cand_ce_table_det: null plan buffer");
+    EDGL_REQUIRE(n > 0 && n < (1L << 31) && np1 >= 2, EDGL_ERR_SHAPE, "edgl_cand_ce_table_det: %ld list slots unsupported", n);
+    segsum::SumP p{};
+    p.C = C; p.src = rows; p.dv = dv; p.np1 = np1; p.d_item = d_table; p.d_bias = d_bias;
+    return segsum_run(segsum::CAND_ROWS, keys, (int)n, nullptr, I, 0, I, 0, p, plan, dtype, st);
 }
 
 // d_table[key] = sum over the rows with that key, in plan order, of sq * drop(src[row * ld + c]) into the ZERO-FILLED d_table

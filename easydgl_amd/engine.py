@@ -58,6 +58,9 @@ class TrainEngine:
 
     def __init__(self, model, batch: int, use_graph: bool = True, process_group=None, fused_tail=None, flash_ce=None,
                  deterministic=None):
+        if int(getattr(model, "train_negatives", 0) or 0) > 0:
+            raise _lib.EdglError("TrainEngine: the static engine scores the whole catalogue; a model with train_negatives > 0 "
+                                 "(sampled-softmax training, DESIGN 4.13) trains on the autograd path: model.train_step")
         # the environment switches (class docstring): read here, once, and nowhere else in the engine
         env = os.environ.get
         self.sw_flash_ce = env("EDGL_FLASH_CE", "1") != "0"

@@ -59,6 +59,12 @@ class Sequential(nn.Module):
         self.act_dtype = {"bf16": torch.bfloat16, "f32": torch.float32, "fp32": torch.float32}[cd]
         # bitwise reproducible training: every scatter / bin sum of the model's ops runs in its ordered form
         self.deterministic = bool(getattr(FLAGS, "deterministic", False))
+        # sampled-softmax training: N > 0 negatives per scored row instead of the softmax over the catalogue
+        self.train_negatives = int(getattr(FLAGS, "train_negatives", 0) or 0)
+        self.train_neg_seed = int(getattr(FLAGS, "train_neg_seed", 0) or 0)
+        self.neg_step = 0       # sampled training steps taken (host side; the `step` key of the lists; travels in checkpoints)
+        if self.train_negatives < 0:
+            raise ValueError(f"train_negatives={self.train_negatives}: the number of sampled negatives per row (0: full softmax)")
         self._arena: Optional[torch.Tensor] = None
         self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (a head dim the kernels do not tile)
         self._metrics = None
@@ -166,6 +172,9 @@ class Sequential(nn.Module):
         (device scalar) that copies the new batch in and replays ~170 kernel launches as one submission.  Everything a step
         needs lives on the device (dropout step counter, Adam step count), so replays advance like eager steps.  The `warmup`
         eager steps that precede the capture are real optimizer steps."""
+        if self.train_negatives > 0:      # (the lists are keyed by a host-side step count: a replay would draw one list for ever)
+            raise ValueError("graphed_train_step: a model with train_negatives > 0 (sampled-softmax training, DESIGN 4.13) trains "
+                             "through train_step; its step is not captured into a graph")
         static_f = {k: v.clone() for k, v in features.items()}
         static_l = labels.clone()
         side = torch.cuda.Stream()
@@ -423,6 +432,20 @@ class Sequential(nn.Module):
         return (labels[:, -1] if labels.dim() == 2 else labels).contiguous()
 
     # ---- Sequential.train (Base.py:119-144) ------------------------------------------------------------------
+    def _score_ce(self, rows, labels, candidates=None):
+        """The cross-entropy of a training step over `rows` [R, C] / `labels` int64 [R]: the softmax over the catalogue
+        (ops.ScoreCEFn), or — with `candidates` (int32 [R, N], one list per scored row) or FLAGS.train_negatives = N > 0 — over each
+        row's label and its own list (ops.SampledCEFn, DESIGN 4.13).  Sampled lists are keyed by (train_neg_seed, neg_step, row);
+        train_step advances neg_step, so a resumed run draws the lists the uninterrupted run would have drawn, and calling
+        train_loss twice in between scores the same lists.  A range [1, hi) too small for the sampler is refused by the sampler."""
+        tab = self.item_embs.lookup_table
+        if candidates is None and self.train_negatives <= 0:
+            return ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, self.deterministic)
+        if candidates is None:
+            candidates = ops.sample_negatives(None, labels, self.train_negatives, 1, self._negatives_hi(), self.train_neg_seed,
+                                              self.neg_step, 0)
+        return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic)
+
     def train_step(self, features, labels):
         """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar)."""
         self.settle_state()
@@ -433,6 +456,8 @@ class Sequential(nn.Module):
         self.collect_grads()
         self.mask_padded_grads()
         self.optimizer_step()
+        if self.train_negatives > 0:
+            self.neg_step += 1
         return loss.detach()
 
     # ---- Sequential.eval (Base.py:150-207) -------------------------------------------------------------------

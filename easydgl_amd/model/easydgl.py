@@ -258,12 +258,11 @@ class EasyDGL(Sequential):
         return ops.ScoreLogitsFn.apply(rows, tab, self.output_bias, self.compute(tab))
 
     # ---- EasyDGL.train (the loss it builds) ------------------------------------------------------------------
-    def train_loss(self, features, labels):
-        """EasyDGL.py:153-188 with the fused scoring/CE path (no [B*M, I] tensor)."""
+    def train_loss(self, features, labels, *, candidates=None):
+        """EasyDGL.py:153-188 with the fused scoring/CE path (no [B*M, I] tensor).  `candidates` (int32 [B*M, N]) or
+        FLAGS.train_negatives > 0: the softmax of every masked position over its label and its own list (Sequential._score_ce)."""
         rows, lams = self.encoder(features, True, self._gather_pos(features, True))
-        tab = self.item_embs.lookup_table
-        loss = ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels.reshape(-1).contiguous(),
-                                   self.deterministic)
+        loss = self._score_ce(rows, labels.reshape(-1).contiguous(), candidates)
         if self.l2_reg != 0.0:                                                                     # :158
             for p in (self.item_embs.lookup_table, self.mark_embs.lookup_table, self.pcoding.pembs.lookup_table):
                 loss = loss + ops.L2Fn.apply(p, self.l2_reg)

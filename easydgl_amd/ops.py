@@ -596,6 +596,73 @@ class ScoreCEFn(torch.autograd.Function):
         return d_rows, d_table, d_bias, None, None, None
 
 
+def cand_ce_fwd(rows, table_c, out_bias, cand, labels):
+    """(vals f32 [R, N + 1], label_val f32 [R], lse f32 [R]) of edgl_cand_ce_fwd: slot 0 is the label, slot 1 + n is cand[r, n]
+    (int32 [R, N]); -inf at an empty slot, an id >= I and an accidental hit (cand[r, n] == labels[r]); rows of label 0 are skipped
+    (vals -inf, label_val = lse = 0).  The values carry the bits of score_candidates."""
+    _ptr(rows)                                               # (GPU tensors only: refused before anything else)
+    R, C = rows.shape
+    I = table_c.shape[0]
+    if table_c.dtype != rows.dtype or table_c.dim() != 2 or table_c.shape[1] != C:
+        raise _lib.EdglError(f"cand_ce: rows {rows.dtype} [{R}, {C}] against a table {table_c.dtype} {tuple(table_c.shape)}")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != R:
+        raise _lib.EdglError(f"cand_ce: candidates must be int32 [{R}, N], one list per scored row (got {cand.dtype} "
+                             f"{tuple(cand.shape)})")
+    if labels.dtype != torch.int64 or labels.shape != (R,):
+        raise _lib.EdglError(f"cand_ce: labels must be int64 [{R}] (got {labels.dtype} {tuple(labels.shape)})")
+    dev, N = rows.device, cand.shape[1]
+    vals = torch.empty((R, N + 1), device=dev, dtype=torch.float32)
+    label_val = torch.empty(R, device=dev, dtype=torch.float32)
+    lse = torch.empty(R, device=dev, dtype=torch.float32)
+    check(lib.edgl_cand_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), R, C, I, N, _ptr(vals),
+                               _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_cand_ce_fwd")
+    return vals, label_val, lse
+
+
+class SampledCEFn(torch.autograd.Function):
+    """Sampled-softmax cross-entropy: ScoreCEFn's loss with the softmax of row r taken over {labels[r]} and its own list
+    cand[r, :] (int32 [R, N]; -1 = empty slot) instead of the catalogue.  Same gradient contract as ScoreCEFn: d_rows in the compute
+    dtype, a dense f32 d_table [I, C] (zero-filled, then scattered into) and d_bias [I - 1].  No compaction: rows of label 0 are
+    skipped inside the kernels, so a row's list never depends on which other rows are weighted.
+    deterministic: the table / bias gradient is summed in plan order (edgl_cand_ce_table_det) instead of with f32 atomics."""
+
+    @staticmethod
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False):
+        ctx.deterministic = bool(deterministic)
+        rows, labels, cand = rows.contiguous(), labels.reshape(-1).contiguous(), cand.contiguous()
+        vals, label_val, lse = cand_ce_fwd(rows, table_c, out_bias, cand, labels)
+        R = rows.shape[0]
+        loss = torch.empty(1, device=rows.device, dtype=torch.float32)
+        coef = torch.empty(R, device=rows.device, dtype=torch.float32)
+        check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
+              "edgl_ce_loss_fwd")
+        ctx.save_for_backward(rows, table_c, out_bias, labels, cand, vals, lse, coef)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, table_c, out_bias, labels, cand, vals, lse, coef = ctx.saved_tensors
+        R, C = rows.shape
+        I, N = table_c.shape[0], cand.shape[1]
+        dev = rows.device
+        g = g.reshape(1).to(torch.float32).contiguous()
+        d_rows = torch.empty_like(rows)
+        dv = torch.empty((R, N + 1), device=dev, dtype=torch.float32)
+        d_table = torch.zeros((I, C), device=dev, dtype=torch.float32)
+        d_bias = torch.zeros(I - 1, device=dev, dtype=torch.float32)
+        det = ctx.deterministic
+        check(lib.edgl_cand_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), _ptr(vals), _ptr(lse),
+                                   _ptr(coef), _ptr(g), R, C, I, N, _ptr(d_rows), _ptr(dv), None if det else _ptr(d_table),
+                                   None if det else _ptr(d_bias), _code(rows), _stream()), "edgl_cand_ce_bwd")
+        if det:
+            n = R * (N + 1)
+            keys = torch.empty(n, device=dev, dtype=torch.int64)
+            plan = segsum_plan_buffer(n, I, dev)
+            check(lib.edgl_cand_ce_table_det(_ptr(rows), _ptr(cand), _ptr(labels), _ptr(dv), R, C, I, N, _ptr(d_table), _ptr(d_bias),
+                                             _ptr(keys), _ptr(plan), _code(rows), _stream()), "edgl_cand_ce_table_det")
+        return d_rows, d_table, d_bias, None, None, None, None
+
+
 class ScoreLogitsFn(torch.autograd.Function):
     """Materialised logits [R, I] (EasyDGL.py:149-151) for API parity with the reference's __call__."""
 

@@ -78,7 +78,17 @@ def args(argv=None):
                         "user has not interacted with (ops.sample_negatives; the same N for every epoch), report H / N at 1, 5, 10 and "
                         "MRR, select the model on H10.  0: rank against the whole catalogue")
     p.add_argument("--eval_neg_seed", type=int, default=0, help="seed of the sampled negatives")
+    p.add_argument("--train_negatives", type=int, default=0,
+                   help="N > 0: sampled-softmax training (DESIGN 4.13) — the cross-entropy of every scored position over its label and N "
+                        "negatives drawn uniformly from the catalogue (fresh lists every step) instead of the whole catalogue; every "
+                        "batch goes through model.train_step (no static engine, no --graph).  0: full softmax")
+    p.add_argument("--train_neg_seed", type=int, default=0, help="seed of the sampled training negatives")
     a = p.parse_args(argv)
+    if a.train_negatives < 0:
+        p.error("--train_negatives: the number of sampled negatives per position (0: full softmax)")
+    if a.train_negatives > 0 and a.graph:
+        p.error("--graph with --train_negatives: the sampled-softmax step runs on the autograd path (model.train_step), whose "
+                "negative lists are keyed by a host-side step count; it is not captured into a graph")
     return a
 
 
@@ -133,7 +143,7 @@ def save_checkpoint(model, path: str) -> None:
     model.settle_state()       # (the static engine keeps the counters one step ahead: the file holds "steps taken")
     torch.save({"arena": model._arena.detach().cpu(), "adam_m": model._adam_m.cpu(), "adam_v": model._adam_v.cpu(),
                 "adam_state": model._adam_state.cpu(), "rng_state": model._rng_state.cpu(),
-                "offsets": dict(model._offsets)}, path)
+                "offsets": dict(model._offsets), "neg_step": int(getattr(model, "neg_step", 0))}, path)
 
 
 def load_checkpoint(model, path: str) -> None:
@@ -147,6 +157,7 @@ def load_checkpoint(model, path: str) -> None:
         model._adam_v.copy_(ck["adam_v"])
         model._adam_state.copy_(ck["adam_state"])
         model._rng_state.copy_(ck["rng_state"])
+    model.neg_step = int(ck.get("neg_step", 0))      # (optional field: sampled training steps taken)
     model._state_ahead = False     # the file holds "steps taken" (save_checkpoint settles the engine's look-ahead)
     model.sync_shadow()
 
@@ -234,7 +245,11 @@ def run(FLAGS) -> Dict[str, float]:
     select_on = "H10" if negatives > 0 else "H100"            # (H100 of N + 1 <= 101 candidates is constant)
     # --device_data --graph: the batch no longer arrives from the host, so the EasyDGL step can be replayed as one graph
     engine_graph = device_data and bool(getattr(FLAGS, "graph", False))
-    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs) else None
+    train_negatives = int(getattr(FLAGS, "train_negatives", 0) or 0)
+    if train_negatives > 0 and getattr(FLAGS, "graph", False):
+        raise ValueError("--graph with --train_negatives: the sampled-softmax step runs on the autograd path (model.train_step)")
+    # sampled-softmax training: no static engine, every batch through model.train_step
+    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0) else None
     loader = vl_loader = te_loader = None
     if device_data:
         need = sum(D.DeviceSplit.nbytes(ii, tt) + 4 * len(ii) for ii, tt in ((tr_i, tr_t), (vl_i, vl_t), (te_i, te_t)))

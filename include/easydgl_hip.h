@@ -558,6 +558,31 @@ int edgl_sample_negatives(const int64_t* seen, int T, const int64_t* labels, int
  * how it is cut into batches (the steps on candidate lists use it; a batch costs one lane-loop over its rows). */
 int edgl_rank_metrics_from_rank_rows(const int32_t* rank, int R, const int32_t* ks, int nk, float* sums, void* stream);
 
+/* ---- K5c: sampled-softmax training — cross-entropy over per-row candidate lists (csrc/k_cand_ce.hip) -------------
+ * The training side of edgl_score_candidates: row r (label y = labels[r]) is scored against slot 0 = its label and slots 1 + n =
+ * cand[r, n] (int32 [R, N]) by the SAME arithmetic (cand_gather.h), so vals[r, 1 + n] and label_val carry the bits
+ * edgl_score_candidates gives.  A list slot reads -inf and takes no part in loss or gradient when it is empty (-1), at or past I,
+ * or equal to the row's label (accidental hits).  Rows with label 0 have weight 0: vals -inf, label_val = row_lse = 0, gradients 0.
+ *   edgl_cand_ce_fwd   vals f32 [R, N + 1], label_val f32 [R], row_lse f32 [R] = log sum exp over the label and the live slots, in
+ *                      an order that is a function of N alone (no atomics; a row's outputs do not depend on R or on other rows).
+ *                      Loss and coef come from edgl_ce_loss_fwd(row_lse, label_val, labels, ..).
+ *   edgl_cand_ce_bwd   dv f32 [R, N + 1] = g coef[r] (exp(vals - row_lse) - [slot 0]) (gscale: device scalar or NULL = 1);
+ *                      d_rows [R, C] (`dtype`) = sum_s dv table[c_s], one store per row, no atomics; d_table f32 [I, C] / d_bias f32
+ *                      [I - 1] are ADDED into with f32 atomics (the caller zero-fills them; row 0 is never touched), or both NULL:
+ *                      dv only.  R (N + 1) C 4 bytes of atomic adds, whole contiguous row segments per wave-instruction.
+ *   edgl_cand_ce_table_det   the same table / bias sums without float atomics: ordered sums over a plan of the slot keys (the call
+ *                      builds keys int64 [R (N + 1)] and the plan, edgl_segsum_plan_bytes of (R (N + 1), I) bytes, 16-byte aligned):
+ *                      one writer per table row, the order of every sum a function of (cand, labels) alone.  Adds into d_table / d_bias.
+ * rows / table in `dtype` (f32 or bf16), 16-byte aligned; 16 <= C <= 512 and C % 16 == 0; R >= 1; 1 <= N <= 8192 with
+ * R (N + 1) < 2^31; I > 1; anything else is EDGL_ERR_SHAPE with the bound in the text. */
+int edgl_cand_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels, int R,
+                     int C, int I, int N, float* vals, float* label_val, float* row_lse, int dtype, void* stream);
+int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
+                     const float* vals, const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int N,
+                     void* d_rows, float* dv, float* d_table, float* d_bias, int dtype, void* stream);
+int edgl_cand_ce_table_det(const void* rows, const int32_t* cand, const int64_t* labels, const float* dv, int R, int C, int I, int N,
+                           float* d_table, float* d_bias, int64_t* keys, void* plan, int dtype, void* stream);
+
 /* ---- K5, "flash" form (used by the static training engine): the forward scoring pass already accumulates the row
  * gradients, so the [R, I] logits are computed twice per step instead of three times.
  * edgl_score_flash_fwd: one pass over the item rows [i0, i1) gives row_lse (as edgl_score_lse_fwd), label_logit, and keeps

@@ -1,0 +1,135 @@
+"""Sampled-softmax training against the full-catalogue softmax, in ONE process:
+
+    python tools/train_negatives_bench.py [--rounds 5] [--steps 20] [--models EasyDGL,TiSASREC] [--out profiles/train_negatives.txt]
+
+Per shape (sequences x positions x channels x items; bf16) and model: `model.train_step` with train_negatives N in {0, 100, 1000} —
+N = 0 is the full softmax (ops.ScoreCEFn), the path every step took before sampled training existed — and the loss op alone,
+forward + backward on the model's scored rows: ops.ScoreCEFn against ops.SampledCEFn (atomic and ordered table gradient), with
+the atomic bytes R_w (N + 1) C 4 of the table gradient (R_w weighted rows) over the chip-wide rate of 1.3 TB/s beside it.  Each
+round times `steps` calls between device events after a warm-up; the table gives the median and the spread (min .. max) over the
+rounds.  Needs a GPU: there is no fallback."""
+import argparse
+import os
+import statistics
+import sys
+from types import SimpleNamespace
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import easydgl_amd  # noqa: E402
+from easydgl_amd import data as D  # noqa: E402
+from easydgl_amd import ops  # noqa: E402
+
+# (sequences, positions, channels, items): the headline and a config-3-shaped case (BASELINE.json configs[2])
+SHAPES = [(512, 100, 128, 20000), (512, 200, 256, 1000000)]
+NEGATIVES = (0, 100, 1000)
+ATOMIC_RATE = 1.3e12      # bytes of f32 atomic adds per second, chip-wide
+
+
+def timed(fn, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def rounds_of(fn, rounds, steps, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    return [timed(fn, steps) for _ in range(rounds)]
+
+
+def fmt(ts):
+    return f"{statistics.median(ts):9.4f} ({min(ts):.4f} .. {max(ts):.4f})"
+
+
+def build(name, B, L, C, num_items):
+    F = SimpleNamespace(model=name, num_items=num_items, num_units=C, num_heads=8, num_blocks=1, seqslen=L, masklen=L // 5,
+                        timelen=256, time_scale=86400.0, learning_rate=5e-4, l2_reg=1e-4, ct_reg=1e-7, hidden_dropout_rate=0.1,
+                        attention_probs_dropout_rate=0.1, compute_dtype="bf16", num_train_steps=None, num_warmup_steps=None, seed=9876)
+    if name == "EasyDGL":
+        F.mark_table = D.synthetic_mark_table(num_items, 16)
+    model = easydgl_amd.ranking(F).finalize("cuda")
+    ids, ts = D.synthetic_batch(num_items, L, B, seed=9876)
+    tok, tim = torch.tensor(ids, device="cuda"), torch.tensor(ts, device="cuda")
+    if name == "EasyDGL":
+        state = torch.tensor([9876, 0], dtype=torch.int64, device="cuda")
+        feats, labels = D.device_mask_random(tok, tim, model.mask, L // 5, state)
+    else:
+        feats, labels = {"seqs_i": tok[:, :-1].contiguous(), "seqs_t": tim}, tok[:, 1:].contiguous()
+    return model, feats, labels
+
+
+def scored_rows(name, model, feats):
+    with torch.no_grad():
+        out = model.encoder(feats, False, model._gather_pos(feats, True) if name == "EasyDGL" else None)
+    rows = out[0] if isinstance(out, tuple) else out
+    return rows.reshape(-1, model.num_units).contiguous()
+
+
+def op_call(model, rows, labels, cand, det):
+    tab = model.item_embs.lookup_table
+    r = rows.detach().requires_grad_(True)
+    if cand is None:
+        loss = ops.ScoreCEFn.apply(r, tab, model.output_bias, model.compute(tab), labels, det)
+    else:
+        loss = ops.SampledCEFn.apply(r, tab, model.output_bias, model.compute(tab), labels, cand, det)
+    torch.autograd.grad(loss, (r, tab, model.output_bias))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--models", default="EasyDGL,TiSASREC")
+    ap.add_argument("--out", default=os.path.join("profiles", "train_negatives.txt"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("train_negatives_bench.py: needs a GPU")
+    lines = [f"sampled-softmax training vs the full softmax: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} "
+             f"calls, one process; bf16, dropout 0.1 / 0.1; N = 0 is the full-catalogue softmax (ops.ScoreCEFn)", ""]
+    for name in args.models.split(","):
+        for B, L, C, num_items in SHAPES:
+            try:
+                model, feats, labels = build(name, B, L, C, num_items)
+                lab = labels.reshape(-1).contiguous()
+                rows = scored_rows(name, model, feats)
+                R, Rw, I = rows.shape[0], int((lab != 0).sum()), model.item_embs.lookup_table.shape[0]
+                lines.append(f"{name}  {B} x {L} x {C}, {I} table rows: {R} scored rows, {Rw} weighted")
+                base = None
+                for N in NEGATIVES:
+                    model.train_negatives = N
+                    step = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                    cand = ops.sample_negatives(None, lab, N, 1, model._negatives_hi(), 0) if N else None
+                    op = rounds_of(lambda: op_call(model, rows, lab, cand, False), args.rounds, args.steps)
+                    med = statistics.median(step)
+                    base = med if base is None else base
+                    line = f"  N = {N:5d}  train_step {fmt(step)}  x{med / base:6.3f} of N = 0   loss op fwd + bwd {fmt(op)}"
+                    if N:
+                        det = rounds_of(lambda: op_call(model, rows, lab, cand, True), args.rounds, args.steps)
+                        ab = Rw * (N + 1) * C * 4
+                        line += (f"   ordered {fmt(det)}   atomic bytes {ab / 1e6:9.1f} MB = {ab / ATOMIC_RATE * 1e3:7.3f} ms "
+                                 f"at 1.3 TB/s")
+                    lines.append(line)
+                    print(lines[-1], flush=True)
+                    del cand
+                    torch.cuda.empty_cache()
+            except (RuntimeError, easydgl_amd._lib.EdglError) as e:      # (a shape a model does not take: say so, go on)
+                lines.append(f"{name}  {B} x {L} x {C}, {num_items + 1} items: not measured ({type(e).__name__}: {str(e)[:200]})")
+                print(lines[-1], flush=True)
+            lines.append("")
+            model = feats = labels = rows = None
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
