@@ -155,6 +155,7 @@ SIGNATURES = {
     "edgl_adam_step": (I, [P, P, P, P, L, F, F, F, F, P, F, P, I, P, P]),
     "edgl_step_begin": (I, [P, P, F, F, F, P]),
     "edgl_adam_apply": (I, [P, P, P, P, L, F, F, F, P, F, P, I, P, P]),
+    "edgl_adam_rows": (I, [P, P, P, P, P, I, I, P, L, P, P, I, I, P, F, F, F, P, F, P]),
     "edgl_adam_l2_parts": (I, [L]),
     "edgl_adam_apply_l2p": (I, [P, P, P, P, L, F, F, F, P, F, P, I, P, P, P]),
     "edgl_l2_from_parts": (I, [P, I, F, P, I, P]),

@@ -42,6 +42,7 @@ class Sequential(nn.Module):
     """Base.py:90-207.  Reads the same FLAGS fields as the reference (Base.py:92-104)."""
 
     tf_numpy = True     # tf_values() / tf_gradients() hand float32 numpy arrays out (EasyDGL: tensors on the parameters' device)
+    lazy_adam_ok = False     # FLAGS.lazy_adam (DESIGN 4.14): only a model whose item backward ADDS into d_item (EasyDGL)
 
     def __init__(self, num_items, FLAGS):
         super().__init__()
@@ -65,6 +66,16 @@ class Sequential(nn.Module):
         self.neg_step = 0       # sampled training steps taken (host side; the `step` key of the lists; travels in checkpoints)
         if self.train_negatives < 0:
             raise ValueError(f"train_negatives={self.train_negatives}: the number of sampled negatives per row (0: full softmax)")
+        # lazy row-wise Adam for the item table: the table's gradient lands in place in the gradient arena and the
+        # optimizer walks only the rows the step used
+        self.lazy_adam = bool(getattr(FLAGS, "lazy_adam", False))
+        if self.lazy_adam and self.train_negatives <= 0:
+            raise ValueError("lazy_adam needs train_negatives > 0: the full softmax has a dense table gradient (every row of the "
+                             "catalogue is scored), there are no untouched rows to skip")
+        if self.lazy_adam and not self.lazy_adam_ok:
+            raise ValueError(f"lazy_adam: {type(self).__name__} is not supported — its item backward (edgl_embed_pos_bwd_*) "
+                             "overwrites d_item instead of adding into it; only EasyDGL runs the mode")
+        self._lazy_pending: list = []     # (seqs_i, labels, candidates) of the train_loss calls since the last optimizer step
         self._arena: Optional[torch.Tensor] = None
         self.pad = (0, 0)       # (dh_pad, dh_true) of a channel-padded model (a head dim the kernels do not tile)
         self._metrics = None
@@ -115,6 +126,15 @@ class Sequential(nn.Module):
         if self.act_dtype != torch.float32:
             self._shadow = torch.empty(total, device=device, dtype=self.act_dtype)
             self.sync_shadow()
+        if self.lazy_adam:
+            # the item table's range of the arena and the claim words of edgl_adam_rows (one per table row; not saved in
+            # checkpoints: a zeroed stamp is right after a restore)
+            tab = self.item_embs.lookup_table
+            lo = (tab.data_ptr() - arena.data_ptr()) // 4
+            self._lazy_range = (lo, lo + (tab.numel() + 7) // 8 * 8)
+            self._lazy_grad = tab.grad      # (the table's view of the gradient arena, the object _plist holds)
+            self._stamp = torch.zeros(tab.shape[0], device=device, dtype=torch.int32)
+            self._lazy_pending = []
         # operator modules (module/coding.py, module/temporal.py) read parameters through the owning model's compute copy
         for mod in self.modules():
             if mod is self:
@@ -144,7 +164,10 @@ class Sequential(nn.Module):
         return self._shadow[off:off + p.numel()].view(p.shape)
 
     def zero_grad_arena(self) -> None:
+        """Zero the whole gradient arena.  With lazy_adam this also restores the mode's invariant after an
+        interrupted step — the item table's view is all zeros between steps — and forgets the lists of that step."""
         self._table_grad_zero = None
+        self._lazy_pending = []
         self._grad_arena.zero_()
 
     def detach_grads(self) -> None:
@@ -154,11 +177,17 @@ class Sequential(nn.Module):
             p.grad = None
 
     def collect_grads(self) -> None:
-        """After that backward: copy the gradients into the flat arena with ONE multi-tensor launch and restore the views."""
+        """After that backward: copy the gradients into the flat arena with ONE multi-tensor launch and restore the views.  With
+        lazy_adam the item table's range is neither zero-filled nor copied: its gradient was added in place."""
         src, dst = [], []
+        lazy_view = self._lazy_grad if self.lazy_adam else None
         for p, view in self._plist:
             g = p.grad
-            if g is None:
+            if view is lazy_view:
+                if g is not None:
+                    raise RuntimeError("lazy_adam: an op returned a dense gradient for the item table (its gradient is added in "
+                                       "place into the gradient arena: pass d_table_out)")
+            elif g is None:
                 view.zero_()
             else:
                 src.append(g)
@@ -224,6 +253,10 @@ class Sequential(nn.Module):
         if dht in T.SUPPORTED_HEAD_DIMS or dht > max_pad_dim:
             return
         dhp = next(d for d in T.SUPPORTED_HEAD_DIMS if d >= dht)
+        if self.lazy_adam:
+            raise ValueError(f"lazy_adam: {who} with head dim {dht} runs channel-padded at {dhp}; mask_padded_grads would need its "
+                             "flat index over the item table, which the lazy mode never walks — choose a head dim of "
+                             f"{T.SUPPORTED_HEAD_DIMS}")
         self.pad = (dhp, dht)
         self.num_units = H * dhp
         self.qk_scale = float(dht) ** -0.5
@@ -396,8 +429,40 @@ class Sequential(nn.Module):
         produced by autograd (ops.L2Fn), so no l2 is folded in here."""
         self.settle_state()
         self.mask_padded_grads()     # (channel-padded models; idempotent: every optimizer entry point keeps the padded entries at zero)
+        if self.lazy_adam:
+            return self._lazy_optimizer_step()
         ops.adam_step(self._arena, self._grad_arena, self._adam_m, self._adam_v, self.learning_rate, self._adam_state,
                       0.0, None, self._shadow)
+
+    def _lazy_optimizer_step(self) -> None:
+        """FLAGS.lazy_adam: the dense TF-form Adam on the arena ranges in front of and behind the item table — the
+        first of them advances the step and leaves its learning rate (edgl_adam_step), the other reads it (edgl_adam_apply) —
+        and edgl_adam_rows on the table: the rows named by the (seqs_i, labels, candidates) of the train_loss calls since the last
+        step are updated once each and their gradient rows go back to zero; every other row keeps w, m and v bit for bit.
+        The l2 gradient of the item table, l2_reg * w, is folded in there (the `l2` argument): only touched rows decay, where
+        the dense mode decays every row in every step.  The other l2 tables and the output bias keep the dense update."""
+        lo, hi = self._lazy_range
+        first = True
+        for a, b in ((0, lo), (hi, self._arena.numel())):
+            if b <= a:
+                continue
+            sh = None if self._shadow is None else self._shadow[a:b]
+            if first:
+                ops.adam_step(self._arena[a:b], self._grad_arena[a:b], self._adam_m[a:b], self._adam_v[a:b], self.learning_rate,
+                              self._adam_state, 0.0, None, sh)
+            else:
+                ops.adam_apply(self._arena[a:b], self._grad_arena[a:b], self._adam_m[a:b], self._adam_v[a:b], self._adam_state,
+                               0.0, None, sh)
+            first = False
+        if first:
+            raise RuntimeError("lazy_adam: the arena holds nothing but the item table (no range advances the Adam step)")
+        tab = self.item_embs.lookup_table
+        n = tab.numel()
+        shadow = None if self._shadow is None else self._shadow[lo:lo + n].view(tab.shape)
+        pending, self._lazy_pending = self._lazy_pending, []
+        for ids, labels, cand in pending:      # (one launch per train_loss call; a row named by several is claimed once per step)
+            ops.adam_rows(tab.data, self._lazy_grad, self._adam_m[lo:lo + n].view(tab.shape), self._adam_v[lo:lo + n].view(tab.shape),
+                          shadow, ids, labels, cand, self._stamp, self._adam_state, self.l2_reg)
 
     # ---- Base.py:106-113 ---------------------------------------------------------------------------------
     def make_output_bias(self) -> nn.Parameter:
@@ -444,10 +509,16 @@ class Sequential(nn.Module):
         if candidates is None:
             candidates = ops.sample_negatives(None, labels, self.train_negatives, 1, self._negatives_hi(), self.train_neg_seed,
                                               self.neg_step, 0)
+        if self.lazy_adam:      # (the table gradient is added into the arena; the optimizer needs the step's lists)
+            self._lazy_lists = (labels, candidates)
+            return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic,
+                                         self._lazy_grad)
         return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic)
 
     def train_step(self, features, labels):
-        """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar)."""
+        """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar).
+        With FLAGS.lazy_adam the item table's gradient is consumed row by row by the optimizer: after the step the
+        table's `.grad` (and its entry of tf_gradients()) reads ZERO, not the step's gradient."""
         self.settle_state()
         ops.rng_advance(self._rng_state)
         self.detach_grads()

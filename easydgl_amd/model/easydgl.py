@@ -37,6 +37,7 @@ class _Block(nn.Module):
 
 class EasyDGL(Sequential):
     tf_numpy = False     # tf_values() / tf_gradients(): torch tensors on the parameters' device
+    lazy_adam_ok = True  # (edgl_encode_bwd_add_* ADD the item gradient into d_item)
 
     def __init__(self, num_items, FLAGS):
         super().__init__(num_items, FLAGS)
@@ -166,7 +167,7 @@ class EasyDGL(Sequential):
         return ops.EncodeFn.apply(tab, self.pcoding.pembs.lookup_table, self.mark_embs.lookup_table, self.compute(tab),
                                   ids, ts, self.mark_lookup_table, self.tcoding.scale, self.mask, self.time_scale,
                                   self._drop(self.hidden_dropout_rate, 1, is_training), self.act_dtype, self.pad,
-                                  self.deterministic)
+                                  self.deterministic, self._lazy_grad if (self.lazy_adam and is_training) else None)
 
     def encoder(self, features, is_training, gather_pos):
         """EasyDGL.py:70-146: returns (rows [B*Mg, C] at gather_pos, [lambda per block])."""
@@ -260,11 +261,19 @@ class EasyDGL(Sequential):
     # ---- EasyDGL.train (the loss it builds) ------------------------------------------------------------------
     def train_loss(self, features, labels, *, candidates=None):
         """EasyDGL.py:153-188 with the fused scoring/CE path (no [B*M, I] tensor).  `candidates` (int32 [B*M, N]) or
-        FLAGS.train_negatives > 0: the softmax of every masked position over its label and its own list (Sequential._score_ce)."""
+        FLAGS.train_negatives > 0: the softmax of every masked position over its label and its own list (Sequential._score_ce).
+        FLAGS.lazy_adam: the backward of this loss ADDS the item table's gradient into the table's view of the
+        gradient arena (no dense [I, C] temporary), and the call's (seqs_i, labels, candidates) are remembered for the optimizer
+        step, which walks only those rows.  The item table's l2 term still enters the loss (the value stays comparable with the
+        dense mode) but its backward returns no dense tensor: l2_reg * w reaches the table inside edgl_adam_rows, so only touched
+        rows decay.  The mark and position tables keep the dense l2 gradient."""
         rows, lams = self.encoder(features, True, self._gather_pos(features, True))
         loss = self._score_ce(rows, labels.reshape(-1).contiguous(), candidates)
+        if self.lazy_adam and torch.is_grad_enabled():
+            self._lazy_pending.append((features["seqs_i"],) + self._lazy_lists)
         if self.l2_reg != 0.0:                                                                     # :158
-            for p in (self.item_embs.lookup_table, self.mark_embs.lookup_table, self.pcoding.pembs.lookup_table):
+            loss = loss + ops.L2Fn.apply(self.item_embs.lookup_table, self.l2_reg, self.lazy_adam)
+            for p in (self.mark_embs.lookup_table, self.pcoding.pembs.lookup_table):
                 loss = loss + ops.L2Fn.apply(p, self.l2_reg)
         if self.ct_reg != 0.0:                                                                     # :159-175
             for lam in lams:

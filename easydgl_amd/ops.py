@@ -154,15 +154,27 @@ def segsum_plan(keys: torch.Tensor, I: int, nvalid: Optional[torch.Tensor] = Non
 # ------------------------------------------------------------------------------------------------
 # K1 encode
 # ------------------------------------------------------------------------------------------------
+def _table_out(d_table_out, shape, who):
+    """The `d_table_out` argument of EncodeFn / SampledCEFn: a contiguous f32 GPU tensor of the table's shape."""
+    if d_table_out is None:
+        return None
+    _ptr(d_table_out)
+    if d_table_out.dtype != torch.float32 or tuple(d_table_out.shape) != tuple(shape):
+        raise _lib.EdglError(f"{who}: d_table_out must be f32 {tuple(shape)} (got {d_table_out.dtype} {tuple(d_table_out.shape)})")
+    return d_table_out
+
+
 class EncodeFn(torch.autograd.Function):
     """EasyDGL.py:70-95.  item_c is the compute copy of the item table (the f32 master itself, or its
     bf16 shadow); gradients flow to the masters."""
 
     @staticmethod
     def forward(ctx, item_master, pos_tab, mark_emb, item_c, ids, ts, mark_table, tscale, mask_id, time_scale,
-                drop: Drop, act_dtype, pad=(0, 0), deterministic=False):
+                drop: Drop, act_dtype, pad=(0, 0), deterministic=False, d_table_out=None):
         """pad = (dh_pad, dh_true) of a channel-padded model (model/base.py), (0, 0) otherwise.  deterministic: the backward adds
-        the item gradient as ordered sums over a sorted plan (edgl_encode_bwd_add_det) instead of f32 atomics."""
+        the item gradient as ordered sums over a sorted plan (edgl_encode_bwd_add_det) instead of f32 atomics.  d_table_out
+        (f32 [I, C]): the backward ADDS the item gradient into it, allocates no [I, C] tensor and returns None for
+        the table master."""
         B, T = ids.shape
         I, C = item_c.shape
         E = mark_table.shape[1]
@@ -177,6 +189,7 @@ class EncodeFn(torch.autograd.Function):
         ctx.c_true = (C // pad[0] * pad[1]) if pad[0] else 0
         ctx.deterministic = bool(deterministic)
         ctx.meta = (B, T, C, E, I, drop, item_master.shape, pos_tab.shape, mark_emb.shape)
+        ctx.d_table_out = _table_out(d_table_out, item_master.shape, "EncodeFn")
         ctx.mark_non_differentiable(spans, marks)
         return x0, spans, marks
 
@@ -185,7 +198,8 @@ class EncodeFn(torch.autograd.Function):
         ids, marks = ctx.saved_tensors
         B, T, C, E, I, drop, ishape, pshape, mshape = ctx.meta
         dx0 = dx0.contiguous()
-        d_item = torch.zeros(ishape, device=dx0.device, dtype=torch.float32)
+        in_place = ctx.d_table_out is not None
+        d_item = ctx.d_table_out if in_place else torch.zeros(ishape, device=dx0.device, dtype=torch.float32)
         d_pos = torch.zeros(pshape, device=dx0.device, dtype=torch.float32)
         d_mark = torch.empty(mshape, device=dx0.device, dtype=torch.float32)
         ws = torch.empty(lib.edgl_encode_bwd_workspace(B, T, C), device=dx0.device, dtype=torch.float32)
@@ -198,7 +212,7 @@ class EncodeFn(torch.autograd.Function):
             check(lib.edgl_encode_bwd_add_ct(_ptr(ids), _ptr(marks), _ptr(dx0), None, None, B, T, C, E, I, float(drop.rate), drop.ptr(),
                                              drop.stream_id, _ptr(d_item), _ptr(d_pos), _ptr(d_mark), _ptr(ws), int(ctx.c_true),
                                              _code(dx0), _stream()), "edgl_encode_bwd")
-        return (d_item, d_pos, d_mark) + (None,) * 11
+        return (None if in_place else d_item, d_pos, d_mark) + (None,) * 12
 
 
 def _embed_pos_bwd(deterministic, ids, dx0, B, T, C, I, drop: Drop, d_item, d_pos, c_true):
@@ -624,11 +638,14 @@ class SampledCEFn(torch.autograd.Function):
     cand[r, :] (int32 [R, N]; -1 = empty slot) instead of the catalogue.  Same gradient contract as ScoreCEFn: d_rows in the compute
     dtype, a dense f32 d_table [I, C] (zero-filled, then scattered into) and d_bias [I - 1].  No compaction: rows of label 0 are
     skipped inside the kernels, so a row's list never depends on which other rows are weighted.
-    deterministic: the table / bias gradient is summed in plan order (edgl_cand_ce_table_det) instead of with f32 atomics."""
+    deterministic: the table / bias gradient is summed in plan order (edgl_cand_ce_table_det) instead of with f32 atomics.
+    d_table_out (f32 [I, C]): the backward ADDS the table gradient into it (both entry points add), allocates no
+    [I, C] tensor and returns None for the table master; d_bias stays a dense f32 [I - 1]."""
 
     @staticmethod
-    def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False):
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False, d_table_out=None):
         ctx.deterministic = bool(deterministic)
+        ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SampledCEFn")
         rows, labels, cand = rows.contiguous(), labels.reshape(-1).contiguous(), cand.contiguous()
         vals, label_val, lse = cand_ce_fwd(rows, table_c, out_bias, cand, labels)
         R = rows.shape[0]
@@ -648,7 +665,8 @@ class SampledCEFn(torch.autograd.Function):
         g = g.reshape(1).to(torch.float32).contiguous()
         d_rows = torch.empty_like(rows)
         dv = torch.empty((R, N + 1), device=dev, dtype=torch.float32)
-        d_table = torch.zeros((I, C), device=dev, dtype=torch.float32)
+        in_place = ctx.d_table_out is not None
+        d_table = ctx.d_table_out if in_place else torch.zeros((I, C), device=dev, dtype=torch.float32)
         d_bias = torch.zeros(I - 1, device=dev, dtype=torch.float32)
         det = ctx.deterministic
         check(lib.edgl_cand_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), _ptr(vals), _ptr(lse),
@@ -660,7 +678,7 @@ class SampledCEFn(torch.autograd.Function):
             plan = segsum_plan_buffer(n, I, dev)
             check(lib.edgl_cand_ce_table_det(_ptr(rows), _ptr(cand), _ptr(labels), _ptr(dv), R, C, I, N, _ptr(d_table), _ptr(d_bias),
                                              _ptr(keys), _ptr(plan), _code(rows), _stream()), "edgl_cand_ce_table_det")
-        return d_rows, d_table, d_bias, None, None, None, None
+        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None
 
 
 class ScoreLogitsFn(torch.autograd.Function):
@@ -731,10 +749,13 @@ def _whole_segment(n: int, device) -> torch.Tensor:
 
 
 class L2Fn(torch.autograd.Function):
-    """l2_reg * sum(w^2)/2 over one raw embedding table (coding.py:34-40)."""
+    """l2_reg * sum(w^2)/2 over one raw embedding table (coding.py:34-40).  forward_only (the lazily updated item table, DESIGN
+    4.14): the term enters the loss, the backward returns no dense tensor — its gradient l2 w reaches the table as the `l2`
+    argument of adam_rows, on the touched rows."""
 
     @staticmethod
-    def forward(ctx, w, l2):
+    def forward(ctx, w, l2, forward_only=False):
+        ctx.forward_only = bool(forward_only)
         seg = _whole_segment(w.numel(), w.device)
         out = torch.empty(1, device=w.device, dtype=torch.float32)
         ws = torch.empty(1024, device=w.device, dtype=torch.float32)
@@ -746,7 +767,9 @@ class L2Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (w,) = ctx.saved_tensors
-        return w * (g * ctx.l2), None
+        if ctx.forward_only:
+            return None, None, None
+        return w * (g * ctx.l2), None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1076,6 +1099,47 @@ def adam_step(param, grad, m, v, lr, state, l2, seg, shadow, beta1=0.9, beta2=0.
     check(lib.edgl_adam_step(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), param.numel(), float(lr), beta1, beta2, eps,
                              _ptr(state), float(l2), _ptr(seg), 0 if seg is None else seg.numel() // 2, _ptr(shadow),
                              _stream()), "edgl_adam_step")
+
+
+def adam_apply(param, grad, m, v, state, l2, seg, shadow, beta1=0.9, beta2=0.999, eps=1e-8):
+    """The parameter update of adam_step alone: the step count and learning rate are read from `state` as the last adam_step left them."""
+    check(lib.edgl_adam_apply(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), param.numel(), beta1, beta2, eps, _ptr(state), float(l2),
+                              _ptr(seg), 0 if seg is None else seg.numel() // 2, _ptr(shadow), _stream()), "edgl_adam_apply")
+
+
+def adam_rows(table, grad, m, v, shadow, ids, labels, cand, stamp, state, l2=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+    """Lazy row-wise Adam (edgl_adam_rows): the TF-form update on the rows of `table` f32 [I, C] that `ids` (int64, any
+    shape, or None), `labels` (int64 [R] or None) or `cand` (int32 [R, N] or None; the lists of rows with labels != 0) name, each
+    exactly once; their rows of `grad` are left at zero, every other row keeps its bits.  `stamp`: int32 [I], zero before the first
+    call.  The step count and learning rate are read from `state` (advance it first: adam_step on another range)."""
+    _ptr(table)                                              # (GPU tensors only: refused before anything else)
+    I, C = table.shape
+    for name, t in (("table", table), ("grad", grad), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (I, C):
+            raise _lib.EdglError(f"adam_rows: {name} must be f32 [{I}, {C}] (got {t.dtype} {tuple(t.shape)})")
+    if shadow is not None and (shadow.dtype != torch.bfloat16 or tuple(shadow.shape) != (I, C)):
+        raise _lib.EdglError(f"adam_rows: shadow must be bf16 [{I}, {C}] (got {shadow.dtype} {tuple(shadow.shape)})")
+    if stamp.dtype != torch.int32 or tuple(stamp.shape) != (I,):
+        raise _lib.EdglError(f"adam_rows: stamp must be int32 [{I}] (got {stamp.dtype} {tuple(stamp.shape)})")
+    n_ids = 0
+    if ids is not None:
+        if ids.dtype != torch.int64:
+            raise _lib.EdglError(f"adam_rows: ids must be int64 (got {ids.dtype})")
+        ids = ids.reshape(-1).contiguous()
+        n_ids = ids.numel()
+    R = N = 0
+    if labels is not None:
+        labels = _rank_labels(labels.reshape(-1), labels.numel(), "adam_rows")
+        R = labels.numel()
+    if cand is not None:
+        if labels is None or cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != R:
+            raise _lib.EdglError(f"adam_rows: candidates must be int32 [{R}, N] beside int64 labels [{R}] (got {cand.dtype} "
+                                 f"{tuple(cand.shape)})")
+        cand = cand.contiguous()
+        N = cand.shape[1]
+    check(lib.edgl_adam_rows(_ptr(table), _ptr(grad), _ptr(m), _ptr(v), _ptr(shadow), I, C, _ptr(ids) if n_ids else None, n_ids,
+                             _ptr(labels) if R else None, _ptr(cand) if R and N else None, R, N, _ptr(stamp), beta1, beta2, eps,
+                             _ptr(state), float(l2), _stream()), "edgl_adam_rows")
 
 
 class DropoutFn(torch.autograd.Function):

@@ -83,7 +83,13 @@ def args(argv=None):
                         "negatives drawn uniformly from the catalogue (fresh lists every step) instead of the whole catalogue; every "
                         "batch goes through model.train_step (no static engine, no --graph).  0: full softmax")
     p.add_argument("--train_neg_seed", type=int, default=0, help="seed of the sampled training negatives")
+    p.add_argument("--lazy_adam", action="store_true",
+                   help="EasyDGL with --train_negatives: lazy row-wise Adam for the item table (DESIGN 4.14, TensorFlow's "
+                        "LazyAdamOptimizer) — the table gradient lands in place and the optimizer updates only the rows the step used "
+                        "(input ids, labels, negatives); every other parameter keeps the dense Adam")
     a = p.parse_args(argv)
+    if a.lazy_adam and a.train_negatives <= 0:
+        p.error("--lazy_adam needs --train_negatives N > 0: the full softmax has a dense table gradient, there are no untouched rows")
     if a.train_negatives < 0:
         p.error("--train_negatives: the number of sampled negatives per position (0: full softmax)")
     if a.train_negatives > 0 and a.graph:
@@ -158,6 +164,9 @@ def load_checkpoint(model, path: str) -> None:
         model._adam_state.copy_(ck["adam_state"])
         model._rng_state.copy_(ck["rng_state"])
     model.neg_step = int(ck.get("neg_step", 0))      # (optional field: sampled training steps taken)
+    if getattr(model, "lazy_adam", False):           # (the claim words are not saved; the step count may have gone back)
+        model._stamp.zero_()
+        model.zero_grad_arena()
     model._state_ahead = False     # the file holds "steps taken" (save_checkpoint settles the engine's look-ahead)
     model.sync_shadow()
 

@@ -786,6 +786,21 @@ int edgl_adam_apply_ex(float* param, float* grad, float* m, float* v, long n, fl
                        const float* slabs_a, long stride_a, long lo_a, long hi_a, long zero_first_a,
                        const float* slabs_b, long stride_b, long lo_b, long hi_b, int nslab,
                        const uint64_t* rng_cur, uint64_t* step_next, uint64_t* rng_next, float lr, void* stream);
+/* Lazy row-wise Adam for the item table of sampled-softmax training (k_adam_rows.hip; TensorFlow's LazyAdamOptimizer):
+ * edgl_adam_apply's update on the TOUCHED rows of table f32 [I, C] and on no other.  Row i in [1, I) is touched when it occurs in
+ * ids (int64 [n_ids]: the batch's input ids; NULL with n_ids = 0), or is labels[r] (int64 [R]) of a row with 1 <= labels[r] < I, or
+ * is cand[r, n] (int32 [R, N]; NULL with N = 0) of such a row; ids <= 0 or >= I are skipped, the list of a row of weight 0 touches
+ * nothing, row 0 is never touched — a function of the integer inputs alone.  A touched row is updated exactly ONCE however often it
+ * is listed: g' = g + l2 w, m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) g'^2, w -= lr_t m / (sqrt(v) + eps) with lr_t read from
+ * step_state as edgl_adam_apply reads it (the caller has advanced the step: edgl_adam_step / edgl_step_begin), shadow (bf16 [I, C] or
+ * NULL) = bf16(w), and its row of grad is written back as ZEROS; an untouched row keeps every bit of w, m, v, shadow and grad.
+ * stamp: int32 [I], caller-owned, zero before the first call (and again whenever the step count is set back): the step count is
+ * raised into stamp[id] with one returning integer atomic per entry and the entry that raised it owns the row.  No float atomics,
+ * no sort, no read-back.  f32 masters, C % 4 == 0, 4 <= C <= 512, I > 1, R (N + 1) < 2^31, arrays 16-byte aligned; anything else is
+ * EDGL_ERR_SHAPE, checked before any pointer is read.  Base.py:142-144 on the rows of the step. */
+int edgl_adam_rows(float* table, float* grad, float* m, float* v, void* shadow, int I, int C, const int64_t* ids, long n_ids,
+                   const int64_t* labels, const int32_t* cand, int R, int N, int32_t* stamp, float beta1, float beta2, float eps,
+                   const uint64_t* step_state, float l2, void* stream);
 /* out[0] / out[1]: float offsets of the d_table [nslab][I * C] / d_bias [nslab][I - 1] slabs inside the edgl_score_flash_workspace
  * buffer, out[2] = nslab — what edgl_score_flash_bwd_ex leaves there with (defer_label_term & 4) (requires & 1, the whole item range
  * and gscale == NULL; otherwise the flag is ignored and the slabs are reduced as usual).  EasyDGL.py:149-151 backward. */

@@ -1,13 +1,20 @@
 """Sampled-softmax training against the full-catalogue softmax, in ONE process:
 
-    python tools/train_negatives_bench.py [--rounds 5] [--steps 20] [--models EasyDGL,TiSASREC] [--out profiles/train_negatives.txt]
+    python tools/train_negatives_bench.py [--rounds 5] [--steps 20] [--models EasyDGL,TiSASREC] [--sections full,lazy]
+                                          [--out profiles/train_negatives.txt]
 
 Per shape (sequences x positions x channels x items; bf16) and model: `model.train_step` with train_negatives N in {0, 100, 1000} —
 N = 0 is the full softmax (ops.ScoreCEFn), the path every step took before sampled training existed — and the loss op alone,
 forward + backward on the model's scored rows: ops.ScoreCEFn against ops.SampledCEFn (atomic and ordered table gradient), with
 the atomic bytes R_w (N + 1) C 4 of the table gradient (R_w weighted rows) over the chip-wide rate of 1.3 TB/s beside it.  Each
 round times `steps` calls between device events after a warm-up; the table gives the median and the spread (min .. max) over the
-rounds.  Needs a GPU: there is no fallback."""
+rounds.
+Section `lazy` (EasyDGL): `train_step` with N in {10, 100} sampled negatives, the dense sampled step against
+FLAGS.lazy_adam, with the distinct rows the step touches and the byte model beside them: touched rows x 8.5 C 4 bytes (w, g, m, v read;
+w, m, v, zeros and the bf16 shadow written) against the dense path's 14.5 I C 4 (two zero fills, their sum, the copy into the arena
+and the dense Adam; the l2 term's dense gradient, which the lazy mode also drops, is not counted).  `--sections lazy` keeps the
+part of --out in front of the section's heading and replaces the rest.
+Needs a GPU: there is no fallback."""
 import argparse
 import os
 import statistics
@@ -24,6 +31,8 @@ from easydgl_amd import ops  # noqa: E402
 # (sequences, positions, channels, items): the headline and a config-3-shaped case (BASELINE.json configs[2])
 SHAPES = [(512, 100, 128, 20000), (512, 200, 256, 1000000)]
 NEGATIVES = (0, 100, 1000)
+LAZY_NEGATIVES = (10, 100)
+LAZY_HEADING = "lazy row-wise Adam for the item table (DESIGN 4.14)"
 ATOMIC_RATE = 1.3e12      # bytes of f32 atomic adds per second, chip-wide
 
 
@@ -48,8 +57,9 @@ def fmt(ts):
     return f"{statistics.median(ts):9.4f} ({min(ts):.4f} .. {max(ts):.4f})"
 
 
-def build(name, B, L, C, num_items):
-    F = SimpleNamespace(model=name, num_items=num_items, num_units=C, num_heads=8, num_blocks=1, seqslen=L, masklen=L // 5,
+def build(name, B, L, C, num_items, negatives=0, lazy=False):
+    F = SimpleNamespace(train_negatives=negatives, lazy_adam=lazy,
+                        model=name, num_items=num_items, num_units=C, num_heads=8, num_blocks=1, seqslen=L, masklen=L // 5,
                         timelen=256, time_scale=86400.0, learning_rate=5e-4, l2_reg=1e-4, ct_reg=1e-7, hidden_dropout_rate=0.1,
                         attention_probs_dropout_rate=0.1, compute_dtype="bf16", num_train_steps=None, num_warmup_steps=None, seed=9876)
     if name == "EasyDGL":
@@ -82,16 +92,75 @@ def op_call(model, rows, labels, cand, det):
     torch.autograd.grad(loss, (r, tab, model.output_bias))
 
 
+def touched_rows(model, feats, labels, N):
+    """Distinct item-table rows one sampled step names: input ids, labels of weighted rows and their lists (the step's own draw)."""
+    I = model.item_embs.lookup_table.shape[0]
+    lab = labels.reshape(-1).contiguous()
+    cand = ops.sample_negatives(None, lab, N, 1, model._negatives_hi(), model.train_neg_seed, model.neg_step, 0)
+    hit = torch.zeros(I, device=lab.device, dtype=torch.bool)
+    live = (lab >= 1) & (lab < I)
+    for ids in (feats["seqs_i"].reshape(-1), lab[live], cand[live].reshape(-1).long()):
+        hit[ids[(ids >= 1) & (ids < I)]] = True
+    return int(hit.sum())
+
+
+def lazy_section(args, lines):
+    lines += [f"{LAZY_HEADING}: ms per `train_step`, median (min .. max) of {args.rounds} rounds x {args.steps} calls; bf16, "
+              f"dropout 0.1 / 0.1, l2 1e-4; dense = the sampled step with the flag unset", ""]
+    for B, L, C, num_items in SHAPES:
+        res = {}
+        for lazy in (False, True):
+            model, feats, labels = build("EasyDGL", B, L, C, num_items, LAZY_NEGATIVES[0], lazy)
+            I = model.item_embs.lookup_table.shape[0]
+            for N in LAZY_NEGATIVES:
+                model.train_negatives = N
+                res[(lazy, N)] = (rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps),
+                                  touched_rows(model, feats, labels, N), int((labels != 0).sum()), I)
+            model = feats = labels = None
+            torch.cuda.empty_cache()
+        I = res[(True, LAZY_NEGATIVES[0])][3]
+        lines.append(f"EasyDGL  {B} x {L} x {C}, {I} table rows, {res[(True, LAZY_NEGATIVES[0])][2]} weighted rows; dense path "
+                     f"{14.5 * I * C * 4 / 1e6:9.1f} MB per step")
+        for N in LAZY_NEGATIVES:
+            d, z = res[(False, N)], res[(True, N)]
+            md, mz = statistics.median(d[0]), statistics.median(z[0])
+            lines.append(f"  N = {N:5d}  dense {fmt(d[0])}  lazy {fmt(z[0])}  x{mz / md:6.3f} of dense   distinct rows {z[1]:8d} "
+                         f"({z[1] / I:5.3f} of the table)   lazy bytes {z[1] * 8.5 * C * 4 / 1e6:9.1f} MB")
+            print(lines[-1], flush=True)
+        lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--models", default="EasyDGL,TiSASREC")
+    ap.add_argument("--sections", default="full,lazy")
     ap.add_argument("--out", default=os.path.join("profiles", "train_negatives.txt"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_negatives_bench.py: needs a GPU")
-    lines = [f"sampled-softmax training vs the full softmax: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} "
+    sections = args.sections.split(",")
+    lines = []
+    if "full" not in sections and os.path.exists(args.out):      # keep what stands in front of the lazy section
+        old = open(args.out).read().split("\n")
+        cut = next((i for i, ln in enumerate(old) if ln.startswith(LAZY_HEADING)), len(old))
+        lines = old[:cut]
+        while lines and not lines[-1]:
+            lines.pop()
+        lines.append("")
+    if "full" in sections:
+        full_section(args, lines)
+    if "lazy" in sections:
+        lazy_section(args, lines)
+    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines))
+    print("wrote", args.out)
+
+
+def full_section(args, lines):
+    lines += [f"sampled-softmax training vs the full softmax: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} "
              f"calls, one process; bf16, dropout 0.1 / 0.1; N = 0 is the full-catalogue softmax (ops.ScoreCEFn)", ""]
     for name in args.models.split(","):
         for B, L, C, num_items in SHAPES:
@@ -125,10 +194,6 @@ def main():
             lines.append("")
             model = feats = labels = rows = None
             torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines))
-    print("wrote", args.out)
 
 
 if __name__ == "__main__":
