@@ -969,12 +969,13 @@ __device__ __forceinline__ void copy_in2(char* d0, const bf16* s0, long ld0, cha
         *reinterpret_cast<uint4*>(d1 + vec_off(row, cv)) = b[i];
     }
 }
-__device__ __forceinline__ void copy_out(bf16* dst, long ld, const char* img, int T) {
-    const int nv = T * 16;
+// image -> global [T, 128] (row stride ld): uniform base + 32-bit lane offset, the thread's offsets rebuilt by every call
+__device__ __forceinline__ void copy_out(bf16* dst, int ld, const char* img, int T) {
+    const int nv = T * 16, tid = fresh_tid();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int v = threadIdx.x + i * NTHR, row = v >> 4, cv = v & 15;
-        if (v < nv) *reinterpret_cast<uint4*>(dst + (long)row * ld + cv * 8) = *reinterpret_cast<const uint4*>(img + vec_off(row, cv));
+        const int v = tid + i * NTHR, row = v >> 4, cv = v & 15;
+        if (v < nv) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + (uint32_t)((row * ld + cv * 8) * 2)) = *reinterpret_cast<const uint4*>(img + vec_off(row, cv));
     }
 }
 // accumulators (bias not yet added) -> f32 staging image, rows < T only (the image is exactly two bf16 images long)
@@ -988,8 +989,8 @@ __device__ __forceinline__ void stage_acc(char* stg, const f32x4 (&acc)[MAXRT], 
 // GELU pass over the staging image: a thread owns 8 columns (cv) of rows rsub + 32 k.  dact = gelu'(pre) and act = gelu(pre) go to
 // global memory at once; act also into image `act_img` — behind a barrier when that image is part of the staging area (SYNC).
 template <bool SYNC>
-__device__ __forceinline__ void gelu_pass(const char* stg, const float* bias_g, bf16* dact_g, bf16* act_g, long ldg, char* act_img, int T) {
-    const int cv = threadIdx.x & 15, rsub = threadIdx.x >> 4;
+__device__ __forceinline__ void gelu_pass(const char* stg, const float* bias_g, bf16* dact_g, bf16* act_g, int ldg, char* act_img, int T) {
+    const int tid = fresh_tid(), cv = tid & 15, rsub = tid >> 4;
     const float4 b0 = *reinterpret_cast<const float4*>(bias_g + cv * 8), b1 = *reinterpret_cast<const float4*>(bias_g + cv * 8 + 4);
     const int s0 = rsub * 512 + (((2 * cv) ^ (rsub & 15)) << 4);          // (r & 15 == rsub & 15 for r = rsub + 32 k)
     uint4 keep0 = make_uint4(0, 0, 0, 0), keep1 = keep0, keep2 = keep0, keep3 = keep0;
@@ -1011,8 +1012,9 @@ __device__ __forceinline__ void gelu_pass(const char* stg, const float* bias_g, 
                 // registers of six more chains are what this kernel does not have
                 if (j & 1) __builtin_amdgcn_sched_barrier(0);
             }
-            st16<bf16>(dact_g + (long)r * ldg + cv * 8, dact);
-            st16<bf16>(act_g + (long)r * ldg + cv * 8, act);
+            const uint32_t go = (uint32_t)((r * ldg + cv * 8) * 2);      // uniform base + 32-bit lane offset
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dact_g) + go) = *reinterpret_cast<const uint4*>(&dact);
+            *reinterpret_cast<uint4*>(reinterpret_cast<char*>(act_g) + go) = *reinterpret_cast<const uint4*>(&act);
             const uint4 a = *reinterpret_cast<const uint4*>(&act);
             if (!SYNC) *reinterpret_cast<uint4*>(act_img + vec_off(r, cv)) = a;
             else if (k == 0) keep0 = a;
@@ -1034,8 +1036,10 @@ __device__ __forceinline__ void gelu_pass(const char* stg, const float* bias_g, 
 // store issued before it — behind a copy_out or a GELU pass that is a full HBM write acknowledge (2-3 us with 512 workgroups storing
 // at once), and a sample has ten such batches.  Hence: the three parameter vectors used before the first store batches go to
 // registers in the prologue, the others wait in the LDS table, and a product's weight fragments are requested BEFORE the store
-// batch in front of it and their wait pinned (touch_regs) in front of that batch's first store — except where 16 more registers do
-// not exist (the out-dense fragments of the second hidden half: one load behind the GELU pass's stores per sample).
+// batch in front of it and their wait pinned (touch_regs) in front of that batch's first store — except the out-dense fragments of
+// the second hidden half (one load behind the GELU pass's stores per sample).  The same holds for a SPILLED register: its reload
+// from scratch is a load.  The kernel must stay free of scratch (tests/test_tail2_resources.py): every store batch rebuilds its
+// offsets, and the lane's operand offsets are rebuilt behind it, so that none of them lives across the kernel.
 template <int NRT>
 __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1043,8 +1047,10 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     float* red = reinterpret_cast<float*>(smem + OFF_RED);
     float* par = reinterpret_cast<float*>(smem + OFF_PAR);
     const int b = blockIdx.x, T = p.T;
-    const Lane L = make_lane();
-    const int n0 = L.wave * 16, nl = L.nl, l15 = L.l15;
+    // rebuilt (fresh) behind every store batch, as in the backward: held across the kernel they went to scratch
+    Lane L = make_lane();
+    int n0 = L.wave * 16, nl = L.nl, l15 = L.l15;
+    auto fresh = [&]() { L = fresh_lane(); n0 = L.wave * 16; nl = L.nl; l15 = L.l15; };
     const long row0 = (long)b * T;
     const ChanPad cpad = chan_pad<8>(nl, p.dhp, p.dht);
     if ((int)threadIdx.x < C) {
@@ -1093,6 +1099,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     lds_barrier();
     touch_regs(wf);                  // every load so far has arrived: stores may start
     copy_out(p.ao + row0 * C, C, R, T);
+    fresh();
     // ---- a1 = LN1(z1) (EasyDGL.py:116) -> P (att is consumed) ---------------------------------------------------------------------------
     {
         float mean, rstd;
@@ -1109,6 +1116,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     }
     lds_barrier();
     copy_out(p.a1 + row0 * C, C, P, T);
+    fresh();
     // ---- f = gelu(a1.Wi + bi), two halves of C hidden channels; o accumulates f.Wout half by half (EasyDGL.py:120-125) ----------------
     f32x4 acc3[MAXRT];
     zero_acc<NRT>(acc3);
@@ -1121,6 +1129,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
         lds_barrier();
         touch_regs(wo); touch_regs(wf);          // (acc3 is not live yet: both sets fit across the pass)
         gelu_pass<true>(Q, par + PAR_BI * C, p.pre_f + row0 * 2 * C, p.f + row0 * 2 * C, 2 * C, R, T);
+        fresh();
         lds_barrier();
         gemm<NRT>(wo, R, L, acc3);
     }
@@ -1131,7 +1140,8 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
         stage_acc<NRT>(Q, acc, L, T);
         lds_barrier();
         gelu_pass<true>(Q, par + (PAR_BI + 1) * C, p.pre_f + row0 * 2 * C + C, p.f + row0 * 2 * C + C, 2 * C, R, T);
-        wf = load_wfrags<NKB>(p.WoutT + (long)n0 * 2 * C + C, 2 * C, L.lane);       // out dense, second half (behind the pass's stores: no registers for it earlier)
+        fresh();
+        wf = load_wfrags<NKB>(p.WoutT + (long)n0 * 2 * C + C, 2 * C, L.lane);       // out dense, second half (behind the pass's stores; requested ahead of them it measured nothing: DESIGN rule 80)
         lds_barrier();
         gemm<NRT>(wf, R, L, acc3);
     }
@@ -1156,6 +1166,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     lds_barrier();
     if (p.head) touch_regs(wf);
     copy_out(p.o + row0 * C, C, Q, T);
+    fresh();
     {
         float mean, rstd;
         joint_moments<8>(z, NRT, T, L.lane, red, mean, rstd, cpad);
@@ -1173,12 +1184,14 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_fwd_kernel(TailP p) {
     lds_barrier();
     copy_out(p.y + row0 * C, C, R, T);
     if (!p.head) return;
+    fresh();
     // ---- head: so = gelu(y.Wt + bt) ; rows = LN3(so)[masked positions] (EasyDGL.py:136-146): staging = P + Q, so -> R, rows -> Q ----------
     zero_acc<NRT>(acc);
     gemm<NRT>(wf, R, L, acc);
     stage_acc<NRT>(P, acc, L, T);                    // (a1 and o are consumed: every wave is past the barrier behind LN2)
     lds_barrier();                                   // ... which also says that nobody reads y (R) any more
     gelu_pass<false>(P, par + PAR_BT * C, p.pre_t + row0 * C, p.so + row0 * C, C, R, T);
+    fresh();
     lds_barrier();
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt) ld_bf4(reinterpret_cast<const bf16*>(R + L.quad + rt * 4096), z[rt]);   // so, rounded through the activation dtype
@@ -1241,16 +1254,6 @@ __device__ __forceinline__ void store_part(float* part_b, const Lane& L, const f
     if (L.l15 == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { part_b[L.nl + r] = dbe[r]; part_b[C + L.nl + r] = dga[r]; }
-    }
-}
-
-// copy_out with the thread's offsets rebuilt by every call (uniform base + 32-bit lane offset)
-__device__ __forceinline__ void copy_out_b(bf16* dst, int ld, const char* img, int T) {
-    const int nv = T * 16, tid = fresh_tid();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int v = tid + i * NTHR, row = v >> 4, cv = v & 15;
-        if (v < nv) *reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + (uint32_t)((row * ld + cv * 8) * 2)) = *reinterpret_cast<const uint4*>(img + vec_off(row, cv));
     }
 }
 
@@ -1406,7 +1409,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
         }
         lds_barrier();
         store_part(p.part3 + (long)b * 2 * C, L, dga, dbe);
-        copy_out_b(p.d_pre_t + row0 * C, C, R, T);
+        copy_out(p.d_pre_t + row0 * C, C, R, T);
         // the product's fragments and the next phase's inputs (behind the store batch: see the kernel's header comment)
         EDGL_PIN();
         wf = load_wfrags<NKB>(p.Wt + (long)n0 * C, C, L.lane);
@@ -1463,7 +1466,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
     }
     lds_barrier();
     store_part(p.part2 + (long)b * 2 * C, L, dga, dbe);
-    copy_out_b(p.d_o + row0 * C, C, Q, T);
+    copy_out(p.d_o + row0 * C, C, Q, T);
     EDGL_PIN();
     qa = load_quads<NRT>(p.pre_f + row0 * 2 * C, 2 * C, T);        // gelu'(pre_f), first half
     wf = load_wfrags<NKB>(p.Wout + (long)n0 * C, C, L.lane);
@@ -1492,7 +1495,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
             wi = load_wfrags<NKB>(p.Wi + (long)n0 * 2 * C + C, 2 * C, L.lane);
         }
         lds_barrier();
-        copy_out_b(p.d_pre_f + row0 * 2 * C + h * C, 2 * C, R, T);
+        copy_out(p.d_pre_f + row0 * 2 * C + h * C, 2 * C, R, T);
         // (the accumulator tiles of the product above are dead: room for the operands of what follows this half)
         EDGL_PIN();
         if (h == 0) {
@@ -1548,8 +1551,8 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
     }
     lds_barrier();
     store_part(p.part1 + (long)b * 2 * C, L, dga, dbe);
-    copy_out_b(p.d_ao + row0 * C, C, Q, T);
-    copy_out_b(p.d_res1 + row0 * C, C, R, T);
+    copy_out(p.d_ao + row0 * C, C, Q, T);
+    copy_out(p.d_res1 + row0 * C, C, R, T);
     EDGL_PIN();
     wf = load_wfrags<NKB>(p.Wo + (long)n0 * C, C, L.lane);
     PHB_MARK(6);   // LN1', d_ao, d_res1
@@ -1563,7 +1566,7 @@ __global__ __launch_bounds__(NTHR, 4) void tail2_bwd_kernel(TailBwdP p) {
         __builtin_amdgcn_sched_barrier(0);      // (one row tile at a time)
     }
     lds_barrier();
-    copy_out_b(p.d_att + row0 * C, C, P, T);
+    copy_out(p.d_att + row0 * C, C, P, T);
     PHB_MARK(7);   // dX(Wo), d_att
     PHB_FLUSH();
 }
