@@ -135,6 +135,9 @@ SIGNATURES = {
     "edgl_cand_ce_fwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "edgl_cand_ce_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, I, P]),
     "edgl_cand_ce_table_det": (I, [P, P, P, P, I, I, I, I, P, P, P, P, I, P]),
+    "edgl_shared_ce_workspace": (L, [I, I, I, I]),
+    "edgl_shared_ce_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
+    "edgl_shared_ce_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
     "edgl_rank_metrics_from_rank_rows": (I, [P, I, P, I, P, P]),
     "edgl_topk_merge": (I, [P, P, I, I, I, P, P, P]),
     "edgl_rank_metrics": (I, [P, I, I, P, P, P]),

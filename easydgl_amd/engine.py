@@ -61,6 +61,9 @@ class TrainEngine:
         if int(getattr(model, "train_negatives", 0) or 0) > 0:
             raise _lib.EdglError("TrainEngine: the static engine scores the whole catalogue; a model with train_negatives > 0 "
                                  "(sampled-softmax training, DESIGN 4.13) trains on the autograd path: model.train_step")
+        if int(getattr(model, "shared_negatives", 0) or 0) > 0:
+            raise _lib.EdglError("TrainEngine: the static engine scores the whole catalogue; a model with shared_negatives > 0 "
+                                 "(sampled-softmax training, DESIGN 4.15) trains on the autograd path: model.train_step")
         # the environment switches (class docstring): read here, once, and nowhere else in the engine
         env = os.environ.get
         self.sw_flash_ce = env("EDGL_FLASH_CE", "1") != "0"

@@ -66,11 +66,19 @@ class Sequential(nn.Module):
         self.neg_step = 0       # sampled training steps taken (host side; the `step` key of the lists; travels in checkpoints)
         if self.train_negatives < 0:
             raise ValueError(f"train_negatives={self.train_negatives}: the number of sampled negatives per row (0: full softmax)")
+        # one negative list per step, shared by every row: S > 0 ids drawn once per step; a different estimator
+        self.shared_negatives = int(getattr(FLAGS, "shared_negatives", 0) or 0)
+        if self.shared_negatives < 0 or self.shared_negatives > ops.MAX_SHARED:
+            raise ValueError(f"shared_negatives={self.shared_negatives}: the length of the step's shared negative list "
+                             f"(0: off, at most {ops.MAX_SHARED})")
+        if self.shared_negatives > 0 and self.train_negatives > 0:
+            raise ValueError("shared_negatives and train_negatives are both set: one estimator per run (per-row lists, DESIGN "
+                             "4.13, or one shared list, DESIGN 4.15)")
         # lazy row-wise Adam for the item table: the table's gradient lands in place in the gradient arena and the
         # optimizer walks only the rows the step used
         self.lazy_adam = bool(getattr(FLAGS, "lazy_adam", False))
-        if self.lazy_adam and self.train_negatives <= 0:
-            raise ValueError("lazy_adam needs train_negatives > 0: the full softmax has a dense table gradient (every row of the "
+        if self.lazy_adam and self.train_negatives <= 0 and self.shared_negatives <= 0:
+            raise ValueError("lazy_adam needs train_negatives > 0 or shared_negatives > 0: the full softmax has a dense table gradient (every row of the "
                              "catalogue is scored), there are no untouched rows to skip")
         if self.lazy_adam and not self.lazy_adam_ok:
             raise ValueError(f"lazy_adam: {type(self).__name__} is not supported — its item backward (edgl_embed_pos_bwd_*) "
@@ -203,6 +211,9 @@ class Sequential(nn.Module):
         eager steps that precede the capture are real optimizer steps."""
         if self.train_negatives > 0:      # (the lists are keyed by a host-side step count: a replay would draw one list for ever)
             raise ValueError("graphed_train_step: a model with train_negatives > 0 (sampled-softmax training, DESIGN 4.13) trains "
+                             "through train_step; its step is not captured into a graph")
+        if self.shared_negatives > 0:
+            raise ValueError("graphed_train_step: a model with shared_negatives > 0 (sampled-softmax training, DESIGN 4.15) trains "
                              "through train_step; its step is not captured into a graph")
         static_f = {k: v.clone() for k, v in features.items()}
         static_l = labels.clone()
@@ -497,23 +508,40 @@ class Sequential(nn.Module):
         return (labels[:, -1] if labels.dim() == 2 else labels).contiguous()
 
     # ---- Sequential.train (Base.py:119-144) ------------------------------------------------------------------
-    def _score_ce(self, rows, labels, candidates=None):
+    def _score_ce(self, rows, labels, candidates=None, shared=None):
         """The cross-entropy of a training step over `rows` [R, C] / `labels` int64 [R]: the softmax over the catalogue
         (ops.ScoreCEFn), or — with `candidates` (int32 [R, N], one list per scored row) or FLAGS.train_negatives = N > 0 — over each
         row's label and its own list (ops.SampledCEFn, DESIGN 4.13).  Sampled lists are keyed by (train_neg_seed, neg_step, row);
         train_step advances neg_step, so a resumed run draws the lists the uninterrupted run would have drawn, and calling
-        train_loss twice in between scores the same lists.  A range [1, hi) too small for the sampler is refused by the sampler."""
+        train_loss twice in between scores the same lists.  A range [1, hi) too small for the sampler is refused by the sampler.
+        `shared` (int32 [S], one list for every row) or FLAGS.shared_negatives = S > 0: each row's label and the step's ONE list
+        (ops.SharedCEFn), drawn once through the same sampler, keyed by (train_neg_seed, neg_step)."""
         tab = self.item_embs.lookup_table
+        if candidates is not None and shared is not None:
+            raise ValueError("_score_ce: both `candidates` and `shared` are given: one estimator per call")
+        if shared is None and candidates is None and self.shared_negatives > 0:
+            shared = self.draw_shared_negatives(labels.device)
+        if shared is not None:
+            if self.lazy_adam:
+                self._lazy_lists = (labels, None, shared)
+            return ops.SharedCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, shared, self.deterministic,
+                                        self._lazy_grad if self.lazy_adam else None)
         if candidates is None and self.train_negatives <= 0:
             return ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, self.deterministic)
         if candidates is None:
             candidates = ops.sample_negatives(None, labels, self.train_negatives, 1, self._negatives_hi(), self.train_neg_seed,
                                               self.neg_step, 0)
         if self.lazy_adam:      # (DESIGN 4.14: the table gradient is added into the arena; the optimizer needs the step's lists)
-            self._lazy_lists = (labels, candidates)
+            self._lazy_lists = (labels, candidates, None)
             return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic,
                                          self._lazy_grad)
         return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic)
+
+    def draw_shared_negatives(self, device, step=None):
+        """int32 [S]: the shared list of step `step` (default: neg_step) — the device sampler asked for one row of S negatives."""
+        one = torch.zeros(1, device=device, dtype=torch.int64)
+        return ops.sample_negatives(None, one, self.shared_negatives, 1, self._negatives_hi(), self.train_neg_seed,
+                                    self.neg_step if step is None else step, 0).reshape(-1)
 
     def train_step(self, features, labels):
         """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar).
@@ -527,7 +555,7 @@ class Sequential(nn.Module):
         self.collect_grads()
         self.mask_padded_grads()
         self.optimizer_step()
-        if self.train_negatives > 0:
+        if self.train_negatives > 0 or self.shared_negatives > 0:
             self.neg_step += 1
         return loss.detach()
 

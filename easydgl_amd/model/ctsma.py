@@ -124,11 +124,12 @@ class CTSMA(Sequential):
         tab = self.item_embs.lookup_table
         return ops.ScoreLogitsFn.apply(rows, tab, self.output_bias, self.compute(tab))
 
-    def train_loss(self, features, labels, *, candidates=None):
+    def train_loss(self, features, labels, *, candidates=None, shared=None):
         """CTSMA.train (CTSMA.py:95-127) with the fused scoring / cross-entropy (no [B*T, I] tensor).  `candidates` (int32 [B*T, N])
-        or FLAGS.train_negatives > 0: the softmax of every position over its label and its own list (Sequential._score_ce)."""
+        or FLAGS.train_negatives > 0: the softmax of every position over its label and its own list (Sequential._score_ce);
+        `shared` (int32 [S]) or FLAGS.shared_negatives > 0: over its label and the step's ONE list."""
         rows, lams = self.encoder(features, True, None)
-        loss = self._score_ce(rows.reshape(-1, self.num_units), labels.reshape(-1).contiguous(), candidates)
+        loss = self._score_ce(rows.reshape(-1, self.num_units), labels.reshape(-1).contiguous(), candidates, shared)
         if self.l2_reg != 0.0:
             for p in (self.item_embs.lookup_table, self.pcoding.pembs.lookup_table):
                 loss = loss + ops.L2Fn.apply(p, self.l2_reg)

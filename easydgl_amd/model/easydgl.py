@@ -259,18 +259,22 @@ class EasyDGL(Sequential):
         return ops.ScoreLogitsFn.apply(rows, tab, self.output_bias, self.compute(tab))
 
     # ---- EasyDGL.train (the loss it builds) ------------------------------------------------------------------
-    def train_loss(self, features, labels, *, candidates=None):
+    def train_loss(self, features, labels, *, candidates=None, shared=None):
         """EasyDGL.py:153-188 with the fused scoring/CE path (no [B*M, I] tensor).  `candidates` (int32 [B*M, N]) or
         FLAGS.train_negatives > 0: the softmax of every masked position over its label and its own list (Sequential._score_ce).
         FLAGS.lazy_adam: the backward of this loss ADDS the item table's gradient into the table's view of the
         gradient arena (no dense [I, C] temporary), and the call's (seqs_i, labels, candidates) are remembered for the optimizer
         step, which walks only those rows.  The item table's l2 term still enters the loss (the value stays comparable with the
         dense mode) but its backward returns no dense tensor: l2_reg * w reaches the table inside edgl_adam_rows, so only touched
-        rows decay.  The mark and position tables keep the dense l2 gradient."""
+        rows decay.  The mark and position tables keep the dense l2 gradient.
+        `shared` (int32 [S]) or FLAGS.shared_negatives > 0: every masked position against its label and the step's ONE
+        list; lazy_adam then remembers (seqs_i and the list, labels): a live slot of the list is touched whenever the step ran."""
         rows, lams = self.encoder(features, True, self._gather_pos(features, True))
-        loss = self._score_ce(rows, labels.reshape(-1).contiguous(), candidates)
+        loss = self._score_ce(rows, labels.reshape(-1).contiguous(), candidates, shared)
         if self.lazy_adam and torch.is_grad_enabled():
-            self._lazy_pending.append((features["seqs_i"],) + self._lazy_lists)
+            lab, cand, sh = self._lazy_lists
+            ids = features["seqs_i"] if sh is None else torch.cat((features["seqs_i"].reshape(-1), sh.long()))
+            self._lazy_pending.append((ids, lab, cand))
         if self.l2_reg != 0.0:                                                                     # :158
             loss = loss + ops.L2Fn.apply(self.item_embs.lookup_table, self.l2_reg, self.lazy_adam)
             for p in (self.mark_embs.lookup_table, self.pcoding.pembs.lookup_table):

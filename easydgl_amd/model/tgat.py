@@ -121,11 +121,12 @@ class TGAT(Sequential):
         tab = self.item_embs.lookup_table
         return ops.ScoreLogitsFn.apply(rows, tab, self.output_bias, self.compute(tab))                            # :74-83
 
-    def train_loss(self, features, labels, *, candidates=None):
+    def train_loss(self, features, labels, *, candidates=None, shared=None):
         """Sequential.train (Base.py:119-131) with the fused scoring / cross-entropy (no [B*T, I] tensor).  `candidates` (int32
-        [B*T, N]) or FLAGS.train_negatives > 0: the softmax of every position over its label and its own list (Sequential._score_ce)."""
+        [B*T, N]) or FLAGS.train_negatives > 0: the softmax of every position over its label and its own list (Sequential._score_ce);
+        `shared` (int32 [S]) or FLAGS.shared_negatives > 0: over its label and the step's ONE list."""
         rows = self.encoder(features, True, None)
-        loss = self._score_ce(rows.reshape(-1, self.num_units), labels.reshape(-1).contiguous(), candidates)
+        loss = self._score_ce(rows.reshape(-1, self.num_units), labels.reshape(-1).contiguous(), candidates, shared)
         if self.l2_reg != 0.0:
             for n in self.l2_param_names():
                 loss = loss + ops.L2Fn.apply(self.get_parameter(n), self.l2_reg)

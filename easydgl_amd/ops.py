@@ -681,6 +681,91 @@ class SampledCEFn(torch.autograd.Function):
         return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None
 
 
+MAX_SHARED = 8192
+
+
+def _shared_ce_check(rows, table_c, shared, labels):
+    _ptr(rows)                                               # (GPU tensors only: refused before anything else)
+    R, C = rows.shape
+    if table_c.dtype != rows.dtype or table_c.dim() != 2 or table_c.shape[1] != C:
+        raise _lib.EdglError(f"shared_ce: rows {rows.dtype} [{R}, {C}] against a table {table_c.dtype} {tuple(table_c.shape)}")
+    if shared.dtype != torch.int32 or shared.dim() != 1 or not 1 <= shared.shape[0] <= MAX_SHARED:
+        raise _lib.EdglError(f"shared_ce: the shared list must be int32 [S], 1 <= S <= {MAX_SHARED}, one list for every row (got "
+                             f"{shared.dtype} {tuple(shared.shape)})")
+    if labels.dtype != torch.int64 or labels.shape != (R,):
+        raise _lib.EdglError(f"shared_ce: labels must be int64 [{R}] (got {labels.dtype} {tuple(labels.shape)})")
+
+
+def _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid):
+    R, C = rows.shape
+    I, S, dev = table_c.shape[0], shared.shape[0], rows.device
+    vals = torch.empty((R, S), device=dev, dtype=torch.float32)
+    label_val = torch.empty(R, device=dev, dtype=torch.float32)
+    lse = torch.empty(R, device=dev, dtype=torch.float32)
+    check(lib.edgl_shared_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(shared), _ptr(labels), _ptr(nvalid), R, C, I, S,
+                                 _ptr(vals), _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_shared_ce_fwd")
+    return vals, label_val, lse
+
+
+def shared_ce_fwd(rows, table_c, out_bias, shared, labels):
+    """(vals f32 [R, S], label_val f32 [R], lse f32 [R]) of edgl_shared_ce_fwd, in the caller's row order: vals[r, s] is the value of
+    (rows[r], shared[s]) (int32 [S], one list for every row); -inf at an id < 0, an id >= I and an accidental hit (shared[s] ==
+    labels[r]); label_val is the label's value; rows of label 0 are skipped (vals -inf, label_val = lse = 0)."""
+    _shared_ce_check(rows, table_c, shared, labels)
+    return _shared_ce_fwd(rows.contiguous(), table_c, out_bias, shared.contiguous(), labels.contiguous(), None)
+
+
+class SharedCEFn(torch.autograd.Function):
+    """Sampled-softmax cross-entropy on ONE negative list per call: SampledCEFn's loss with cand[r, :] = shared[:]
+    (int32 [S]; an id < 0 or >= I is an empty slot, an id equal to a row's label is dead for that row) — the scoring and both
+    gradient products run as dense products on MFMA (edgl_shared_ce_fwd / _bwd).  SampledCEFn's gradient contract: d_rows in the
+    compute dtype, a dense f32 d_table [I, C] (zero-filled, then added into) and d_bias [I - 1].  The weighted rows are compacted
+    first, as in ScoreCEFn: the list does not depend on the row, so that changes nothing but the work.
+    deterministic: no float atomics — repeated ids are summed in slot order, the label term over a k_segsum.hip plan.
+    d_table_out (f32 [I, C]): the backward ADDS the table gradient into it and returns None for the table master."""
+
+    @staticmethod
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, shared, deterministic=False, d_table_out=None):
+        ctx.deterministic = bool(deterministic)
+        ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SharedCEFn")
+        rows, labels, shared = rows.contiguous(), labels.reshape(-1).contiguous(), shared.contiguous()
+        _shared_ce_check(rows, table_c, shared, labels)
+        if lib.edgl_shared_ce_workspace(rows.shape[0], rows.shape[1], shared.shape[0], _code(rows)) < 0:     # (the shape rule, before the compaction)
+            check(-1, "edgl_shared_ce_workspace")
+        rows, labels, _perm, inv, nvalid = compact_rows(rows, labels)
+        vals, label_val, lse = _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid)
+        R = rows.shape[0]
+        loss = torch.empty(1, device=rows.device, dtype=torch.float32)
+        coef = torch.empty(R, device=rows.device, dtype=torch.float32)
+        check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
+              "edgl_ce_loss_fwd")
+        ctx.save_for_backward(rows, table_c, labels, shared, vals, label_val, lse, coef, inv, nvalid)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, table_c, labels, shared, vals, label_val, lse, coef, inv, nvalid = ctx.saved_tensors
+        R, C = rows.shape
+        I, S = table_c.shape[0], shared.shape[0]
+        dev, code = rows.device, _code(rows)
+        g = g.reshape(1).to(torch.float32).contiguous()
+        d_rows_c = torch.empty_like(rows)
+        d_rows = torch.empty_like(rows)
+        in_place = ctx.d_table_out is not None
+        d_table = ctx.d_table_out if in_place else torch.zeros((I, C), device=dev, dtype=torch.float32)
+        d_bias = torch.zeros(I - 1, device=dev, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_shared_ce_workspace(R, C, S, code)), device=dev, dtype=torch.float32)
+        keys = plan = None
+        if ctx.deterministic:
+            keys = torch.empty(2 * R, device=dev, dtype=torch.int64)
+            plan = segsum_plan_buffer(2 * R, I, dev)
+        check(lib.edgl_shared_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(shared), _ptr(labels), _ptr(vals), _ptr(label_val), _ptr(lse),
+                                     _ptr(coef), _ptr(g), _ptr(nvalid), R, C, I, S, _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
+                                     _ptr(ws), _ptr(keys), _ptr(plan), code, _stream()), "edgl_shared_ce_bwd")
+        check(lib.edgl_scatter_rows(_ptr(d_rows_c), _ptr(inv), R, C, _ptr(d_rows), code, _stream()), "edgl_scatter_rows")
+        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None
+
+
 class ScoreLogitsFn(torch.autograd.Function):
     """Materialised logits [R, I] (EasyDGL.py:149-151) for API parity with the reference's __call__."""
 

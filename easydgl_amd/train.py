@@ -82,14 +82,25 @@ def args(argv=None):
                    help="N > 0: sampled-softmax training (DESIGN 4.13) — the cross-entropy of every scored position over its label and N "
                         "negatives drawn uniformly from the catalogue (fresh lists every step) instead of the whole catalogue; every "
                         "batch goes through model.train_step (no static engine, no --graph).  0: full softmax")
+    p.add_argument("--shared_negatives", type=int, default=0,
+                   help="S > 0: sampled-softmax training on ONE list of S negatives per step, shared by every scored position (DESIGN "
+                        "4.15; tf.nn.sampled_softmax_loss's default form) — scoring and gradients run as dense products on the matrix "
+                        "pipe; a different estimator from --train_negatives, not both; no static engine, no --graph.  0: off")
     p.add_argument("--train_neg_seed", type=int, default=0, help="seed of the sampled training negatives")
     p.add_argument("--lazy_adam", action="store_true",
-                   help="EasyDGL with --train_negatives: lazy row-wise Adam for the item table (DESIGN 4.14, TensorFlow's "
+                   help="EasyDGL with --train_negatives or --shared_negatives: lazy row-wise Adam for the item table (DESIGN 4.14, TensorFlow's "
                         "LazyAdamOptimizer) — the table gradient lands in place and the optimizer updates only the rows the step used "
                         "(input ids, labels, negatives); every other parameter keeps the dense Adam")
     a = p.parse_args(argv)
-    if a.lazy_adam and a.train_negatives <= 0:
-        p.error("--lazy_adam needs --train_negatives N > 0: the full softmax has a dense table gradient, there are no untouched rows")
+    if a.train_negatives > 0 and a.shared_negatives > 0:
+        p.error("--shared_negatives with --train_negatives: one estimator per run (per-row lists or one shared list)")
+    if a.shared_negatives < 0 or a.shared_negatives > 8192:
+        p.error("--shared_negatives: the length of the step's shared negative list (0: off, at most 8192)")
+    if a.shared_negatives > 0 and a.graph:
+        p.error("--graph with --shared_negatives: the sampled-softmax step runs on the autograd path (model.train_step), whose "
+                "negative lists are keyed by a host-side step count; it is not captured into a graph")
+    if a.lazy_adam and a.train_negatives <= 0 and a.shared_negatives <= 0:
+        p.error("--lazy_adam needs --train_negatives N > 0 or --shared_negatives S > 0: the full softmax has a dense table gradient, there are no untouched rows")
     if a.train_negatives < 0:
         p.error("--train_negatives: the number of sampled negatives per position (0: full softmax)")
     if a.train_negatives > 0 and a.graph:
@@ -257,8 +268,11 @@ def run(FLAGS) -> Dict[str, float]:
     train_negatives = int(getattr(FLAGS, "train_negatives", 0) or 0)
     if train_negatives > 0 and getattr(FLAGS, "graph", False):
         raise ValueError("--graph with --train_negatives: the sampled-softmax step runs on the autograd path (model.train_step)")
-    # sampled-softmax training (DESIGN 4.13): no static engine, every batch through model.train_step
-    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0) else None
+    shared_negatives = int(getattr(FLAGS, "shared_negatives", 0) or 0)
+    if shared_negatives > 0 and getattr(FLAGS, "graph", False):
+        raise ValueError("--graph with --shared_negatives: the sampled-softmax step runs on the autograd path (model.train_step)")
+    # sampled-softmax training (DESIGN 4.13, 4.15): no static engine, every batch through model.train_step
+    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0 and shared_negatives <= 0) else None
     loader = vl_loader = te_loader = None
     if device_data:
         need = sum(D.DeviceSplit.nbytes(ii, tt) + 4 * len(ii) for ii, tt in ((tr_i, tr_t), (vl_i, vl_t), (te_i, te_t)))

@@ -583,6 +583,31 @@ int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias,
 int edgl_cand_ce_table_det(const void* rows, const int32_t* cand, const int64_t* labels, const float* dv, int R, int C, int I, int N,
                            float* d_table, float* d_bias, int64_t* keys, void* plan, int dtype, void* stream);
 
+/* ---- K5d: sampled-softmax training on ONE negative list per step (csrc/k_shared_ce.hip) ---------------------------
+ * The definition of edgl_cand_ce_* with cand[r, :] = shared[:] (int32 [S]) for every row: the label is kept apart (label_val) and
+ * vals f32 [R, S] holds slot s = shared[s]; a slot reads -inf for row r when shared[s] < 0, shared[s] >= I or shared[s] == labels[r].
+ * Rows of weight 0 (label outside [1, I), or at / past nvalid[0]; nvalid: device int32 of a compacted batch, or NULL = R): vals
+ * -inf, label_val = row_lse = 0, d_rows 0.
+ *   edgl_shared_ce_fwd   the [R, C] x [C, S] product on MFMA with the listed table rows gathered into the LDS image; an online
+ *                        (max, sum) per row in an order that is a function of (dtype, C, S) alone: no atomics, a row's outputs do not
+ *                        depend on R or on the other rows.  Loss and coef come from edgl_ce_loss_fwd(row_lse, label_val, labels, ..).
+ *   edgl_shared_ce_bwd   d_rows [R, C] (`dtype`) = dv W_S + dv_label table[y] without atomics; the slab dv^T rows [S, C] is summed
+ *                        over fixed row splits in order and ADDED into d_table f32 [I, C] / d_bias f32 [I - 1] (row 0 is never
+ *                        touched), as is the label term.  keys / plan NULL: both with f32 atomics, (R + S) C 4 bytes.  keys (int64
+ *                        [2 R]) and plan (edgl_segsum_plan_bytes(2 R, I) bytes, 16-byte aligned) given: no float atomics — the first
+ *                        slot of a repeated id sums its repeats in slot order, the label term is an ordered sum over the plan.
+ *                        workspace: edgl_shared_ce_workspace(R, C, S, dtype) floats, 16-byte aligned.
+ * rows / table in `dtype`, 16-byte aligned; 16 <= C <= 512 with C % 8 == 0 (bf16) or C % 4 == 0 (f32); R >= 1; 1 <= S <= 8192 with
+ * R (S + 8) < 2^31; I > 1; anything else is EDGL_ERR_SHAPE with the bound in the text, checked before any pointer is read. */
+long edgl_shared_ce_workspace(int R, int C, int S, int dtype);
+int edgl_shared_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* shared, const int64_t* labels,
+                       const int32_t* nvalid, int R, int C, int I, int S, float* vals, float* label_val, float* row_lse, int dtype,
+                       void* stream);
+int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,
+                       const float* label_val, const float* row_lse, const float* coef, const float* gscale, const int32_t* nvalid,
+                       int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias, float* workspace, int64_t* keys,
+                       void* plan, int dtype, void* stream);
+
 /* ---- K5, "flash" form (used by the static training engine): the forward scoring pass already accumulates the row
  * gradients, so the [R, I] logits are computed twice per step instead of three times.
  * edgl_score_flash_fwd: one pass over the item rows [i0, i1) gives row_lse (as edgl_score_lse_fwd), label_logit, and keeps

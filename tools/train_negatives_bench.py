@@ -1,7 +1,7 @@
 """Sampled-softmax training against the full-catalogue softmax, in ONE process:
 
-    python tools/train_negatives_bench.py [--rounds 5] [--steps 20] [--models EasyDGL,TiSASREC] [--sections full,lazy]
-                                          [--out profiles/train_negatives.txt]
+    python tools/train_negatives_bench.py [--rounds 5] [--steps 20] [--models EasyDGL,TiSASREC] [--sections full,lazy,shared]
+                                          [--out profiles/train_negatives.txt] [--parent TREE]
 
 Per shape (sequences x positions x channels x items; bf16) and model: `model.train_step` with train_negatives N in {0, 100, 1000} —
 N = 0 is the full softmax (ops.ScoreCEFn), the path every step took before sampled training existed — and the loss op alone,
@@ -14,6 +14,13 @@ FLAGS.lazy_adam, with the distinct rows the step touches and the byte model besi
 w, m, v, zeros and the bf16 shadow written) against the dense path's 14.5 I C 4 (two zero fills, their sum, the copy into the arena
 and the dense Adam; the l2 term's dense gradient, which the lazy mode also drops, is not counted).  `--sections lazy` keeps the
 part of --out in front of the section's heading and replaces the rest.
+Section `shared`: `train_step` with ONE list of S in {128, 1024, 8192} negatives per step (FLAGS.shared_negatives)
+beside two baselines timed in the same session — the per-row step at N = 100 and the full softmax (N = 0), both from the tree
+`--parent TREE` names (a checkout of the parent commit with its library built; a fresh child process of this tool with `--tree
+TREE --sections baseline`), or from this tree when no parent is given — then, EasyDGL, shared + lazy_adam against the parent's lazy
+step at N = 100, and the loss op alone (ops.SharedCEFn forward + backward, atomic and deterministic) beside its byte model: (R_w + S) C 4
+bytes of f32 atomics plus the [R, S] traffic (f32 values written and read, dv in bf16 written and read twice).  `--sections shared`
+replaces the part of --out from the section's heading on and keeps the rest.
 Needs a GPU: there is no fallback."""
 import argparse
 import os
@@ -21,7 +28,9 @@ import statistics
 import sys
 from types import SimpleNamespace
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+# --tree TREE: the package of another checkout (the parent commit's, with its own library) instead of this file's
+_TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.abspath(_TREE))
 import torch  # noqa: E402
 
 import easydgl_amd  # noqa: E402
@@ -33,6 +42,9 @@ SHAPES = [(512, 100, 128, 20000), (512, 200, 256, 1000000)]
 NEGATIVES = (0, 100, 1000)
 LAZY_NEGATIVES = (10, 100)
 LAZY_HEADING = "lazy row-wise Adam for the item table (DESIGN 4.14)"
+SHARED_SIZES = (128, 1024, 8192)
+SHARED_HEADING = "one negative list per step, shared by every row (DESIGN 4.15)"
+HBM_RATE = 5.0e12         # bytes per second of streamed reads / writes (a round figure for the [R, S] traffic's floor)
 ATOMIC_RATE = 1.3e12      # bytes of f32 atomic adds per second, chip-wide
 
 
@@ -57,8 +69,8 @@ def fmt(ts):
     return f"{statistics.median(ts):9.4f} ({min(ts):.4f} .. {max(ts):.4f})"
 
 
-def build(name, B, L, C, num_items, negatives=0, lazy=False):
-    F = SimpleNamespace(train_negatives=negatives, lazy_adam=lazy,
+def build(name, B, L, C, num_items, negatives=0, lazy=False, shared=0):
+    F = SimpleNamespace(train_negatives=negatives, lazy_adam=lazy, shared_negatives=shared,
                         model=name, num_items=num_items, num_units=C, num_heads=8, num_blocks=1, seqslen=L, masklen=L // 5,
                         timelen=256, time_scale=86400.0, learning_rate=5e-4, l2_reg=1e-4, ct_reg=1e-7, hidden_dropout_rate=0.1,
                         attention_probs_dropout_rate=0.1, compute_dtype="bf16", num_train_steps=None, num_warmup_steps=None, seed=9876)
@@ -130,8 +142,98 @@ def lazy_section(args, lines):
         lines.append("")
 
 
+def baseline_section(args):
+    """The per-row step at N = 100, the full softmax and (EasyDGL) the lazy per-row step of THIS process's tree, one `BASE` line
+    each on stdout: what the `shared` section of another tree's run reads."""
+    for name in args.models.split(","):
+        for B, L, C, num_items in SHAPES:
+            for N, lazy in ((0, False), (100, False)) + (((100, True),) if name == "EasyDGL" else ()):
+                model, feats, labels = build(name, B, L, C, num_items, N, lazy)
+                ts = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                print("BASE", name, B, L, C, num_items, N, int(lazy), *(f"{t:.6f}" for t in ts), flush=True)
+                model = feats = labels = None
+                torch.cuda.empty_cache()
+
+
+def parent_baselines(args):
+    """{(model, B, L, C, items, N, lazy): [ms per round]} of the tree args.parent names, measured by a fresh child process."""
+    import subprocess
+    cmd = [sys.executable, os.path.abspath(__file__), "--tree", args.parent, "--sections", "baseline", "--rounds", str(args.rounds),
+           "--steps", str(args.steps), "--models", args.models]
+    out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout
+    res = {}
+    for ln in out.split("\n"):
+        w = ln.split()
+        if w and w[0] == "BASE":
+            res[(w[1],) + tuple(int(x) for x in w[2:8])] = [float(x) for x in w[8:]]
+    return res
+
+
+def shared_op_call(model, rows, labels, shared, det):
+    tab = model.item_embs.lookup_table
+    r = rows.detach().requires_grad_(True)
+    loss = ops.SharedCEFn.apply(r, tab, model.output_bias, model.compute(tab), labels, shared, det)
+    torch.autograd.grad(loss, (r, tab, model.output_bias))
+
+
+def shared_section(args, lines):
+    src = "a checkout of the parent commit built from its own sources" if args.parent else "this tree with the flag unset (no --parent given)"
+    lines += [f"{SHARED_HEADING}: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} calls; bf16, dropout 0.1 / "
+              f"0.1; baselines (per-row N = 100, full softmax N = 0) from {src}, timed in the same session", ""]
+    if args.parent:
+        base = parent_baselines(args)
+    for name in args.models.split(","):
+        for B, L, C, num_items in SHAPES:
+            if not args.parent:
+                base = {}
+                for N, lazy in ((0, False), (100, False)) + (((100, True),) if name == "EasyDGL" else ()):
+                    model, feats, labels = build(name, B, L, C, num_items, N, lazy)
+                    base[(name, B, L, C, num_items, N, int(lazy))] = rounds_of(lambda: model.train_step(feats, labels), args.rounds,
+                                                                               args.steps)
+                    model = feats = labels = None
+                    torch.cuda.empty_cache()
+            b0, b100 = base[(name, B, L, C, num_items, 0, 0)], base[(name, B, L, C, num_items, 100, 0)]
+            model, feats, labels = build(name, B, L, C, num_items, 0, False, SHARED_SIZES[0])
+            lab = labels.reshape(-1).contiguous()
+            rows = scored_rows(name, model, feats)
+            R, Rw, I = rows.shape[0], int((lab != 0).sum()), model.item_embs.lookup_table.shape[0]
+            lines.append(f"{name}  {B} x {L} x {C}, {I} table rows: {R} scored rows, {Rw} weighted")
+            lines.append(f"  parent   N = 0   train_step {fmt(b0)}      N = 100   train_step {fmt(b100)}   spread of N = 100 "
+                         f"{max(b100) - min(b100):.4f}")
+            m100 = statistics.median(b100)
+            for S in SHARED_SIZES:
+                model.shared_negatives = S
+                step = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                sh = model.draw_shared_negatives(lab.device)
+                op = rounds_of(lambda: shared_op_call(model, rows, lab, sh, False), args.rounds, args.steps)
+                det = rounds_of(lambda: shared_op_call(model, rows, lab, sh, True), args.rounds, args.steps)
+                med = statistics.median(step)
+                ab, tb = (Rw + S) * C * 4, Rw * S * (4 + 4 + 2 + 2 + 2)
+                lines.append(f"  S = {S:5d}  train_step {fmt(step)}  x{med / m100:6.3f} of N = 100 (saves {m100 - med:+.4f} ms)  x"
+                             f"{med / statistics.median(b0):6.3f} of N = 0   loss op fwd + bwd {fmt(op)}   deterministic {fmt(det)}   "
+                             f"atomic bytes {ab / 1e6:7.1f} MB = {ab / ATOMIC_RATE * 1e3:6.3f} ms, [R, S] traffic {tb / 1e6:8.1f} MB = "
+                             f"{tb / HBM_RATE * 1e3:6.3f} ms at 5 TB/s")
+                print(lines[-1], flush=True)
+            model = feats = labels = rows = None
+            torch.cuda.empty_cache()
+            if name == "EasyDGL":
+                bl = base[(name, B, L, C, num_items, 100, 1)]
+                lines.append(f"  parent   N = 100 + lazy_adam   train_step {fmt(bl)}")
+                for S in SHARED_SIZES:
+                    model, feats, labels = build(name, B, L, C, num_items, 0, True, S)
+                    step = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                    lines.append(f"  S = {S:5d} + lazy_adam   train_step {fmt(step)}  x{statistics.median(step) / statistics.median(bl):6.3f} "
+                                 f"of the parent's lazy step")
+                    print(lines[-1], flush=True)
+                    model = feats = labels = None
+                    torch.cuda.empty_cache()
+            lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", default=None, help="run against the package of this checkout (read before the imports)")
+    ap.add_argument("--parent", default=None, help="section shared: a checkout of the parent commit, library built, for the baselines")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--models", default="EasyDGL,TiSASREC")
@@ -141,6 +243,21 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("train_negatives_bench.py: needs a GPU")
     sections = args.sections.split(",")
+    if sections == ["baseline"]:
+        return baseline_section(args)
+    if sections == ["shared"]:      # keep what stands in front of the shared section
+        lines = []
+        if os.path.exists(args.out):
+            old = open(args.out).read().split("\n")
+            lines = old[:next((i for i, ln in enumerate(old) if ln.startswith(SHARED_HEADING)), len(old))]
+            while lines and not lines[-1]:
+                lines.pop()
+            lines.append("")
+        shared_section(args, lines)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines))
+        print("wrote", args.out)
+        return
     lines = []
     if "full" not in sections and os.path.exists(args.out):      # keep what stands in front of the lazy section
         old = open(args.out).read().split("\n")
@@ -153,6 +270,8 @@ def main():
         full_section(args, lines)
     if "lazy" in sections:
         lazy_section(args, lines)
+    if "shared" in sections:
+        shared_section(args, lines)
     os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines))
