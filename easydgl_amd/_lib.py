@@ -132,11 +132,14 @@ SIGNATURES = {
     "edgl_score_candidates_chunk": (I, [I, I, I, I]),
     "edgl_score_candidates": (I, [P, P, P, P, P, I, P, I, I, I, I, P, P, P, I, P]),
     "edgl_sample_negatives": (I, [P, I, P, I, I, I, I, I, U64, U64, I, P, P]),
+    "edgl_sample_negatives_alias": (I, [P, I, P, I, I, I, I, I, P, U64, U64, I, P, P]),
     "edgl_cand_ce_fwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
+    "edgl_cand_ce_fwd_q": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "edgl_cand_ce_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, I, P]),
     "edgl_cand_ce_table_det": (I, [P, P, P, P, I, I, I, I, P, P, P, P, I, P]),
     "edgl_shared_ce_workspace": (L, [I, I, I, I]),
     "edgl_shared_ce_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
+    "edgl_shared_ce_fwd_q": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "edgl_shared_ce_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
     "edgl_rank_metrics_from_rank_rows": (I, [P, I, P, I, P, P]),
     "edgl_topk_merge": (I, [P, P, I, I, I, P, P, P]),

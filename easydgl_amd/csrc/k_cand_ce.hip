@@ -9,7 +9,10 @@
 //   dv(r, s)       = g coef[r] (exp(v_s - lse) - [s == 0])
 //   d_rows[r]      = sum_s dv table_c[c_s]     (item 0 adds nothing)        d_table[c_s] += dv rows[r] (row 0 stays zero)
 //   d_bias[c_s - 1] += dv  (c_s >= 1)
-// Negatives are uniform over [1, hi): the log-Q correction of sampled softmax is one constant for every slot and cancels.
+// Uniform negatives over [1, hi): the log-Q correction of sampled softmax is one constant for every slot and cancels.  A weighted
+// sampler hands logq [I] to edgl_cand_ce_fwd_q: the label and every live slot then read v - logq[c] — one f32
+// subtraction on the finished value, so logq = 0 or NULL gives the bits above; the backward forms dv from the saved vals and lse
+// and is the same code either way.
 //
 //   cand_ce_fwd_kernel   one workgroup (4 waves) per row; the structure of score_cand_kernel: query row in registers over a lane group,
 //                        UNROLL gathered table rows in flight, the next step's ids fetched under this step's arithmetic.  Writes
@@ -40,6 +43,7 @@ constexpr int MAX_N = 8192;
 
 struct P {
     const void* rows; const void* table; const float* bias; const int32_t* cand; const int64_t* labels;
+    const float* logq;                                               // forward only: [I] or NULL
     int R, C, I, N;
     float* vals; float* label_val; float* lse;                       // forward: outputs; backward: vals / lse are inputs
     const float* coef; const float* gscale;
@@ -53,7 +57,8 @@ __device__ __forceinline__ void lse_join(float& m, float& s, float m2, float s2)
     m = M;
 }
 
-template <typename T, int G, int PPL>
+// Q: with the log-Q term (p.logq != NULL); Q = false compiles to the kernel without it
+template <typename T, int G, int PPL, bool Q>
 __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
     constexpr int RPW = 64 / G;               // candidate rows per wave-instruction
     constexpr int STEP = 4 * UNROLL * RPW;    // slots of one step of the workgroup
@@ -81,6 +86,7 @@ __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
         uint4 w[PPL];
         load_pieces<T, G, PPL>(table, y, p.C, gl, w);
         vy = cand_value<T, G, PPL>(xq, w, y, p.bias[y - 1], p.C, gl);
+        if constexpr (Q) vy -= p.logq[y];     // the log-Q correction: one f32 subtraction on the finished value
     }
     const int32_t* crow = p.cand + (long)r * N;
     auto slot_of = [&](int base, int u) { return base + u * (4 * RPW) + wave * RPW + grp; };
@@ -93,7 +99,7 @@ __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
     float m = -INFINITY, s = 0.0f;
     for (int base = 0; base < N; base += STEP) {              // (block-uniform)
         uint4 w[UNROLL][PPL];
-        float b[UNROLL];
+        float b[UNROLL], q[Q ? UNROLL : 1];
         int c[UNROLL], ca[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
@@ -101,6 +107,7 @@ __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
             ca[u] = (c[u] >= 0 && c[u] < p.I) ? c[u] : 0;     // (addresses stay inside the table whatever the id)
             load_pieces<T, G, PPL>(table, ca[u], p.C, gl, w[u]);
             b[u] = p.bias[max(ca[u], 1) - 1];
+            if constexpr (Q) q[u] = p.logq[ca[u]];            // (logq[0] = 0: item 0 keeps its -1000)
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {                    // the next step's ids, under this step's arithmetic
@@ -109,7 +116,8 @@ __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
         }
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-            const float vv = cand_value<T, G, PPL>(xq, w[u], ca[u], ca[u] == 0 ? -1000.0f : b[u], p.C, gl);
+            float vv = cand_value<T, G, PPL>(xq, w[u], ca[u], ca[u] == 0 ? -1000.0f : b[u], p.C, gl);
+            if constexpr (Q) vv -= q[u];
             const bool live = c[u] >= 0 && c[u] < p.I && c[u] != y;
             const float v = live ? vv : -INFINITY;
             const int n = slot_of(base, u);
@@ -284,7 +292,8 @@ __global__ __launch_bounds__(256) void cand_ce_keys_kernel(const int32_t* cand, 
 template <typename T, int G, int PPL>
 int launch(const P& p, bool bwd, hipStream_t st) {
     if (bwd) hipLaunchKernelGGL((cand_ce_bwd_kernel<T, G, PPL>), dim3((unsigned)p.R), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((cand_ce_fwd_kernel<T, G, PPL>), dim3((unsigned)p.R), dim3(256), 0, st, p);
+    else if (p.logq) hipLaunchKernelGGL((cand_ce_fwd_kernel<T, G, PPL, true>), dim3((unsigned)p.R), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((cand_ce_fwd_kernel<T, G, PPL, false>), dim3((unsigned)p.R), dim3(256), 0, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
@@ -318,16 +327,24 @@ int check_shape(const char* who, const void* rows, const void* table, int R, int
 
 }  // namespace cce
 
-extern "C" int edgl_cand_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
-                                int R, int C, int I, int N, float* vals, float* label_val, float* row_lse, int dtype, void* stream) {
+// logq (f32 [I], or NULL): every live slot and the label read v - logq[c]; NULL subtracts nothing
+extern "C" int edgl_cand_ce_fwd_q(const void* rows, const void* table, const float* out_bias, const float* logq, const int32_t* cand,
+                                  const int64_t* labels, int R, int C, int I, int N, float* vals, float* label_val, float* row_lse,
+                                  int dtype, void* stream) {
     const int rc = cce::check_shape("edgl_cand_ce_fwd", rows, table, R, C, I, N, dtype);      // (first: an empty list has no address)
     if (rc) return rc;
     EDGL_REQUIRE(rows && table && out_bias && cand && labels && vals && label_val && row_lse, EDGL_ERR_NULL, "edgl_cand_ce_fwd: null pointer");
     cce::P p{};
     p.rows = rows; p.table = table; p.bias = out_bias; p.cand = cand; p.labels = labels; p.R = R; p.C = C; p.I = I; p.N = N;
+    p.logq = logq;
     p.vals = vals; p.label_val = label_val; p.lse = row_lse;
     hipStream_t st = (hipStream_t)stream;
     return dtype == EDGL_BF16 ? cce::dispatch<bf16>(p, false, st) : cce::dispatch<float>(p, false, st);
+}
+
+extern "C" int edgl_cand_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
+                                int R, int C, int I, int N, float* vals, float* label_val, float* row_lse, int dtype, void* stream) {
+    return edgl_cand_ce_fwd_q(rows, table, out_bias, nullptr, cand, labels, R, C, I, N, vals, label_val, row_lse, dtype, stream);
 }
 
 extern "C" int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,

@@ -20,6 +20,7 @@
 //                        no float atomics, no workspace, no finish kernel; scratch 0.
 //   sample_neg_kernel    cand[r, n] = the first of 32 counter-based draws from [lo, hi) that is neither one of the row's seen ids nor
 //                        its label (the draw is specified in DESIGN 4.12 and replicated by tests/_cand_ref.py), else -1.
+//   sample_neg_alias_kernel   the same draw with the id taken from an alias table: popularity-weighted negatives.
 //   rank_metrics_rows_kernel   edgl_rank_metrics_from_rank with the rows added one by one in row order: sampled-negative steps give
 //                        the same metric sums whatever the batch size.
 #include <algorithm>
@@ -176,6 +177,42 @@ __global__ __launch_bounds__(256) void sample_neg_kernel(SP p) {
     }
 }
 
+// The weighted draw: sample_neg_kernel with one change — the map from the attempt's word h to an id goes through an
+// alias table of span = hi - lo buckets (ops.build_neg_dist: Vose's method, uint32 thresholds).  bucket j = (h span) >> 32, a second
+// word h2 = mix32(h + ALIAS_K), id = lo + (h2 < thr[j] || alias[j] == j ? j : alias[j]).  tab[j] = (thr[j], alias[j]): ONE 8-byte
+// random read per attempt.  Keys, row / slot / attempt hashing, row0, 32 attempts, the LDS image of the seen ids and -1 on failure
+// are sample_neg_kernel's.  The bucket index is < span by construction; an alias outside [0, span) (a caller's broken table) falls
+// back to the bucket itself, so no id outside [lo, hi) is ever written.
+constexpr uint32_t ALIAS_K = 0x68E31DA4u;
+
+__global__ __launch_bounds__(256) void sample_neg_alias_kernel(SP p, const uint2* __restrict__ tab) {
+    __shared__ int sseen[MAX_T];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int T_ = p.seen ? p.T : 0;
+    for (int t = tid; t < T_; t += 256) sseen[t] = seen_id32(p.seen[(long)r * p.T + t]);
+    __syncthreads();
+    const int64_t y64 = p.labels ? p.labels[r] : -1;
+    const int y = seen_id32(y64);
+    const uint32_t hrow = edgl_mix32(p.key ^ edgl_mix32(p.row0 + (uint32_t)r));
+    const uint32_t span = (uint32_t)(p.hi - p.lo);
+    for (int n = tid; n < p.n; n += 256) {
+        const uint32_t hs = edgl_mix32(hrow + (uint32_t)n * 0x9E3779B1u);
+        int out = -1;
+        for (uint32_t att = 0; att < 32u && out < 0; ++att) {
+            const uint32_t h = edgl_mix32(hs ^ (att * 0x85EBCA6Bu));
+            const uint32_t j = (uint32_t)(((uint64_t)h * (uint64_t)span) >> 32);
+            const uint2 e = tab[j];
+            const uint32_t h2 = edgl_mix32(h + ALIAS_K);
+            const uint32_t a = e.y < span ? e.y : j;
+            const int id = p.lo + (int)((h2 < e.x || a == j) ? j : a);
+            bool hit = id == y;
+            for (int t = 0; t < T_; ++t) hit |= sseen[t] == id;       // (no early exit: the LDS reads pipeline)
+            if (!hit) out = id;
+        }
+        p.cand[(long)r * p.n + n] = out;
+    }
+}
+
 // sums[0 .. nk) += H@k, sums[nk .. 2 nk) += N@k, sums[2 nk] += MRR, ONE lane per sum, the rows in ascending order: ((s + g_0) + g_1) + ..
 // — the same f32 value however a split is cut into batches (k_eval_rank.hip's form adds a batch as a tree).  The gains of a block of
 // rows are formed by all threads into LDS; only the additions are serial.
@@ -288,6 +325,34 @@ extern "C" int edgl_sample_negatives(const int64_t* seen, int T, const int64_t* 
     p.seen = T > 0 ? seen : nullptr; p.labels = labels; p.cand = cand; p.T = T; p.R = R; p.n = n; p.lo = lo; p.hi = hi;
     p.key = k; p.row0 = (uint32_t)row0;
     hipLaunchKernelGGL(evc::sample_neg_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, p);
+    EDGL_LAUNCH_CHECK();
+    return EDGL_OK;
+}
+
+// edgl_sample_negatives with the weighted draw of DESIGN 4.16.  thr_alias: uint32 [hi - lo, 2], entry j = (acceptance threshold,
+// alias bucket) of ops.build_neg_dist.  The weighted form of 2 (T + 1) <= hi - lo — the T + 1 heaviest ids hold at most half of the
+// weight — is a property of the weights and is checked where the table is built.
+extern "C" int edgl_sample_negatives_alias(const int64_t* seen, int T, const int64_t* labels, int R, int n, int lo, int hi, int I,
+                                           const uint32_t* thr_alias, uint64_t seed, uint64_t step, int row0, int32_t* cand,
+                                           void* stream) {
+    EDGL_REQUIRE(cand && thr_alias, EDGL_ERR_NULL, "edgl_sample_negatives_alias: null pointer");
+    EDGL_REQUIRE(seen || T == 0, EDGL_ERR_NULL, "edgl_sample_negatives_alias: T > 0 without seen ids");
+    EDGL_REQUIRE(R >= 1 && n >= 1 && row0 >= 0 && (long)R * n < (1L << 31), EDGL_ERR_SHAPE,
+                 "edgl_sample_negatives_alias: R=%d n=%d row0=%d (R >= 1, n >= 1, row0 >= 0, R n < 2^31)", R, n, row0);
+    EDGL_REQUIRE(T >= 0 && T <= evc::MAX_T, EDGL_ERR_SHAPE, "edgl_sample_negatives_alias: T=%d (0 <= T <= %d)", T, evc::MAX_T);
+    EDGL_REQUIRE(1 <= lo && lo < hi && hi <= I, EDGL_ERR_SHAPE, "edgl_sample_negatives_alias: range [%d, %d) of %d items (1 <= lo < hi <= I)",
+                 lo, hi, I);
+    EDGL_REQUIRE(((uintptr_t)thr_alias & 7) == 0, EDGL_ERR_SHAPE, "edgl_sample_negatives_alias: the table must be 8-byte aligned");
+    // key(seed, step) of DESIGN 4.12, on the host: mix32 as edgl_mix32
+    auto mix = [](uint32_t h) { h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16; return h; };
+    uint32_t k = mix((uint32_t)seed ^ 0xC4ED1DA7u);
+    k = mix(k + (uint32_t)(seed >> 32));
+    k = mix(k ^ (uint32_t)step);
+    evc::SP p{};
+    p.seen = T > 0 ? seen : nullptr; p.labels = labels; p.cand = cand; p.T = T; p.R = R; p.n = n; p.lo = lo; p.hi = hi;
+    p.key = k; p.row0 = (uint32_t)row0;
+    hipLaunchKernelGGL(evc::sample_neg_alias_kernel, dim3((unsigned)R), dim3(256), 0, (hipStream_t)stream, p,
+                       reinterpret_cast<const uint2*>(thr_alias));
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }

@@ -8,7 +8,9 @@
 //   dv(r, s)       = g coef[r] exp(v - lse);   dv_label(r) = g coef[r] (exp(label_val - lse) - 1)
 //   d_rows[r]      = sum_s dv table_c[shared[s]] + dv_label table_c[y]
 //   d_table[c]    += sum over the slots / labels that name c of dv rows[r]  (row 0 stays zero);   d_bias[c - 1] += sum dv
-// Negatives are uniform over [1, hi): the log-Q term of sampled softmax is one constant for every slot and cancels.
+// Uniform negatives over [1, hi): the log-Q term of sampled softmax is one constant for every slot and cancels.  A weighted sampler
+//  hands logq [I] to edgl_shared_ce_fwd_q: the label and every live slot read v - logq[c], one f32 subtraction on the
+// finished value (logq = 0 or NULL: the bits above); the backward forms dv from the saved vals / label_val / lse and is unchanged.
 //
 //   shared_label_kernel   label_val[r]: one gathered dot product per row, cand_gather.h's rule (the bits of k_cand_ce.hip's slot 0).
 //   shared_ce_fwd_kernel  a workgroup owns 128 rows and walks the list in tiles of 128 slots.  Per tile the contraction over C runs
@@ -44,6 +46,7 @@ constexpr int TS = 128;                       // slots of a tile
 
 struct P {
     const void* rows; const void* table; const float* bias; const int32_t* shared; const int64_t* labels; const int32_t* nvalid;
+    const float* logq;                                               // forward only: [I] or NULL
     int R, C, I, S, Sp;
     float* vals; float* label_val; float* lse;                       // forward: outputs; backward: inputs
     const float* coef; const float* gscale;
@@ -74,17 +77,21 @@ __global__ __launch_bounds__(256) void shared_label_kernel(P p) {
 #pragma unroll
     for (int pp = 0; pp < PPL; ++pp) unpack<T>(w[pp], gl + pp * 64 < p.C / (int)(16 / sizeof(T)), xq.x[pp]);
     load_pieces<T, G, PPL>(reinterpret_cast<const T*>(p.table), y, p.C, gl, w);
-    const float v = cand_value<T, G, PPL>(xq, w, y, p.bias[y - 1], p.C, gl);
+    float v = cand_value<T, G, PPL>(xq, w, y, p.bias[y - 1], p.C, gl);
+    if (p.logq) v -= p.logq[y];                                       // (grid-uniform) the label's log-Q term
     if (r < p.R && gl == 0) p.label_val[r] = live ? v : 0.0f;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void shared_ce_fwd_kernel(P p) {
+// Q: the per-slot log-Q term rides with the staged bias (slq) and is subtracted from the finished value; Q = false is the
+// kernel without it (the two __global__ wrappers follow the body)
+template <typename T, bool Q>
+__device__ __forceinline__ void shared_ce_fwd_body(const P& p) {
     constexpr int VEC = ElemTraits<T>::VEC, KB = ElemTraits<T>::KB, BK = 2 * KB, LDK = BK + VEC, KV = BK / VEC;
     __shared__ __attribute__((aligned(16))) T As[128 * LDK];
     __shared__ __attribute__((aligned(16))) T Bs[TS * LDK];
     __shared__ int sid[TS];
     __shared__ float sbias[TS];
+    __shared__ float slq[Q ? TS : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lm = lane & 15, lq = lane >> 4;
     const int row0 = blockIdx.x * 128, R = p.R, S = p.S, C = p.C;
     const int nlive = nlive_of(p);
@@ -132,6 +139,7 @@ __global__ __launch_bounds__(256) void shared_ce_fwd_kernel(P p) {
             const bool ok = c >= 0 && c < p.I;
             sid[tid] = ok ? c : -1;
             sbias[tid] = ok ? (c == 0 ? -1000.0f : p.bias[c - 1]) : -INFINITY;
+            if constexpr (Q) slq[tid] = ok ? p.logq[c] : 0.0f;
         }
         __syncthreads();
         f32x4 acc[8][2];
@@ -173,7 +181,8 @@ __global__ __launch_bounds__(256) void shared_ce_fwd_kernel(P p) {
                 for (int r = 0; r < 4; ++r) {
                     const int c = sid[n + r];
                     const bool live = c >= 0 && y[i] > 0 && c != y[i];
-                    v[r] = live ? acc[j][i][r] + sbias[n + r] : -INFINITY;
+                    if constexpr (Q) v[r] = live ? (acc[j][i][r] + sbias[n + r]) - slq[n + r] : -INFINITY;
+                    else v[r] = live ? acc[j][i][r] + sbias[n + r] : -INFINITY;
                     if (live) {                                       // this lane's slots in ascending order
                         if (v[r] > m[i]) { s[i] = s[i] * __expf(m[i] - v[r]) + 1.0f; m[i] = v[r]; }
                         else s[i] += __expf(v[r] - m[i]);
@@ -209,6 +218,14 @@ __global__ __launch_bounds__(256) void shared_ce_fwd_kernel(P p) {
         }
     }
 }
+
+template <typename T>
+__global__ __launch_bounds__(256) void shared_ce_fwd_kernel(P p) { shared_ce_fwd_body<T, false>(p); }
+
+// With the term, two waves per SIMD are asked for: the bf16 form sits at the 256-register edge of that occupancy and the extra
+// LDS operand would otherwise halve it (measured: the forward 0.13 -> 0.23 ms at 50 k rows x 1024 slots).
+template <typename T>
+__global__ __launch_bounds__(256, 2) void shared_ce_fwd_q_kernel(P p) { shared_ce_fwd_body<T, true>(p); }
 
 template <typename T>
 __device__ __forceinline__ void store_quad(T* dst, const float (&x)[4]) {
@@ -337,7 +354,8 @@ int forward(const P& p, hipStream_t st) {
         default: rc = launch_label<T, 64, 1>(p, st); break;
     }
     if (rc) return rc;
-    hipLaunchKernelGGL((shared_ce_fwd_kernel<T>), dim3((unsigned)edgl_cdiv(p.R, 128)), dim3(256), 0, st, p);
+    if (p.logq) hipLaunchKernelGGL((shared_ce_fwd_q_kernel<T>), dim3((unsigned)edgl_cdiv(p.R, 128)), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((shared_ce_fwd_kernel<T>), dim3((unsigned)edgl_cdiv(p.R, 128)), dim3(256), 0, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
@@ -405,9 +423,10 @@ extern "C" long edgl_shared_ce_workspace(int R, int C, int S, int dtype) {
     return sce::layout(R, C, S, dtype).total;
 }
 
-extern "C" int edgl_shared_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* shared, const int64_t* labels,
-                                  const int32_t* nvalid, int R, int C, int I, int S, float* vals, float* label_val, float* row_lse,
-                                  int dtype, void* stream) {
+// logq (f32 [I], or NULL): the label and every live slot read v - logq[c]; NULL launches the kernels without the term
+extern "C" int edgl_shared_ce_fwd_q(const void* rows, const void* table, const float* out_bias, const float* logq, const int32_t* shared,
+                                    const int64_t* labels, const int32_t* nvalid, int R, int C, int I, int S, float* vals,
+                                    float* label_val, float* row_lse, int dtype, void* stream) {
     const int rc = sce::check_shape("edgl_shared_ce_fwd", R, C, I, S, dtype);                  // (first: no pointer is read before it)
     if (rc) return rc;
     EDGL_REQUIRE(rows && table && out_bias && shared && labels && vals && label_val && row_lse, EDGL_ERR_NULL,
@@ -416,10 +435,17 @@ extern "C" int edgl_shared_ce_fwd(const void* rows, const void* table, const flo
                  "edgl_shared_ce_fwd: rows, table and vals must be 16-byte aligned");
     sce::P p{};
     p.rows = rows; p.table = table; p.bias = out_bias; p.shared = shared; p.labels = labels; p.nvalid = nvalid;
+    p.logq = logq;
     p.R = R; p.C = C; p.I = I; p.S = S; p.Sp = sce::pad8(S);
     p.vals = vals; p.label_val = label_val; p.lse = row_lse;
     hipStream_t st = (hipStream_t)stream;
     return dtype == EDGL_BF16 ? sce::forward<bf16>(p, st) : sce::forward<float>(p, st);
+}
+
+extern "C" int edgl_shared_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* shared, const int64_t* labels,
+                                  const int32_t* nvalid, int R, int C, int I, int S, float* vals, float* label_val, float* row_lse,
+                                  int dtype, void* stream) {
+    return edgl_shared_ce_fwd_q(rows, table, out_bias, nullptr, shared, labels, nvalid, R, C, I, S, vals, label_val, row_lse, dtype, stream);
 }
 
 extern "C" int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,

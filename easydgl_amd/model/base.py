@@ -11,6 +11,9 @@ from .. import ops
 from ..module.coding import glorot_uniform_
 
 
+NEG_SAMPLERS = ("uniform", "popularity", "log_uniform")     # FLAGS.neg_sampler
+
+
 class _Dense(nn.Module):
     """tf.layers.dense parameters: kernel [in,out] glorot_uniform, bias zeros."""
 
@@ -74,6 +77,16 @@ class Sequential(nn.Module):
         if self.shared_negatives > 0 and self.train_negatives > 0:
             raise ValueError("shared_negatives and train_negatives are both set: one estimator per run (per-row lists, DESIGN "
                              "4.13, or one shared list, DESIGN 4.15)")
+        # weighted negatives with the log-Q correction: which distribution the sampled modes draw from
+        self.neg_sampler = str(getattr(FLAGS, "neg_sampler", None) or "uniform")
+        alpha = getattr(FLAGS, "neg_alpha", None)
+        self.neg_alpha = 0.75 if alpha is None else float(alpha)
+        if self.neg_sampler not in NEG_SAMPLERS:
+            raise ValueError(f"neg_sampler={self.neg_sampler!r}: one of {', '.join(NEG_SAMPLERS)}")
+        if self.neg_sampler != "uniform" and self.train_negatives <= 0 and self.shared_negatives <= 0:
+            raise ValueError(f"neg_sampler={self.neg_sampler!r} needs train_negatives > 0 or shared_negatives > 0: the full softmax "
+                             "draws no negatives")
+        self._neg_dist = None   # ops.NegDist over [1, _negatives_hi()): set_negative_weights (log_uniform: built at the first draw)
         # lazy row-wise Adam for the item table: the table's gradient lands in place in the gradient arena and the
         # optimizer walks only the rows the step used
         self.lazy_adam = bool(getattr(FLAGS, "lazy_adam", False))
@@ -515,33 +528,81 @@ class Sequential(nn.Module):
         train_step advances neg_step, so a resumed run draws the lists the uninterrupted run would have drawn, and calling
         train_loss twice in between scores the same lists.  A range [1, hi) too small for the sampler is refused by the sampler.
         `shared` (int32 [S], one list for every row) or FLAGS.shared_negatives = S > 0: each row's label and the step's ONE list
-        (ops.SharedCEFn), drawn once through the same sampler, keyed by (train_neg_seed, neg_step)."""
+        (ops.SharedCEFn), drawn once through the same sampler, keyed by (train_neg_seed, neg_step).
+        FLAGS.neg_sampler other than "uniform" (DESIGN 4.16): the lists are drawn by the model's weights (set_negative_weights) and
+        every sampled loss — a caller's `candidates` / `shared` too — subtracts log Q(c) from the label's and every slot's logit."""
         tab = self.item_embs.lookup_table
         if candidates is not None and shared is not None:
             raise ValueError("_score_ce: both `candidates` and `shared` are given: one estimator per call")
         if shared is None and candidates is None and self.shared_negatives > 0:
             shared = self.draw_shared_negatives(labels.device)
+        sampled = shared is not None or candidates is not None or self.train_negatives > 0
+        # FLAGS.neg_sampler (DESIGN 4.16): a non-uniform sampler corrects every sampled loss by log Q, a caller's list included
+        dist = self._negative_dist() if sampled else None
+        tail = () if dist is None else (dist.logq_on(labels.device),)
         if shared is not None:
             if self.lazy_adam:
                 self._lazy_lists = (labels, None, shared)
             return ops.SharedCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, shared, self.deterministic,
-                                        self._lazy_grad if self.lazy_adam else None)
-        if candidates is None and self.train_negatives <= 0:
+                                        self._lazy_grad if self.lazy_adam else None, *tail)
+        if not sampled:
             return ops.ScoreCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, self.deterministic)
         if candidates is None:
-            candidates = ops.sample_negatives(None, labels, self.train_negatives, 1, self._negatives_hi(), self.train_neg_seed,
-                                              self.neg_step, 0)
+            candidates = self._sample(None, labels, self.train_negatives, self.train_neg_seed, self.neg_step, 0, dist)
         if self.lazy_adam:      # (DESIGN 4.14: the table gradient is added into the arena; the optimizer needs the step's lists)
             self._lazy_lists = (labels, candidates, None)
             return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic,
-                                         self._lazy_grad)
+                                         self._lazy_grad, *tail)
+        if dist is not None:
+            return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic, None,
+                                         *tail)
         return ops.SampledCEFn.apply(rows, tab, self.output_bias, self.compute(tab), labels, candidates, self.deterministic)
 
+    def _sample(self, seen, labels, n, seed, step, row0, dist):
+        """ops.sample_negatives over [1, _negatives_hi()): uniform, or by `dist` (ops.NegDist)."""
+        if dist is None:
+            return ops.sample_negatives(seen, labels, n, 1, self._negatives_hi(), seed, step, row0)
+        return ops.sample_negatives(seen, labels, n, 1, self._negatives_hi(), seed, step, row0, dist=dist)
+
     def draw_shared_negatives(self, device, step=None):
-        """int32 [S]: the shared list of step `step` (default: neg_step) — the device sampler asked for one row of S negatives."""
+        """int32 [S]: the shared list of step `step` (default: neg_step) — the device sampler asked for one row of S negatives,
+        from the model's negative distribution (FLAGS.neg_sampler)."""
         one = torch.zeros(1, device=device, dtype=torch.int64)
-        return ops.sample_negatives(None, one, self.shared_negatives, 1, self._negatives_hi(), self.train_neg_seed,
-                                    self.neg_step if step is None else step, 0).reshape(-1)
+        return self._sample(None, one, self.shared_negatives, self.train_neg_seed, self.neg_step if step is None else step, 0,
+                            self._negative_dist()).reshape(-1)
+
+    # ---- weighted negatives (DESIGN 4.16) ---------------------------------------------------------------------
+    def negative_dist(self, weights, T_reject=0) -> "ops.NegDist":
+        """ops.build_neg_dist over the model's negative range [1, _negatives_hi()) from per-item weights (float [>= hi], indexed by
+        item id; entries outside the range are ignored); logq is sized to the item table.  T_reject: the seen ids a row may reject
+        besides its label (training: 0; evaluation: the sequence length)."""
+        import numpy as np
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        hi, rows = self._negatives_hi(), int(self.item_embs.lookup_table.shape[0])
+        if w.shape[0] < hi:
+            raise ValueError(f"negative weights: {w.shape[0]} entries, one per item id of [0, {hi}) are needed")
+        full = np.zeros(rows, dtype=np.float64)
+        full[:hi] = w[:hi]
+        return ops.build_neg_dist(full, 1, hi, T_reject)
+
+    def set_negative_weights(self, weights) -> None:
+        """The weights FLAGS.neg_sampler draws training negatives by (float [>= hi], indexed by item id): ops.neg_weights gives the
+        presets — popularity from item counts, log_uniform from the ids' order.  None: back to no weights."""
+        if self.neg_sampler == "uniform":
+            raise ValueError("set_negative_weights: neg_sampler is 'uniform' (FLAGS.neg_sampler = popularity or log_uniform)")
+        self._neg_dist = None if weights is None else self.negative_dist(weights, 0)
+
+    def _negative_dist(self):
+        """None for the uniform sampler, else the training distribution; log_uniform needs nothing but the range and is built here."""
+        if self.neg_sampler == "uniform":
+            return None
+        if self._neg_dist is None:
+            if self.neg_sampler != "log_uniform":
+                raise ValueError(f"neg_sampler={self.neg_sampler!r}: no weights yet — call model.set_negative_weights(weights) before "
+                                 "the first training step (ops.neg_weights('popularity', I, 1, hi, counts, alpha) from item counts)")
+            hi = self._negatives_hi()
+            self.set_negative_weights(ops.neg_weights("log_uniform", hi, 1, hi))
+        return self._neg_dist
 
     def train_step(self, features, labels):
         """One optimizer step: forward, backward, TF-Adam.  Returns the loss tensor (device scalar).
@@ -592,15 +653,16 @@ class Sequential(nn.Module):
                                     features["seqs_i"] if mask_seen else None)[0]
 
     @torch.no_grad()
-    def eval_candidates(self, features, labels, candidates=None, num_negatives=100, mask_seen=True, seed=0, step=0, row0=0):
+    def eval_candidates(self, features, labels, candidates=None, num_negatives=100, mask_seen=True, seed=0, step=0, row0=0, dist=None):
         """int32 [B]: the label's place among its candidates in the (logit desc, item id asc) order.  `candidates` int32 [B, N], or
         None: `num_negatives` ids per sequence drawn from the catalogue by ops.sample_negatives(seed, step, row0) — never an id of
         the sequence's history and never the label, whatever mask_seen says; mask_seen decides whether seen ids of a caller's list
-        and a seen label read -inf."""
+        and a seen label read -inf.  `dist` (ops.NegDist, e.g. negative_dist(weights, T_reject=sequence length)): the
+        negatives are drawn by its weights — the popularity-sampled protocol; the ranking uses the raw logits, no log-Q term."""
         lab = self._last_labels(labels)
         seen = features["seqs_i"]
         if candidates is None:
-            candidates = ops.sample_negatives(seen, lab, num_negatives, 1, self._negatives_hi(), seed, step, row0)
+            candidates = self._sample(seen, lab, num_negatives, seed, step, row0, dist)
         tab = self.item_embs.lookup_table
         return ops.score_candidates(self._last_rows(features), self.compute(tab), self.output_bias, candidates,
                                     seen if mask_seen else None, lab, want_scores=False)[2]
@@ -618,16 +680,18 @@ class Sequential(nn.Module):
         self._rank_count = 0
 
     @torch.no_grad()
-    def eval_step(self, features, labels, mask_seen=True, by_rank=False, *, candidates=None, negatives=0, neg_seed=0, row0=0):
+    def eval_step(self, features, labels, mask_seen=True, by_rank=False, *, candidates=None, negatives=0, neg_seed=0, row0=0,
+                  neg_dist=None):
         """`candidates` (int32 [B, N]) or `negatives` > 0: the label is ranked inside the list / among that many sampled negatives
-        (eval_candidates; `row0` = index of the batch's first sequence in its split) and the step accumulates like a by-rank step."""
+        (eval_candidates; `row0` = index of the batch's first sequence in its split) and the step accumulates like a by-rank step.
+        `neg_dist` (ops.NegDist): the sampled negatives are drawn by its weights instead of uniformly."""
         if self._metrics is None:
             self.reset_metrics()
         on_list = candidates is not None or negatives > 0
         if by_rank or on_list:
             if self._metric_count != self._rank_count:
                 raise RuntimeError("eval_step: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
-            rank = (self.eval_candidates(features, labels, candidates, negatives, mask_seen, neg_seed, 0, row0) if on_list
+            rank = (self.eval_candidates(features, labels, candidates, negatives, mask_seen, neg_seed, 0, row0, neg_dist) if on_list
                     else self.eval_rank(features, labels, mask_seen))
             # (steps on lists add row by row: with `row0` a split gives the same sums whatever the batch size)
             ops.rank_metrics_from_rank(rank, self._rank_ks_dev, self._rank_sums, row_order=on_list)

@@ -610,10 +610,21 @@ class ScoreCEFn(torch.autograd.Function):
         return d_rows, d_table, d_bias, None, None, None
 
 
-def cand_ce_fwd(rows, table_c, out_bias, cand, labels):
+def _logq_arg(logq, I, device, who):
+    """The `logq` argument of the sampled losses: None, or a contiguous f32 [I] GPU tensor (NegDist.logq_on)."""
+    if logq is None:
+        return None
+    if not torch.is_tensor(logq) or logq.dtype != torch.float32 or logq.shape != (I,) or logq.device != device or not logq.is_contiguous():
+        raise _lib.EdglError(f"{who}: logq must be a contiguous f32 [{I}] tensor on {device}, one term per item id (got "
+                             f"{getattr(logq, 'dtype', type(logq))} {tuple(getattr(logq, 'shape', ()))})")
+    return logq
+
+
+def cand_ce_fwd(rows, table_c, out_bias, cand, labels, logq=None):
     """(vals f32 [R, N + 1], label_val f32 [R], lse f32 [R]) of edgl_cand_ce_fwd: slot 0 is the label, slot 1 + n is cand[r, n]
     (int32 [R, N]); -inf at an empty slot, an id >= I and an accidental hit (cand[r, n] == labels[r]); rows of label 0 are skipped
-    (vals -inf, label_val = lse = 0).  The values carry the bits of score_candidates."""
+    (vals -inf, label_val = lse = 0).  The values carry the bits of score_candidates.
+    logq (f32 [I]): the label and every live slot read v - logq[c] (edgl_cand_ce_fwd_q); zeros give the bits of None."""
     _ptr(rows)                                               # (GPU tensors only: refused before anything else)
     R, C = rows.shape
     I = table_c.shape[0]
@@ -628,8 +639,13 @@ def cand_ce_fwd(rows, table_c, out_bias, cand, labels):
     vals = torch.empty((R, N + 1), device=dev, dtype=torch.float32)
     label_val = torch.empty(R, device=dev, dtype=torch.float32)
     lse = torch.empty(R, device=dev, dtype=torch.float32)
-    check(lib.edgl_cand_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), R, C, I, N, _ptr(vals),
-                               _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_cand_ce_fwd")
+    logq = _logq_arg(logq, I, dev, "cand_ce")
+    if logq is None:
+        check(lib.edgl_cand_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), R, C, I, N, _ptr(vals),
+                                   _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_cand_ce_fwd")
+    else:
+        check(lib.edgl_cand_ce_fwd_q(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(logq), _ptr(cand), _ptr(labels), R, C, I, N,
+                                     _ptr(vals), _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_cand_ce_fwd_q")
     return vals, label_val, lse
 
 
@@ -640,14 +656,16 @@ class SampledCEFn(torch.autograd.Function):
     skipped inside the kernels, so a row's list never depends on which other rows are weighted.
     deterministic: the table / bias gradient is summed in plan order (edgl_cand_ce_table_det) instead of with f32 atomics.
     d_table_out (f32 [I, C]): the backward ADDS the table gradient into it (both entry points add), allocates no
-    [I, C] tensor and returns None for the table master; d_bias stays a dense f32 [I - 1]."""
+    [I, C] tensor and returns None for the table master; d_bias stays a dense f32 [I - 1].
+    logq (f32 [I]): the log-Q correction of a weighted sampler, subtracted from the label's and every live slot's
+    value in the forward; a constant, so the backward is the same code on the corrected vals / lse."""
 
     @staticmethod
-    def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False, d_table_out=None):
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False, d_table_out=None, logq=None):
         ctx.deterministic = bool(deterministic)
         ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SampledCEFn")
         rows, labels, cand = rows.contiguous(), labels.reshape(-1).contiguous(), cand.contiguous()
-        vals, label_val, lse = cand_ce_fwd(rows, table_c, out_bias, cand, labels)
+        vals, label_val, lse = cand_ce_fwd(rows, table_c, out_bias, cand, labels, logq)
         R = rows.shape[0]
         loss = torch.empty(1, device=rows.device, dtype=torch.float32)
         coef = torch.empty(R, device=rows.device, dtype=torch.float32)
@@ -678,7 +696,7 @@ class SampledCEFn(torch.autograd.Function):
             plan = segsum_plan_buffer(n, I, dev)
             check(lib.edgl_cand_ce_table_det(_ptr(rows), _ptr(cand), _ptr(labels), _ptr(dv), R, C, I, N, _ptr(d_table), _ptr(d_bias),
                                              _ptr(keys), _ptr(plan), _code(rows), _stream()), "edgl_cand_ce_table_det")
-        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None
+        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None, None
 
 
 MAX_SHARED = 8192
@@ -696,23 +714,30 @@ def _shared_ce_check(rows, table_c, shared, labels):
         raise _lib.EdglError(f"shared_ce: labels must be int64 [{R}] (got {labels.dtype} {tuple(labels.shape)})")
 
 
-def _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid):
+def _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid, logq=None):
     R, C = rows.shape
     I, S, dev = table_c.shape[0], shared.shape[0], rows.device
     vals = torch.empty((R, S), device=dev, dtype=torch.float32)
     label_val = torch.empty(R, device=dev, dtype=torch.float32)
     lse = torch.empty(R, device=dev, dtype=torch.float32)
-    check(lib.edgl_shared_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(shared), _ptr(labels), _ptr(nvalid), R, C, I, S,
-                                 _ptr(vals), _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_shared_ce_fwd")
+    logq = _logq_arg(logq, I, dev, "shared_ce")
+    if logq is None:
+        check(lib.edgl_shared_ce_fwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(shared), _ptr(labels), _ptr(nvalid), R, C, I, S,
+                                     _ptr(vals), _ptr(label_val), _ptr(lse), _code(rows), _stream()), "edgl_shared_ce_fwd")
+    else:
+        check(lib.edgl_shared_ce_fwd_q(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(logq), _ptr(shared), _ptr(labels), _ptr(nvalid),
+                                       R, C, I, S, _ptr(vals), _ptr(label_val), _ptr(lse), _code(rows), _stream()),
+              "edgl_shared_ce_fwd_q")
     return vals, label_val, lse
 
 
-def shared_ce_fwd(rows, table_c, out_bias, shared, labels):
+def shared_ce_fwd(rows, table_c, out_bias, shared, labels, logq=None):
     """(vals f32 [R, S], label_val f32 [R], lse f32 [R]) of edgl_shared_ce_fwd, in the caller's row order: vals[r, s] is the value of
     (rows[r], shared[s]) (int32 [S], one list for every row); -inf at an id < 0, an id >= I and an accidental hit (shared[s] ==
-    labels[r]); label_val is the label's value; rows of label 0 are skipped (vals -inf, label_val = lse = 0)."""
+    labels[r]); label_val is the label's value; rows of label 0 are skipped (vals -inf, label_val = lse = 0).
+    logq (f32 [I]): the label and every live slot read v - logq[c] (edgl_shared_ce_fwd_q); zeros give the bits of None."""
     _shared_ce_check(rows, table_c, shared, labels)
-    return _shared_ce_fwd(rows.contiguous(), table_c, out_bias, shared.contiguous(), labels.contiguous(), None)
+    return _shared_ce_fwd(rows.contiguous(), table_c, out_bias, shared.contiguous(), labels.contiguous(), None, logq)
 
 
 class SharedCEFn(torch.autograd.Function):
@@ -722,10 +747,11 @@ class SharedCEFn(torch.autograd.Function):
     compute dtype, a dense f32 d_table [I, C] (zero-filled, then added into) and d_bias [I - 1].  The weighted rows are compacted
     first, as in ScoreCEFn: the list does not depend on the row, so that changes nothing but the work.
     deterministic: no float atomics — repeated ids are summed in slot order, the label term over a k_segsum.hip plan.
-    d_table_out (f32 [I, C]): the backward ADDS the table gradient into it and returns None for the table master."""
+    d_table_out (f32 [I, C]): the backward ADDS the table gradient into it and returns None for the table master.
+    logq (f32 [I]): the log-Q correction of a weighted sampler, as in SampledCEFn."""
 
     @staticmethod
-    def forward(ctx, rows, table_master, out_bias, table_c, labels, shared, deterministic=False, d_table_out=None):
+    def forward(ctx, rows, table_master, out_bias, table_c, labels, shared, deterministic=False, d_table_out=None, logq=None):
         ctx.deterministic = bool(deterministic)
         ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SharedCEFn")
         rows, labels, shared = rows.contiguous(), labels.reshape(-1).contiguous(), shared.contiguous()
@@ -733,7 +759,7 @@ class SharedCEFn(torch.autograd.Function):
         if lib.edgl_shared_ce_workspace(rows.shape[0], rows.shape[1], shared.shape[0], _code(rows)) < 0:     # (the shape rule, before the compaction)
             check(-1, "edgl_shared_ce_workspace")
         rows, labels, _perm, inv, nvalid = compact_rows(rows, labels)
-        vals, label_val, lse = _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid)
+        vals, label_val, lse = _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid, logq)
         R = rows.shape[0]
         loss = torch.empty(1, device=rows.device, dtype=torch.float32)
         coef = torch.empty(R, device=rows.device, dtype=torch.float32)
@@ -763,7 +789,7 @@ class SharedCEFn(torch.autograd.Function):
                                      _ptr(coef), _ptr(g), _ptr(nvalid), R, C, I, S, _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
                                      _ptr(ws), _ptr(keys), _ptr(plan), code, _stream()), "edgl_shared_ce_bwd")
         check(lib.edgl_scatter_rows(_ptr(d_rows_c), _ptr(inv), R, C, _ptr(d_rows), code, _stream()), "edgl_scatter_rows")
-        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None
+        return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None, None
 
 
 class ScoreLogitsFn(torch.autograd.Function):
@@ -1124,10 +1150,112 @@ def rank_metrics_from_rank(rank: torch.Tensor, ks: torch.Tensor, sums: torch.Ten
 
 
 # ---- K6c: evaluation on candidate lists (csrc/k_eval_cand.hip) — sampled negatives and re-ranking -------------------
-def sample_negatives(seen, labels, n, lo, hi, seed, step=0, row0=0):
+class NegDist:
+    """A weighted negative distribution over the ids [lo, hi), as build_neg_dist leaves it: the alias table on the
+    host (thr uint32 [n], alias int32 [n], n = hi - lo), logq f32 [I] and the number of rejected ids per row the table was checked
+    for (T_reject).  The device copies — the interleaved (thr, alias) table the sampler reads and logq — are made once per device."""
+
+    def __init__(self, lo, hi, T_reject, thr, alias, logq):
+        self.lo, self.hi, self.T_reject = int(lo), int(hi), int(T_reject)
+        self.thr, self.alias, self.logq = thr, alias, logq
+        self._dev = {}
+
+    def _on(self, device):
+        key = str(torch.device(device))
+        if key not in self._dev:
+            tab = np.stack([self.thr.view(np.int32), self.alias], axis=1)        # [n, 2]: one 8-byte entry per bucket
+            self._dev[key] = (torch.from_numpy(np.ascontiguousarray(tab)).to(device), torch.from_numpy(self.logq).to(device))
+        return self._dev[key]
+
+    def table_on(self, device) -> torch.Tensor:
+        return self._on(device)[0]
+
+    def logq_on(self, device) -> torch.Tensor:
+        return self._on(device)[1]
+
+    def probabilities(self) -> np.ndarray:
+        """fp64 [n]: the probability of every id of [lo, hi) that the stored (thr, alias) imply for a uniform bucket."""
+        n = self.hi - self.lo
+        acc = np.where(self.alias == np.arange(n), 1.0, self.thr.astype(np.float64) * 2.0 ** -32)
+        p = acc.copy()
+        np.add.at(p, self.alias, 1.0 - acc)
+        return p / n
+
+
+def neg_weights(sampler, I, lo, hi, counts=None, alpha=0.75):
+    """fp64 [I]: the weight presets of FLAGS.neg_sampler over the ids [lo, hi); 0 outside the range.
+    popularity: (count_c + 1)^alpha — add-one smoothing, so every id of the range can be drawn and no corrected logit is +inf.
+    log_uniform: log((c - lo + 2) / (c - lo + 1)) — TensorFlow's default sampler, meant for ids sorted by falling frequency."""
+    w = np.zeros(int(I), dtype=np.float64)
+    if sampler == "popularity":
+        if counts is None:
+            raise ValueError("neg_weights: the popularity sampler needs `counts` (one count per item id)")
+        counts = np.asarray(counts, dtype=np.float64).reshape(-1)
+        if counts.shape[0] < hi or not np.isfinite(counts[lo:hi]).all() or (counts[lo:hi] < 0).any():
+            raise ValueError(f"neg_weights: counts must hold a finite count >= 0 for every id of [{lo}, {hi}) (got {counts.shape[0]} entries)")
+        w[lo:hi] = (counts[lo:hi] + 1.0) ** float(alpha)
+    elif sampler == "log_uniform":
+        k = np.arange(hi - lo, dtype=np.float64)
+        w[lo:hi] = np.log((k + 2.0) / (k + 1.0))
+    else:
+        raise ValueError(f"neg_weights: sampler {sampler!r} (popularity or log_uniform)")
+    return w
+
+
+def build_neg_dist(weights, lo, hi, T_reject=0) -> NegDist:
+    """The alias table (Vose's method, fp64) and the log-Q terms of the weighted negative sampler over the ids
+    [lo, hi) of `weights` (float [I]; entries outside the range are ignored).  Host work in numpy, once per run.
+    Refused: a weight of the range that is not finite or not > 0, and weights whose T_reject + 1 heaviest ids hold more than half of
+    the total — the weighted form of 2 (T + 1) <= hi - lo: a row rejects at most T_reject seen ids and its label, so every attempt
+    is then rejected with probability <= 1/2 and a slot stays empty (-1) with probability <= 2^-32.
+    Build order (fixed): p_j = w_j n / sum(w); the buckets with p_j < 1 and those with p_j >= 1 go on two stacks in ascending j; the
+    tops s (small) and l (large) are popped, bucket s keeps p_s and takes alias l, p_l <- (p_l + p_s) - 1 and l goes back on the
+    stack its new p_l names; what is left on either stack when one runs empty is a full bucket (alias[j] = j).  thr[j] =
+    floor(p_j 2^32) < 2^32 for a bucket with an alias; a full bucket returns j on either branch, so no threshold has to be 2^32.
+    logq[c] = log(w_c / sum(w)) for lo <= c < hi (fp64, rounded once to f32), 0 elsewhere."""
+    w_all = np.asarray(weights)
+    if w_all.ndim != 1 or w_all.dtype not in (np.float64, np.float32):
+        raise ValueError(f"build_neg_dist: weights must be float64 / float32 [I] (got {w_all.dtype} {w_all.shape})")
+    I, lo, hi, T_reject = w_all.shape[0], int(lo), int(hi), int(T_reject)
+    if not (1 <= lo < hi <= I) or T_reject < 0:
+        raise ValueError(f"build_neg_dist: range [{lo}, {hi}) of {I} ids, T_reject={T_reject} (1 <= lo < hi <= I, T_reject >= 0)")
+    w = w_all[lo:hi].astype(np.float64)
+    n = hi - lo
+    bad = ~np.isfinite(w) | ~(w > 0.0)
+    if bad.any():
+        c = lo + int(np.argmax(bad))
+        raise ValueError(f"build_neg_dist: weight {w[c - lo]!r} of id {c}: every weight of [{lo}, {hi}) must be finite and > 0 "
+                         f"({int(bad.sum())} are not; a zero weight would make the id's corrected logit +inf)")
+    total = float(w.sum())
+    k = min(T_reject + 1, n)
+    top = float(np.sort(w)[n - k:].sum())
+    if top > 0.5 * total:
+        raise ValueError(f"build_neg_dist: the T_reject + 1 = {T_reject + 1} heaviest ids of [{lo}, {hi}) hold {top / total:.4f} of "
+                         "the weight, more than 1/2: a row may reject that many ids, every attempt must be rejected with "
+                         "probability <= 1/2 (a slot then stays empty with probability <= 2^-32)")
+    p = w * (n / total)
+    small = np.flatnonzero(p < 1.0).tolist()
+    large = np.flatnonzero(p >= 1.0).tolist()
+    p = p.tolist()
+    thr = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    alias = np.arange(n, dtype=np.int32)
+    while small and large:
+        s, l = small.pop(), large.pop()
+        thr[s] = int(p[s] * 4294967296.0)                    # (p_s < 1 in fp64 and the product is exact: < 2^32)
+        alias[s] = l
+        p[l] = (p[l] + p[s]) - 1.0
+        (small if p[l] < 1.0 else large).append(l)
+    logq = np.zeros(I, dtype=np.float32)
+    logq[lo:hi] = np.log(w / total).astype(np.float32)
+    return NegDist(lo, hi, T_reject, thr, alias, logq)
+
+
+def sample_negatives(seen, labels, n, lo, hi, seed, step=0, row0=0, dist=None):
     """int32 [R, n]: per row n ids drawn uniformly from [lo, hi) (with replacement between slots), never one of the row's seen ids
     (int64 [R, T] or None) and never labels[r] (int64 [R]).  Counter-based on (seed, step, row0 + r, slot): `row0` is the index of the
-    batch's first sequence in its split, so a sequence's list does not depend on the batch size.  Needs 2 (T + 1) <= hi - lo."""
+    batch's first sequence in its split, so a sequence's list does not depend on the batch size.  Needs 2 (T + 1) <= hi - lo.
+    dist (NegDist of build_neg_dist over the same [lo, hi)): the ids are drawn by its weights instead
+    (edgl_sample_negatives_alias); the table must have been checked for at least T rejected ids per row."""
     _ptr(labels)                                             # (GPU tensors only: refused before anything else)
     R = labels.shape[0]
     labels = _rank_labels(labels, R, "sample_negatives")
@@ -1138,6 +1266,18 @@ def sample_negatives(seen, labels, n, lo, hi, seed, step=0, row0=0):
     T = 0 if seen is None else seen.shape[1]
     cand = torch.empty((R, int(n)), device=labels.device, dtype=torch.int32)
     mask64 = (1 << 64) - 1
+    if dist is not None:
+        if not isinstance(dist, NegDist) or (dist.lo, dist.hi) != (int(lo), int(hi)):
+            raise _lib.EdglError(f"sample_negatives: dist must be a NegDist over [{int(lo)}, {int(hi)}) (got "
+                                 f"{'[%d, %d)' % (dist.lo, dist.hi) if isinstance(dist, NegDist) else type(dist).__name__})")
+        if T > dist.T_reject:
+            raise _lib.EdglError(f"sample_negatives: {T} seen ids per row against a table checked for T_reject = {dist.T_reject} "
+                                 "(build_neg_dist(..., T_reject=T): the T + 1 heaviest ids may hold at most half of the weight)")
+        tab = dist.table_on(labels.device)
+        check(lib.edgl_sample_negatives_alias(_ptr(seen), T, _ptr(labels), R, int(n), int(lo), int(hi), int(hi), _ptr(tab),
+                                              int(seed) & mask64, int(step) & mask64, int(row0), _ptr(cand), _stream()),
+              "edgl_sample_negatives_alias")
+        return cand
     check(lib.edgl_sample_negatives(_ptr(seen), T, _ptr(labels), R, int(n), int(lo), int(hi), int(hi), int(seed) & mask64,
                                     int(step) & mask64, int(row0), _ptr(cand), _stream()), "edgl_sample_negatives")
     return cand

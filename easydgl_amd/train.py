@@ -91,7 +91,19 @@ def args(argv=None):
                    help="EasyDGL with --train_negatives or --shared_negatives: lazy row-wise Adam for the item table (DESIGN 4.14, TensorFlow's "
                         "LazyAdamOptimizer) — the table gradient lands in place and the optimizer updates only the rows the step used "
                         "(input ids, labels, negatives); every other parameter keeps the dense Adam")
+    p.add_argument("--neg_sampler", choices=("uniform", "popularity", "log_uniform"), default="uniform",
+                   help="with --train_negatives / --shared_negatives: the distribution the training negatives are drawn from (DESIGN "
+                        "4.16).  popularity: (count + 1)^neg_alpha over the item counts of the training split; log_uniform: "
+                        "TensorFlow's default, for ids sorted by falling frequency.  Both subtract log Q(c) from every sampled logit")
+    p.add_argument("--neg_alpha", type=float, default=0.75, help="exponent of the popularity sampler (word2vec: 0.75)")
+    p.add_argument("--eval_neg_sampler", choices=("uniform", "popularity"), default="uniform",
+                   help="with --eval_negatives: draw the evaluation negatives by (count + 1)^neg_alpha over the training split's item "
+                        "counts — the popularity-sampled protocol; ranking uses the raw logits")
     a = p.parse_args(argv)
+    if a.neg_sampler != "uniform" and a.train_negatives <= 0 and a.shared_negatives <= 0:
+        p.error("--neg_sampler needs --train_negatives N > 0 or --shared_negatives S > 0: the full softmax draws no negatives")
+    if a.eval_neg_sampler != "uniform" and a.eval_negatives <= 0:
+        p.error("--eval_neg_sampler needs --eval_negatives N > 0")
     if a.train_negatives > 0 and a.shared_negatives > 0:
         p.error("--shared_negatives with --train_negatives: one estimator per run (per-row lists or one shared list)")
     if a.shared_negatives < 0 or a.shared_negatives > 8192:
@@ -160,7 +172,9 @@ def save_checkpoint(model, path: str) -> None:
     model.settle_state()       # (the static engine keeps the counters one step ahead: the file holds "steps taken")
     torch.save({"arena": model._arena.detach().cpu(), "adam_m": model._adam_m.cpu(), "adam_v": model._adam_v.cpu(),
                 "adam_state": model._adam_state.cpu(), "rng_state": model._rng_state.cpu(),
-                "offsets": dict(model._offsets), "neg_step": int(getattr(model, "neg_step", 0))}, path)
+                "offsets": dict(model._offsets), "neg_step": int(getattr(model, "neg_step", 0)),
+                "neg_sampler": str(getattr(model, "neg_sampler", "uniform")), "neg_alpha": float(getattr(model, "neg_alpha", 0.75))},
+               path)
 
 
 def load_checkpoint(model, path: str) -> None:
@@ -168,6 +182,12 @@ def load_checkpoint(model, path: str) -> None:
     ck = torch.load(path, map_location="cpu")
     if dict(ck["offsets"]) != dict(model._offsets):
         raise ValueError("checkpoint does not match the model's parameter layout")
+    # (optional fields, DESIGN 4.16: a resumed run must draw the lists the uninterrupted run would have drawn)
+    saved = (str(ck.get("neg_sampler", "uniform")), float(ck.get("neg_alpha", 0.75)))
+    mine = (str(getattr(model, "neg_sampler", "uniform")), float(getattr(model, "neg_alpha", 0.75)))
+    if saved[0] != mine[0] or (saved[0] == "popularity" and saved[1] != mine[1]):
+        raise ValueError(f"checkpoint was trained with neg_sampler={saved[0]!r} neg_alpha={saved[1]}, the model has "
+                         f"neg_sampler={mine[0]!r} neg_alpha={mine[1]}: a resumed run keeps its negative sampler")
     with torch.no_grad():
         model._arena.copy_(ck["arena"])
         model._adam_m.copy_(ck["adam_m"])
@@ -189,21 +209,23 @@ def regressive_batch(tok, tim, is_training: bool):
 
 
 def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False, negatives: int = 0,
-             neg_seed: int = 0) -> Dict[str, float]:
+             neg_seed: int = 0, neg_dist=None) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
     prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
     (--device_data) — the batches are then assembled on the device, in file order.  `by_rank`: the metrics from the label's rank
     (model.eval_step(by_rank=True)) — the same H / N values plus "MRR".  `negatives` > 0: the sampled-negative protocol —
     the label ranked among that many negatives per sequence, keyed by (neg_seed, step 0, the sequence's index in the split): every
-    pass over a split ranks against the same lists, whatever the batch size; cut-offs (1, 5, 10)."""
+    pass over a split ranks against the same lists, whatever the batch size; cut-offs (1, 5, 10).  `neg_dist` (ops.NegDist): those
+    negatives are drawn by its weights."""
     import torch
     from . import data as D
     if negatives > 0:
         model.reset_metrics((1, 5, 10))
         row0 = [0]      # running sequence offset of the split
+        extra = {} if neg_dist is None else {"neg_dist": neg_dist}
 
         def step(feats, labels):
-            model.eval_step(feats, labels, mask_seen=mask_seen, negatives=negatives, neg_seed=neg_seed, row0=row0[0])
+            model.eval_step(feats, labels, mask_seen=mask_seen, negatives=negatives, neg_seed=neg_seed, row0=row0[0], **extra)
             row0[0] += labels.shape[0]
     else:
         model.reset_metrics()
@@ -271,8 +293,21 @@ def run(FLAGS) -> Dict[str, float]:
     shared_negatives = int(getattr(FLAGS, "shared_negatives", 0) or 0)
     if shared_negatives > 0 and getattr(FLAGS, "graph", False):
         raise ValueError("--graph with --shared_negatives: the sampled-softmax step runs on the autograd path (model.train_step)")
+    # weighted negatives: the counts are one bincount of the training split's item ids (the host copy, with
+    # --device_data too), so a resumed run rebuilds the same table
+    neg_sampler = str(getattr(FLAGS, "neg_sampler", None) or "uniform")
+    eval_dist = None
+    if neg_sampler == "popularity" or getattr(FLAGS, "eval_neg_sampler", "uniform") == "popularity":
+        from . import ops
+        hi = model._negatives_hi()
+        counts = np.bincount(np.asarray(tr_i).reshape(-1).astype(np.int64), minlength=hi)
+        w = ops.neg_weights("popularity", hi, 1, hi, counts, float(getattr(FLAGS, "neg_alpha", 0.75)))
+        if neg_sampler == "popularity":
+            model.set_negative_weights(w)
+        if getattr(FLAGS, "eval_neg_sampler", "uniform") == "popularity":
+            eval_dist = model.negative_dist(w, T_reject=int(vl_i.shape[1]))       # (a sequence rejects its history and its label)
     # sampled-softmax training: no static engine, every batch through model.train_step
-    engine = TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0 and shared_negatives <= 0) else None
+    engine =TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0 and shared_negatives <= 0) else None
     loader = vl_loader = te_loader = None
     if device_data:
         need = sum(D.DeviceSplit.nbytes(ii, tt) + 4 * len(ii) for ii, tt in ((tr_i, tr_t), (vl_i, vl_t), (te_i, te_t)))
@@ -354,9 +389,9 @@ def run(FLAGS) -> Dict[str, float]:
             break
         if epoch % FLAGS.eval_per_steps:
             continue
-        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed)
+        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed, eval_dist)
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
-        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed)
+        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed, eval_dist)
         if stopper.step(running_loss, vl[select_on], vl, te):
             break
     return stopper.summary()

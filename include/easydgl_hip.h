@@ -554,6 +554,14 @@ int edgl_score_candidates(const void* rows, const void* table, const float* out_
  * 1 <= lo < hi <= I and 2 (T + 1) <= hi - lo (a draw is then rejected with probability <= 1/2), 0 <= T <= 1024, else EDGL_ERR_SHAPE. */
 int edgl_sample_negatives(const int64_t* seen, int T, const int64_t* labels, int R, int n, int lo, int hi, int I,
                           uint64_t seed, uint64_t step, int row0, int32_t* cand, void* stream);
+/* edgl_sample_negatives with a weighted draw: everything above stands but the last line.  thr_alias: uint32
+ * [hi - lo, 2], 8-byte aligned, entry j = (acceptance threshold thr[j], alias bucket alias[j]) of an alias table over the ids
+ * lo + j (Vose's method; a full bucket stores alias[j] = j).  With n = hi - lo:
+ *   j = ((u64)h * n) >> 32;  h2 = mix32(h + 0x68E31DA4);  id = lo + (h2 < thr[j] || alias[j] == j ? j : alias[j])
+ * one 8-byte random read per attempt.  The weighted form of 2 (T + 1) <= hi - lo is a property of the weights — the T + 1
+ * heaviest ids hold at most half of the total weight — and is the table builder's to check (easydgl_amd.ops.build_neg_dist). */
+int edgl_sample_negatives_alias(const int64_t* seen, int T, const int64_t* labels, int R, int n, int lo, int hi, int I,
+                                const uint32_t* thr_alias, uint64_t seed, uint64_t step, int row0, int32_t* cand, void* stream);
 /* edgl_rank_metrics_from_rank with the rows added to every sum one by one, in row order: the f32 sums of a split do not depend on
  * how it is cut into batches (the steps on candidate lists use it; a batch costs one lane-loop over its rows). */
 int edgl_rank_metrics_from_rank_rows(const int32_t* rank, int R, const int32_t* ks, int nk, float* sums, void* stream);
@@ -577,6 +585,12 @@ int edgl_rank_metrics_from_rank_rows(const int32_t* rank, int R, const int32_t* 
  * R (N + 1) < 2^31; I > 1; anything else is EDGL_ERR_SHAPE with the bound in the text. */
 int edgl_cand_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels, int R,
                      int C, int I, int N, float* vals, float* label_val, float* row_lse, int dtype, void* stream);
+/* edgl_cand_ce_fwd with the log-Q correction of a weighted sampler: logq f32 [I] (log of each id's draw probability,
+ * 0 where none is defined) — the label and every live slot read v - logq[c], one f32 subtraction on the finished value.  logq of
+ * zeros, or NULL, gives the bits of edgl_cand_ce_fwd (which forwards here with NULL).  edgl_cand_ce_bwd serves both. */
+int edgl_cand_ce_fwd_q(const void* rows, const void* table, const float* out_bias, const float* logq, const int32_t* cand,
+                       const int64_t* labels, int R, int C, int I, int N, float* vals, float* label_val, float* row_lse, int dtype,
+                       void* stream);
 int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
                      const float* vals, const float* row_lse, const float* coef, const float* gscale, int R, int C, int I, int N,
                      void* d_rows, float* dv, float* d_table, float* d_bias, int dtype, void* stream);
@@ -603,6 +617,11 @@ long edgl_shared_ce_workspace(int R, int C, int S, int dtype);
 int edgl_shared_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* shared, const int64_t* labels,
                        const int32_t* nvalid, int R, int C, int I, int S, float* vals, float* label_val, float* row_lse, int dtype,
                        void* stream);
+/* edgl_shared_ce_fwd with the log-Q correction: logq f32 [I] as in edgl_cand_ce_fwd_q; zeros or NULL give the bits
+ * of edgl_shared_ce_fwd (which forwards here with NULL).  edgl_shared_ce_bwd serves both. */
+int edgl_shared_ce_fwd_q(const void* rows, const void* table, const float* out_bias, const float* logq, const int32_t* shared,
+                         const int64_t* labels, const int32_t* nvalid, int R, int C, int I, int S, float* vals, float* label_val,
+                         float* row_lse, int dtype, void* stream);
 int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,
                        const float* label_val, const float* row_lse, const float* coef, const float* gscale, const int32_t* nvalid,
                        int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias, float* workspace, int64_t* keys,

@@ -21,6 +21,11 @@ TREE --sections baseline`), or from this tree when no parent is given — then, 
 step at N = 100, and the loss op alone (ops.SharedCEFn forward + backward, atomic and deterministic) beside its byte model: (R_w + S) C 4
 bytes of f32 atomics plus the [R, S] traffic (f32 values written and read, dv in bf16 written and read twice).  `--sections shared`
 replaces the part of --out from the section's heading on and keeps the rest.
+Sections `popularity` and `metrics` (`--sections popularity,metrics`, which keeps what stands in front of them):
+per shape the per-row step at N = 100 and the shared step at S = 1024 — the parent's (`--parent TREE`), this tree's with the flags
+unset and this tree's with FLAGS.neg_sampler = popularity (counts = bincount of the batch's Zipf ids) — then the uniform against
+the alias draw and the loss forward without / with the gathered logq; `metrics`: H10 / N10 on the synthetic Zipf task of
+tests/metric_parity.py after `--metric_steps` equal steps under uniform negatives, popularity with log-Q and popularity without.
 Needs a GPU: there is no fallback."""
 import argparse
 import os
@@ -44,6 +49,9 @@ LAZY_NEGATIVES = (10, 100)
 LAZY_HEADING = "lazy row-wise Adam for the item table (DESIGN 4.14)"
 SHARED_SIZES = (128, 1024, 8192)
 SHARED_HEADING = "one negative list per step, shared by every row (DESIGN 4.15)"
+POP_HEADING = "popularity-weighted negatives with the log-Q correction (DESIGN 4.16)"
+METRIC_HEADING = "ranking metrics under the three samplers (DESIGN 4.16)"
+POP_N, POP_S = 100, 1024
 HBM_RATE = 5.0e12         # bytes per second of streamed reads / writes (a round figure for the [R, S] traffic's floor)
 ATOMIC_RATE = 1.3e12      # bytes of f32 atomic adds per second, chip-wide
 
@@ -147,19 +155,26 @@ def baseline_section(args):
     each on stdout: what the `shared` section of another tree's run reads."""
     for name in args.models.split(","):
         for B, L, C, num_items in SHAPES:
-            for N, lazy in ((0, False), (100, False)) + (((100, True),) if name == "EasyDGL" else ()):
+            modes = ((0, False), (100, False)) + (((100, True),) if name == "EasyDGL" else ())
+            for N, lazy in ((POP_N, False),) if args.for_popularity else modes:
                 model, feats, labels = build(name, B, L, C, num_items, N, lazy)
                 ts = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
                 print("BASE", name, B, L, C, num_items, N, int(lazy), *(f"{t:.6f}" for t in ts), flush=True)
                 model = feats = labels = None
                 torch.cuda.empty_cache()
+            if args.for_popularity:      # (the shared step at S = POP_S, keyed as N = S with the mode field 2)
+                model, feats, labels = build(name, B, L, C, num_items, 0, False, POP_S)
+                ts = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                print("BASE", name, B, L, C, num_items, POP_S, 2, *(f"{t:.6f}" for t in ts), flush=True)
+                model = feats = labels = None
+                torch.cuda.empty_cache()
 
 
-def parent_baselines(args):
+def parent_baselines(args, for_popularity=False):
     """{(model, B, L, C, items, N, lazy): [ms per round]} of the tree args.parent names, measured by a fresh child process."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--tree", args.parent, "--sections", "baseline", "--rounds", str(args.rounds),
-           "--steps", str(args.steps), "--models", args.models]
+           "--steps", str(args.steps), "--models", args.models] + (["--for_popularity"] if for_popularity else [])
     out = subprocess.run(cmd, capture_output=True, text=True, check=True).stdout
     res = {}
     for ln in out.split("\n"):
@@ -230,8 +245,120 @@ def shared_section(args, lines):
             lines.append("")
 
 
+def set_popularity(model, feats):
+    """FLAGS.neg_sampler = popularity on a built model, the counts from the batch's own (Zipf) item ids."""
+    hi = model._negatives_hi()
+    ids = feats["seqs_i"].reshape(-1)
+    counts = torch.bincount(ids[(ids >= 0) & (ids < hi)], minlength=hi).cpu().numpy()
+    model.neg_sampler = "popularity"
+    model.set_negative_weights(ops.neg_weights("popularity", hi, 1, hi, counts, model.neg_alpha))
+
+
+def popularity_section(args, lines):
+    """per shape the per-row step at N = 100 and the shared step at S = 1024 — the parent's, this tree's with the flags
+    unset (the same launches) and this tree's with the popularity sampler; then the draw and the loss forward alone."""
+    src = "a checkout of the parent commit built from its own sources" if args.parent else "not measured (no --parent given)"
+    lines += [f"{POP_HEADING}: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} calls; bf16, dropout 0.1 / "
+              f"0.1; N = {POP_N} per row, S = {POP_S} shared; counts = bincount of the batch's item ids, alpha 0.75; parent: {src}", ""]
+    base = parent_baselines(args, True) if args.parent else {}
+    for name in args.models.split(","):
+        for B, L, C, num_items in SHAPES:
+            lines.append(f"{name}  {B} x {L} x {C}, {num_items} items")
+            for tag, N, S, key in ((f"N = {POP_N}", POP_N, 0, (POP_N, 0)), (f"S = {POP_S}", 0, POP_S, (POP_S, 2))):
+                model, feats, labels = build(name, B, L, C, num_items, N, False, S)
+                uni = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                set_popularity(model, feats)
+                pop = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                par = base.get((name, B, L, C, num_items) + key)
+                line = f"  {tag:9s} "
+                if par:
+                    mp, sp = statistics.median(par), max(par) - min(par)
+                    line += (f"parent {fmt(par)}  flags unset {fmt(uni)}  {statistics.median(uni) - mp:+.4f} ms of the parent's median "
+                             f"(its spread {sp:.4f}: {'within' if abs(statistics.median(uni) - mp) <= sp else 'OUTSIDE'})  ")
+                else:
+                    line += f"flags unset {fmt(uni)}  "
+                line += f"popularity {fmt(pop)}  {statistics.median(pop) - statistics.median(uni):+.4f} ms on the flags-unset step"
+                lines.append(line)
+                print(line, flush=True)
+                # the two additions alone: the draw, and the forward with the gathered logq
+                lab = labels.reshape(-1).contiguous()
+                rows = scored_rows(name, model, feats)
+                dist, hi = model._negative_dist(), model._negatives_hi()
+                tab = model.compute(model.item_embs.lookup_table)
+                logq = dist.logq_on(lab.device)
+                if N:
+                    du = rounds_of(lambda: ops.sample_negatives(None, lab, N, 1, hi, 0), args.rounds, args.steps)
+                    dw = rounds_of(lambda: ops.sample_negatives(None, lab, N, 1, hi, 0, dist=dist), args.rounds, args.steps)
+                    cand = ops.sample_negatives(None, lab, N, 1, hi, 0, dist=dist)
+                    fu = rounds_of(lambda: ops.cand_ce_fwd(rows, tab, model.output_bias, cand, lab), args.rounds, args.steps)
+                    fq = rounds_of(lambda: ops.cand_ce_fwd(rows, tab, model.output_bias, cand, lab, logq), args.rounds, args.steps)
+                else:
+                    one = torch.zeros(1, device=lab.device, dtype=torch.int64)
+                    du = rounds_of(lambda: ops.sample_negatives(None, one, S, 1, hi, 0), args.rounds, args.steps)
+                    dw = rounds_of(lambda: ops.sample_negatives(None, one, S, 1, hi, 0, dist=dist), args.rounds, args.steps)
+                    sh = ops.sample_negatives(None, one, S, 1, hi, 0, dist=dist).reshape(-1)
+                    fu = rounds_of(lambda: ops.shared_ce_fwd(rows, tab, model.output_bias, sh, lab), args.rounds, args.steps)
+                    fq = rounds_of(lambda: ops.shared_ce_fwd(rows, tab, model.output_bias, sh, lab, logq), args.rounds, args.steps)
+                line = (f"            draw: uniform {fmt(du)}  alias table ({(hi - 1) * 8 / 1e6:.1f} MB) {fmt(dw)}    loss forward on the "
+                        f"weighted lists: plain {fmt(fu)}  with logq ({logq.numel() * 4 / 1e6:.1f} MB) {fmt(fq)}")
+                lines.append(line)
+                print(line, flush=True)
+                model = feats = labels = rows = tab = None
+                torch.cuda.empty_cache()
+            lines.append("")
+
+
+def metrics_section(args, lines):
+    """H10 / N10 on the synthetic Zipf task of tests/metric_parity.py (full-catalogue ranking of held-out sequences, seen items
+    masked) after equal steps: uniform negatives, popularity with the log-Q correction, popularity without it."""
+    import numpy as np
+    from oracle import easydgl_oracle as O
+    from tests import metric_parity as MP
+    num_items, seqslen, batch, steps, n_eval, S = 400, 20, 128, args.metric_steps, 2048, 32
+    cfg = O.Config(num_items=num_items, seqslen=seqslen, num_units=32, num_heads=2, num_blocks=1, masklen=4, time_scale=86400.0,
+                   ct_reg=1e-3, l2_reg=1e-4, learning_rate=2e-3, num_events=4)
+    rng = np.random.default_rng(11)
+    params0 = O.init_params(cfg, rng)
+    mt = O.synthetic_mark_table(cfg.num_items, cfg.num_events, multi_hot=True)
+    tr_i, tr_t = MP.make_sequences(cfg, batch * steps, rng)
+    ev_i, ev_t = MP.make_sequences(cfg, n_eval, rng)
+    batches = [O.mask_random(cfg, tr_i[s * batch:(s + 1) * batch], tr_t[s * batch:(s + 1) * batch],
+                             O.draw_masked_positions(cfg, batch, rng)) for s in range(steps)]
+    efeats, elabels = O.mask_last(cfg, ev_i, ev_t)
+    lines += [f"{METRIC_HEADING}: EasyDGL f32, {num_items} items, {steps} steps of {batch} sequences, shared_negatives = {S}, "
+              f"full-catalogue ranking of {n_eval} held-out sequences; counts = bincount of the training ids, alpha 0.75", ""]
+    for tag in ("uniform", "popularity with log-Q", "popularity without log-Q"):
+        F = SimpleNamespace(model="EasyDGL", num_items=cfg.num_items, num_units=cfg.num_units, num_heads=cfg.num_heads,
+                            num_blocks=cfg.num_blocks, seqslen=cfg.seqslen, masklen=cfg.masklen, time_scale=cfg.time_scale,
+                            learning_rate=cfg.learning_rate, l2_reg=cfg.l2_reg, ct_reg=cfg.ct_reg, hidden_dropout_rate=0.0,
+                            attention_probs_dropout_rate=0.0, mark_table=mt, compute_dtype="f32", num_train_steps=None,
+                            num_warmup_steps=None, shared_negatives=S, train_neg_seed=1,
+                            neg_sampler="uniform" if tag == "uniform" else "popularity")
+        m = easydgl_amd.ranking(F).finalize("cuda")
+        m.load_tf_variables(params0)
+        if tag != "uniform":
+            hi = m._negatives_hi()
+            m.set_negative_weights(ops.neg_weights("popularity", hi, 1, hi, np.bincount(tr_i.reshape(-1), minlength=hi), 0.75))
+            if tag.endswith("without log-Q"):
+                m._negative_dist().logq[:] = 0.0         # (before the first draw: the device copy is made from this array)
+        for feats, labels in batches:
+            f = {k: torch.as_tensor(np.asarray(v)).cuda().contiguous() for k, v in feats.items()}
+            loss = m.train_step(f, torch.as_tensor(labels).cuda())
+        m.reset_metrics()
+        for lo in range(0, n_eval, 256):
+            ef = {k: torch.as_tensor(np.asarray(v[lo:lo + 256])).cuda().contiguous() for k, v in efeats.items()}
+            m.eval_step(ef, torch.as_tensor(elabels[lo:lo + 256]).cuda(), mask_seen=True)
+        got = m.metrics()
+        lines.append(f"  {tag:26s} H10 {got['H10']:.4f}  N10 {got['N10']:.4f}  H50 {got['H50']:.4f}  N50 {got['N50']:.4f}  last loss "
+                     f"{float(loss):.4f}")
+        print(lines[-1], flush=True)
+    lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--metric_steps", type=int, default=300, help="section metrics: training steps of every run")
+    ap.add_argument("--for_popularity", action="store_true", help="section baseline: the two steps the popularity section compares")
     ap.add_argument("--tree", default=None, help="run against the package of this checkout (read before the imports)")
     ap.add_argument("--parent", default=None, help="section shared: a checkout of the parent commit, library built, for the baselines")
     ap.add_argument("--rounds", type=int, default=5)
@@ -245,6 +372,23 @@ def main():
     sections = args.sections.split(",")
     if sections == ["baseline"]:
         return baseline_section(args)
+    if set(sections) <= {"popularity", "metrics"}:      # keep what stands in front of the first section asked for, replace the rest
+        lines = []
+        if os.path.exists(args.out):
+            old = open(args.out).read().split("\n")
+            head = POP_HEADING if "popularity" in sections else METRIC_HEADING
+            lines = old[:next((i for i, ln in enumerate(old) if ln.startswith(head)), len(old))]
+            while lines and not lines[-1]:
+                lines.pop()
+            lines.append("")
+        if "popularity" in sections:
+            popularity_section(args, lines)
+        if "metrics" in sections:
+            metrics_section(args, lines)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines))
+        print("wrote", args.out)
+        return
     if sections == ["shared"]:      # keep what stands in front of the shared section
         lines = []
         if os.path.exists(args.out):
