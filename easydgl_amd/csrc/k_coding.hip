@@ -1,5 +1,5 @@
 // Operator-level entry points of src/module/coding.py — the stand-alone forms of the classes whose arithmetic the
-// model kernels fuse (k_encode.hip, k_data.hip, k_tattn.hip):
+// model kernels fuse (k_encode.hip, k_data.hip, k_timefn.hip, k_tiattn.hip):
 //   Embedding.__call__            coding.py:60-64     edgl_embedding_fwd / edgl_embedding_bwd
 //   PositionCoding.code           coding.py:76-79     (the same gather, ids = 0..T-1 per row — built by the host wrapper)
 //   TimeIntervalCoding.code       coding.py:93-94     (the same gather on integer intervals)

@@ -3,7 +3,7 @@
 Same class names, constructor arguments and ``__call__`` / ``code`` methods as the reference.  On the model's hot path
 the arithmetic of Embedding / PositionCoding / TimeSinusoidCoding is fused into ONE kernel (``edgl_encode_fwd``, see
 ``easydgl_amd/model/easydgl.py``) and the time-function / interval codings are folded into the attention kernels
-(``csrc/k_tattn.hip``); called on their own, the methods below run the stand-alone HIP entry points of
+(``csrc/k_timefn.hip``, ``csrc/k_tiattn.hip``); called on their own, the methods below run the stand-alone HIP entry points of
 ``csrc/k_coding.hip`` (``edgl_embedding_fwd/bwd``, ``edgl_time_sinusoid``, ``edgl_time_function_fwd/bwd``).  ``compute`` is
 the hook the owning model installs to hand out the bf16 shadow of a parameter (identity in f32 mode)."""
 from __future__ import annotations
@@ -83,7 +83,7 @@ class TimeSinusoidCoding(nn.Module):
 
 class TimeFunctionCoding(nn.Module):
     """coding.py:104-122 (TGAT): ``basis_freq`` [C] = linspace(0, 9, C), ``phase`` [C] zeros; code(dt) = cos(dt * basis_freq +
-    phase).  On the attention path the [B,T,T,C] code tensor is never built (csrc/k_tattn.hip folds it into the operands)."""
+    phase).  On the attention path the [B,T,T,C] code tensor is never built (csrc/k_timefn.hip folds it into the operands)."""
 
     def __init__(self, num_units):
         super().__init__()

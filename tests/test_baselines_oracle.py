@@ -23,7 +23,7 @@ def _tgat_problem(seed=0, B=3, T=9, C=32, h=2, I=20, nb=2, time_scale=50.0):
 
 def test_tgat_time_term_equals_the_angle_difference_form_on_sorted_timestamps():
     """S = Q.(K+pos)^T + sum_d cos(dt w + phi) Q  ==  [Q|Q cos(a w+phi)|Q sin(a w+phi)] . [K+pos|cos(b w)|sin(b w)]^T wherever
-    dt = a - b >= 0 — every unmasked (k <= q) pair of a time-sorted sequence (the form csrc/k_tattn.hip computes)."""
+    dt = a - b >= 0 — every unmasked (k <= q) pair of a time-sorted sequence (the form csrc/k_timefn.hip computes)."""
     rng = np.random.default_rng(1)
     T, C = 7, 8
     Q, K, pos = (torch.tensor(rng.standard_normal((T, C))) for _ in range(3))
