@@ -189,6 +189,17 @@ SIGNATURES = {
     "edgl_tiattn_bwd_det": (I, [P, I, P, I, P, I, P, P, P, P, I, P, I, P, P, I, I, I, I, F, F, I, F, P, U32, P, I, P, I, P, I, P, P, P,
                                 P, I, I, P]),
     "edgl_add_pos2": (I, [P, P, P, I, I, I, P, I, P]),
+    "edgl_gru_seq_pack_bytes": (L, [I, I]),
+    "edgl_gru_seq_resident": (I, [I, I]),
+    "edgl_gru_seq_fwd": (I, [P, P, P, I, I, I, P, P, P, P, I, P]),
+    "edgl_gru_seq_bwd": (I, [P, P, P, I, I, I, P, P, P, I, P]),
+    "edgl_cat_pos_mask_fwd": (I, [P, P, P, I, I, I, P, I, P]),
+    "edgl_cat_pos_mask_bwd": (I, [P, P, I, I, I, P, P, I, P]),
+    "edgl_dict_feat_fwd": (I, [P, P, L, I, P, I, P]),
+    "edgl_dict_feat_bwd": (I, [P, P, P, L, I, P, P, I, P]),
+    "edgl_sigmoid_fwd": (I, [P, P, L, I, P]),
+    "edgl_sigmoid_bwd": (I, [P, P, P, L, I, P]),
+    "edgl_clip_scale": (I, [P, L, P, F, P]),
     "edgl_tail_pack_elems": (L, [I]),
     "edgl_tail_supported": (I, [I, I, I]),
     "edgl_tail_variant": (I, [I]),

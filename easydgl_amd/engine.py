@@ -64,6 +64,9 @@ class TrainEngine:
         if int(getattr(model, "shared_negatives", 0) or 0) > 0:
             raise _lib.EdglError("TrainEngine: the static engine scores the whole catalogue; a model with shared_negatives > 0 "
                                  "(sampled-softmax training, DESIGN 4.15) trains on the autograd path: model.train_step")
+        if not getattr(model, "static_engine_ok", True):
+            raise _lib.EdglError(f"TrainEngine: {type(model).__name__} is not run by the static engine (DESIGN 4.17: its step, with the "
+                                 "model's own Adam hyper-parameters and gradient clipping, is model.train_step / graphed_train_step)")
         # the environment switches (class docstring): read here, once, and nowhere else in the engine
         env = os.environ.get
         self.sw_flash_ce = env("EDGL_FLASH_CE", "1") != "0"

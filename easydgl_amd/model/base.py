@@ -46,6 +46,9 @@ class Sequential(nn.Module):
 
     tf_numpy = True     # tf_values() / tf_gradients() hand float32 numpy arrays out (EasyDGL: tensors on the parameters' device)
     lazy_adam_ok = False     # FLAGS.lazy_adam: only a model whose item backward ADDS into d_item (EasyDGL)
+    adam_hparams = (0.9, 0.999, 1e-8)     # (beta1, beta2, epsilon) of tf.train.AdamOptimizer (Base.py:142-144); S2PNM overrides
+    static_engine_ok = True  # engine.TrainEngine refuses a model that sets this to False (SASRec, S2PNM: DESIGN 4.17)
+    clip_norm = None         # clip_by_global_norm over the whole gradient arena in front of the update (S2PNM.py:87); None: off
 
     def __init__(self, num_items, FLAGS):
         super().__init__()
@@ -453,10 +456,12 @@ class Sequential(nn.Module):
         produced by autograd (ops.L2Fn), so no l2 is folded in here."""
         self.settle_state()
         self.mask_padded_grads()     # (channel-padded models; idempotent: every optimizer entry point keeps the padded entries at zero)
+        if self.clip_norm is not None:      # (a device scalar: no host synchronisation, graphed_train_step captures it)
+            ops.clip_by_global_norm(self._grad_arena, self.clip_norm)
         if self.lazy_adam:
             return self._lazy_optimizer_step()
         ops.adam_step(self._arena, self._grad_arena, self._adam_m, self._adam_v, self.learning_rate, self._adam_state,
-                      0.0, None, self._shadow)
+                      0.0, None, self._shadow, *self.adam_hparams)
 
     def _lazy_optimizer_step(self) -> None:
         """FLAGS.lazy_adam: the dense TF-form Adam on the arena ranges in front of and behind the item table — the
@@ -473,10 +478,10 @@ class Sequential(nn.Module):
             sh = None if self._shadow is None else self._shadow[a:b]
             if first:
                 ops.adam_step(self._arena[a:b], self._grad_arena[a:b], self._adam_m[a:b], self._adam_v[a:b], self.learning_rate,
-                              self._adam_state, 0.0, None, sh)
+                              self._adam_state, 0.0, None, sh, *self.adam_hparams)
             else:
                 ops.adam_apply(self._arena[a:b], self._grad_arena[a:b], self._adam_m[a:b], self._adam_v[a:b], self._adam_state,
-                               0.0, None, sh)
+                               0.0, None, sh, *self.adam_hparams)
             first = False
         if first:
             raise RuntimeError("lazy_adam: the arena holds nothing but the item table (no range advances the Adam step)")
@@ -486,7 +491,7 @@ class Sequential(nn.Module):
         pending, self._lazy_pending = self._lazy_pending, []
         for ids, labels, cand in pending:      # (one launch per train_loss call; a row named by several is claimed once per step)
             ops.adam_rows(tab.data, self._lazy_grad, self._adam_m[lo:lo + n].view(tab.shape), self._adam_v[lo:lo + n].view(tab.shape),
-                          shadow, ids, labels, cand, self._stamp, self._adam_state, self.l2_reg)
+                          shadow, ids, labels, cand, self._stamp, self._adam_state, self.l2_reg, *self.adam_hparams)
 
     # ---- Base.py:106-113 ---------------------------------------------------------------------------------
     def make_output_bias(self) -> nn.Parameter:

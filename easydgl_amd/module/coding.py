@@ -26,6 +26,18 @@ def glorot_uniform_(t: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
     return t
 
 
+def orthogonal_(t: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
+    """tf.orthogonal_initializer on a matrix: Q of the QR decomposition of a normal draw, columns signed by the diagonal of R
+    (so that the result is uniform over the orthogonal group), transposed where there are fewer rows than columns."""
+    rows, cols = t.shape
+    a = torch.randn((max(rows, cols), min(rows, cols)), generator=gen, dtype=torch.float64)
+    q, r = torch.linalg.qr(a)
+    q = q * torch.sign(torch.diagonal(r))
+    with torch.no_grad():
+        t.copy_((q if rows >= cols else q.t()).to(t.dtype))
+    return t
+
+
 class Embedding(nn.Module):
     """coding.py:45-64.  ``lookup_table`` is the RAW variable (l2-regularised incl. row 0, coding.py:53-55);
     with ``zero_pad`` row 0 acts as a zero constant wherever the table is used (coding.py:56-57)."""

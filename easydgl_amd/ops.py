@@ -1582,6 +1582,201 @@ class TiAttnFn(torch.autograd.Function):
 
 
 
+class EmbedCatFn(torch.autograd.Function):
+    """X0 = dropout(concat(item[ids] * sqrt(C), pos[0..T))) without time spans or marks (SASREC.py:43-49): edgl_embed_pos_* with
+    no timestamps and no mark table.  The position half is NOT zero on padding: the caller masks the rows."""
+
+    @staticmethod
+    def forward(ctx, item_master, pos_tab, item_c, ids, drop: Drop, act_dtype, deterministic=False):
+        B, T = ids.shape
+        I, C = item_c.shape
+        x0 = torch.empty((B, T, 2 * C), device=ids.device, dtype=act_dtype)
+        check(lib.edgl_embed_pos_fwd_ct(_ptr(ids), None, _ptr(item_c), _ptr(pos_tab), None, B, T, C, 0, 1.0, float(drop.rate),
+                                        drop.ptr(), drop.stream_id, _ptr(x0), None, None, 0, _DT[act_dtype], _stream()),
+              "edgl_embed_pos_fwd")
+        ctx.save_for_backward(ids)
+        ctx.deterministic = bool(deterministic)
+        ctx.meta = (B, T, C, I, drop, item_master.shape, pos_tab.shape)
+        return x0
+
+    @staticmethod
+    def backward(ctx, dx0):
+        (ids,) = ctx.saved_tensors
+        B, T, C, I, drop, ishape, pshape = ctx.meta
+        dx0 = dx0.contiguous()
+        d_item = torch.empty(ishape, device=dx0.device, dtype=torch.float32)
+        d_pos = torch.zeros(pshape, device=dx0.device, dtype=torch.float32)
+        _embed_pos_bwd(ctx.deterministic, ids, dx0, B, T, C, I, drop, d_item, d_pos, 0)
+        return (d_item, d_pos) + (None,) * 5
+
+
+class PlainAttnFn(torch.autograd.Function):
+    """MultiHeadAttention after its dense layers (sequential.py:39-78): q [B,T,C], kv [B,T,2C] (K | V column blocks), resid = the
+    first C channels of the queries (a row-strided view); the plain-head case Dq == Dv of edgl_tattn_*."""
+
+    @staticmethod
+    def forward(ctx, q, kv, resid, ids, H, drop: Drop, causal=True):
+        B, T, C = q.shape
+        dh = C // H
+        q, kv = q.contiguous(), kv.contiguous()
+        if resid.stride(-1) != 1 or resid.stride(0) != T * resid.stride(1):
+            raise _lib.EdglError("attention residual must be a row-strided view of a contiguous [B,T,*] tensor")
+        if ids.dtype != torch.int64 or tuple(ids.shape) != (B, T) or not ids.is_contiguous():
+            raise _lib.EdglError(f"attention key ids must be a contiguous int64 [B={B}, T={T}] tensor, got {tuple(ids.shape)} {ids.dtype}")
+        code = _code(q)
+        flags = _lib.TATTN_CAUSAL if causal else 0
+        out = torch.empty((B, T, C), device=q.device, dtype=q.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty(int(lib.edgl_tattn_saved_bytes(B, T, H, dh)), device=q.device, dtype=torch.uint8) if need else None
+        scale = 1.0 / float(dh) ** 0.5                                                   # sequential.py:47
+        check(lib.edgl_tattn_fwd(_ptr(q), C, _ptr(kv), 2 * C, _vptr(kv[:, :, C:]), 2 * C, _vptr(resid), resid.stride(1), _ptr(ids), B,
+                                 T, H, dh, dh, scale, float(drop.rate), drop.ptr(), drop.stream_id, _ptr(out), C, _ptr(saved), flags,
+                                 code, _stream()), "edgl_tattn_fwd")
+        ctx.save_for_backward(q, kv, ids, saved)
+        ctx.meta = (B, T, C, H, dh, scale, drop, flags)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q, kv, ids, saved = ctx.saved_tensors
+        B, T, C, H, dh, scale, drop, flags = ctx.meta
+        d_out = d_out.contiguous()
+        d_q, d_kv = torch.empty_like(q), torch.empty_like(kv)
+        check(lib.edgl_tattn_bwd(_ptr(q), C, _ptr(kv), 2 * C, _vptr(kv[:, :, C:]), 2 * C, _ptr(ids), _ptr(d_out), C, _ptr(saved), B, T,
+                                 H, dh, dh, scale, float(drop.rate), drop.ptr(), drop.stream_id, _ptr(d_q), C, _ptr(d_kv), 2 * C,
+                                 _vptr(d_kv[:, :, C:]), 2 * C, flags, _code(q), _stream()), "edgl_tattn_bwd")
+        return d_q, d_kv, d_out, None, None, None, None
+
+
+class GruSeqFn(torch.autograd.Function):
+    """The GRU recurrence over xp = x W + b_W (edgl_gru_seq_fwd / bwd): h [B,T,C] from xp [B,T,3C], R [C,3C] (r_c: its
+    compute copy), b_R [3C].  Gate order r | z | n, cuDNN's form, zero initial state.  The backward carries dh in f32 through the
+    recurrence and returns d_xp; dR = H_prev^T dG_h and db_R are one dense_grads call over the B*T rows.  No atomics anywhere:
+    the same bits in every call, so FLAGS.deterministic needs no second form."""
+
+    @staticmethod
+    def forward(ctx, xp, r_master, r_bias, r_c):
+        B, T, C3 = xp.shape
+        C = C3 // 3
+        xp = xp.contiguous()
+        code = _code(xp)
+        if r_c.dtype != xp.dtype or tuple(r_c.shape) != (C, C3) or tuple(r_bias.shape) != (C3,) or r_bias.dtype != torch.float32:
+            raise _lib.EdglError(f"GruSeqFn: R must be {xp.dtype} [{C}, {C3}] and b_R f32 [{C3}] (got {r_c.dtype} {tuple(r_c.shape)}, "
+                                 f"{r_bias.dtype} {tuple(r_bias.shape)})")
+        nbytes = int(lib.edgl_gru_seq_pack_bytes(C, code))
+        if nbytes <= 0:
+            raise _lib.EdglError(f"GruSeqFn: width C={C} unsupported (a multiple of 16 in [16, 512])")
+        pack = torch.empty(nbytes, device=xp.device, dtype=torch.uint8)
+        h = torch.empty((B, T, C), device=xp.device, dtype=xp.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty((B, T, 5 * C), device=xp.device, dtype=torch.float32) if need else None
+        # the A operand of dR: in f32 mode the h_prev block of `saved` itself, else a copy in the activation dtype
+        hprev = torch.empty((B, T, C), device=xp.device, dtype=xp.dtype) if need and xp.dtype != torch.float32 else None
+        check(lib.edgl_gru_seq_fwd(_ptr(xp), _ptr(r_c), _ptr(r_bias), B, T, C, _ptr(h), _ptr(saved), _ptr(hprev), _ptr(pack), code,
+                                   _stream()), "edgl_gru_seq_fwd")
+        ctx.save_for_backward(r_c, saved, hprev)
+        ctx.meta = (B, T, C, code)
+        return h
+
+    @staticmethod
+    def backward(ctx, d_h):
+        r_c, saved, hprev = ctx.saved_tensors
+        B, T, C, code = ctx.meta
+        d_h = d_h.contiguous()
+        d_xp = torch.empty((B, T, 3 * C), device=d_h.device, dtype=d_h.dtype)
+        d_gh = torch.empty_like(d_xp)
+        pack = torch.empty(int(lib.edgl_gru_seq_pack_bytes(C, code)), device=d_h.device, dtype=torch.uint8)
+        check(lib.edgl_gru_seq_bwd(_ptr(d_h), _ptr(r_c), _ptr(saved), B, T, C, _ptr(d_xp), _ptr(d_gh), _ptr(pack), code, _stream()),
+              "edgl_gru_seq_bwd")
+        hp = saved.view(B * T, 5 * C)[:, 4 * C:] if hprev is None else hprev.view(B * T, C)      # (row stride 5C / C)
+        M, N = B * T, 3 * C
+        both = torch.empty((C + 1) * N, device=d_h.device, dtype=torch.float32)
+        ws = torch.empty(lib.edgl_gemm_dw_workspace(M, C, N, code), device=d_h.device, dtype=torch.float32)
+        check(lib.edgl_gemm_dw(_vptr(hp), _ptr(d_gh), _ptr(both), both.data_ptr() + 4 * C * N, M, C, N, hp.stride(0), N, 0, _ptr(ws), code,
+                               _stream()), "edgl_gemm_dw")
+        return d_xp, both[:C * N].view(C, N), both[C * N:], None
+
+
+class CatPosMaskFn(torch.autograd.Function):
+    """[h | pos[0..T)] * (ids != 0) (S2PNM.py:52-53; PositionCoding concatenates): edgl_cat_pos_mask_fwd / bwd.  d_pos is summed over
+    b in a fixed order, without atomics."""
+
+    @staticmethod
+    def forward(ctx, h, pos_tab, ids):
+        B, T, C = h.shape
+        h = h.contiguous()
+        out = torch.empty((B, T, 2 * C), device=h.device, dtype=h.dtype)
+        check(lib.edgl_cat_pos_mask_fwd(_ptr(h), _ptr(pos_tab), _ptr(ids), B, T, C, _ptr(out), _code(h), _stream()), "edgl_cat_pos_mask_fwd")
+        ctx.save_for_backward(ids)
+        ctx.meta = (B, T, C, pos_tab.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (ids,) = ctx.saved_tensors
+        B, T, C, pshape = ctx.meta
+        d_out = d_out.contiguous()
+        d_h = torch.empty((B, T, C), device=d_out.device, dtype=d_out.dtype)
+        d_pos = torch.zeros(pshape, device=d_out.device, dtype=torch.float32)      # (rows past T, if any, stay zero)
+        check(lib.edgl_cat_pos_mask_bwd(_ptr(d_out), _ptr(ids), B, T, C, _ptr(d_h), _ptr(d_pos), _code(d_out), _stream()),
+              "edgl_cat_pos_mask_bwd")
+        return d_h, d_pos, None
+
+
+class DictFeatFn(torch.autograd.Function):
+    """[g, h, g - h, g * h] along the channels (S2PNM.py:63): edgl_dict_feat_fwd / bwd."""
+
+    @staticmethod
+    def forward(ctx, g, h):
+        g, h = g.contiguous(), h.contiguous()
+        C = g.shape[-1]
+        rows = g.numel() // C
+        out = torch.empty(g.shape[:-1] + (4 * C,), device=g.device, dtype=g.dtype)
+        check(lib.edgl_dict_feat_fwd(_ptr(g), _ptr(h), rows, C, _ptr(out), _code(g), _stream()), "edgl_dict_feat_fwd")
+        ctx.save_for_backward(g, h)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        g, h = ctx.saved_tensors
+        d_out = d_out.contiguous()
+        C = g.shape[-1]
+        d_g, d_h = torch.empty_like(g), torch.empty_like(h)
+        check(lib.edgl_dict_feat_bwd(_ptr(g), _ptr(h), _ptr(d_out), g.numel() // C, C, _ptr(d_g), _ptr(d_h), _code(g), _stream()),
+              "edgl_dict_feat_bwd")
+        return d_g, d_h
+
+
+class SigmoidFn(torch.autograd.Function):
+    """y = sigmoid(x) (the activation of tf.layers.dense(..., tf.nn.sigmoid), S2PNM.py:64): edgl_sigmoid_fwd / bwd."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        check(lib.edgl_sigmoid_fwd(_ptr(x), _ptr(y), x.numel(), _code(x), _stream()), "edgl_sigmoid_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        check(lib.edgl_sigmoid_bwd(_ptr(dy), _ptr(y), _ptr(dx), dy.numel(), _code(dy), _stream()), "edgl_sigmoid_bwd")
+        return dx
+
+
+def clip_by_global_norm(grad: torch.Tensor, clip: float) -> None:
+    """grad (the flat f32 gradient arena) *= clip / max(||grad||, clip), in place: tf.clip_by_global_norm over every gradient.  The
+    sum of squares and the factor stay on the device (edgl_l2_loss with l2 = 2, edgl_clip_scale): no host read, graph-capturable."""
+    seg = _whole_segment(grad.numel(), grad.device)
+    sumsq = torch.empty(1, device=grad.device, dtype=torch.float32)
+    ws = torch.empty(1024, device=grad.device, dtype=torch.float32)
+    check(lib.edgl_l2_loss(_ptr(grad), _ptr(seg), 1, 2.0, _ptr(sumsq), 0, _ptr(ws), _stream()), "edgl_l2_loss")
+    check(lib.edgl_clip_scale(_ptr(grad), grad.numel(), _ptr(sumsq), float(clip), _stream()), "edgl_clip_scale")
+
+
 class FFTailFn(torch.autograd.Function):
     """FeedForward tail: (dropout(a) + b) * (ids != 0) in one kernel (edgl_ff_tail); ids None = no row mask."""
 

@@ -1,7 +1,7 @@
 """Train / evaluate driver — the role of the reference's ``src/main.py:78-151`` with ``util.EarlyStopping``
 (``src/util.py:14-58``), on the HIP model.
 
-Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC (regressive batches,
+Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM (regressive batches,
 ``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``).
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
 ``--num_items --num_units --num_heads --num_blocks --seqslen --time_scale --masklen --mark --ct_reg --batch_size
@@ -34,7 +34,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT or TiSASREC (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC or S2PNM (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512

@@ -15,4 +15,10 @@ def ranking(FLAGS):
     if FLAGS.model == "CTSMA":
         from .model import CTSMA
         return CTSMA(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "SASREC":
+        from .model import SASRec
+        return SASRec(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "S2PNM":
+        from .model import S2PNM
+        return S2PNM(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

@@ -1053,6 +1053,45 @@ int edgl_tail_bwd_ct(const void* xin, int ld_x, const void* ao, const void* a1, 
                      void* d_res1, void* d_att, float* dg1, float* db1, float* dg2, float* db2, float* dg3, float* db3,
                      float* workspace, int dh_pad, int dh_true, int dtype, void* stream);
 
+/* ---- GRU sequence recurrence (S2PNM's recurrent layer) -------------------------------------
+ * One unidirectional GRU layer in cuDNN's form (gate order r, z, n; linear input; zero initial state; every position is a step):
+ *   r = s(xp_r + h R_r + b_Rr)   z = s(xp_z + h R_z + b_Rz)   n = tanh(xp_n + r * (h R_n + b_Rn))   h' = (1 - z) n + z h
+ * xp [B,T,3C] `dtype` = x [W_r|W_z|W_n] + b_W (a plain edgl_gemm), R [C,3C] `dtype` (gate blocks as column blocks), b_R f32 [3C].
+ * edgl_gru_seq_fwd: h [B,T,C] `dtype`; saved f32 [B,T,5C] = r | z | n | h R_n + b_Rn | h_prev per position (NULL: inference);
+ * hprev_c [B,T,C] `dtype` (may be NULL) = the state BEFORE each step, the A operand of dR = H_prev^T dG_h (in f32 mode the
+ * h_prev block of `saved` is that operand already, row stride 5C).  `pack`: edgl_gru_seq_pack_bytes(C, dtype) bytes, 16-byte
+ * aligned, written by the call (R as MFMA fragments).
+ * edgl_gru_seq_bwd: d_h [B,T,C] -> d_xp [B,T,3C] (gradient of xp) and d_gh [B,T,3C] (gradient of h R + b_R: the n block times r);
+ * dh is carried in f32; dR = H_prev^T d_gh and db_R = colsum(d_gh) are ONE edgl_gemm_dw over the B*T rows afterwards.
+ * One workgroup owns 16 samples for all T steps; no atomics: the same bits in every call.  C a multiple of 16 in [16, 512],
+ * B >= 1, T >= 1; anything else is EDGL_ERR_SHAPE before a launch.  edgl_gru_seq_resident: 1 if R stays in LDS for the whole
+ * launch at this width (bf16: C <= 128, f32: C <= 80), 0 if it is streamed from L2 every step, -1 for a bad shape. */
+long edgl_gru_seq_pack_bytes(int C, int dtype);
+int edgl_gru_seq_resident(int C, int dtype);
+int edgl_gru_seq_fwd(const void* xp, const void* R, const float* b_R, int B, int T, int C, void* h, float* saved,
+                     void* hprev_c, void* pack, int dtype, void* stream);
+int edgl_gru_seq_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* d_gh,
+                     void* pack, int dtype, void* stream);
+
+/* ---- S2PNM's element-wise pieces (S2PNM.py:52-66) and gradient clipping (k_s2pnm.hip) -----------------
+ * edgl_cat_pos_mask_fwd: out [B,T,2C] = [h[b,t] | pos[t]] * (ids[b,t] != 0); h `dtype` [B,T,C], pos f32 [>=T, C].
+ * edgl_cat_pos_mask_bwd: d_h [B,T,C] = d_out[:, :, :C] * mask; d_pos f32 [T,C] (overwritten) = sum over b, in ascending b, of the
+ *   masked d_out[:, :, C:] — one thread per element, no atomics.
+ * edgl_dict_feat_fwd: out [rows,4C] = [g, h, g - h, g * h]; edgl_dict_feat_bwd: d_g = d0 + d2 + d3 * h, d_h = d1 - d2 + d3 * g.
+ * edgl_sigmoid_fwd: y = 1 / (1 + exp(-x)); edgl_sigmoid_bwd: dx = dy * y * (1 - y).
+ * edgl_clip_scale: grad[0..n) *= clip / max(sqrt(sumsq[0]), clip) with sumsq a DEVICE scalar (edgl_l2_loss of the gradient
+ *   with l2 = 2): clip_by_global_norm without a host read; the factor is exactly 1 while the norm is below the clip. */
+int edgl_cat_pos_mask_fwd(const void* h, const float* pos, const int64_t* ids, int B, int T, int C, void* out, int dtype,
+                          void* stream);
+int edgl_cat_pos_mask_bwd(const void* d_out, const int64_t* ids, int B, int T, int C, void* d_h, float* d_pos, int dtype,
+                          void* stream);
+int edgl_dict_feat_fwd(const void* g, const void* h, long rows, int C, void* out, int dtype, void* stream);
+int edgl_dict_feat_bwd(const void* g, const void* h, const void* d_feat, long rows, int C, void* d_g, void* d_h, int dtype,
+                       void* stream);
+int edgl_sigmoid_fwd(const void* x, void* y, long n, int dtype, void* stream);
+int edgl_sigmoid_bwd(const void* dy, const void* y, void* dx, long n, int dtype, void* stream);
+int edgl_clip_scale(float* grad, long n, const float* sumsq, float clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
