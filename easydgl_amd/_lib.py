@@ -200,6 +200,16 @@ SIGNATURES = {
     "edgl_sigmoid_fwd": (I, [P, P, L, I, P]),
     "edgl_sigmoid_bwd": (I, [P, P, P, L, I, P]),
     "edgl_clip_scale": (I, [P, L, P, F, P]),
+    "edgl_mate_saved_floats": (I, [I, I, I, I]),
+    "edgl_mate_fwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, I, P]),
+    "edgl_mate_bwd_workspace": (L, [I, I, I, I, I, I, I]),
+    "edgl_mate_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, I, P]),
+    "edgl_tahe_fwd": (I, [P, P, I, I, I, P, I, P]),
+    "edgl_tahe_bwd": (I, [P, P, P, I, I, I, P, P, I, P]),
+    "edgl_tahe_mix_fwd": (I, [P, P, P, P, L, I, P, I, P]),
+    "edgl_cat3": (I, [P, P, P, L, I, P, I, I, P]),
+    "edgl_tahe_mix_bwd_workspace": (L, [L]),
+    "edgl_tahe_mix_bwd": (I, [P, P, P, L, I, P, P, P, I, P]),
     "edgl_tail_pack_elems": (L, [I]),
     "edgl_tail_supported": (I, [I, I, I]),
     "edgl_tail_variant": (I, [I]),

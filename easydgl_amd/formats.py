@@ -261,10 +261,65 @@ def load_mark_table(path: str, num_items: int = None) -> np.ndarray:
     return np.ascontiguousarray(tab.astype(np.uint8))
 
 
-def convert(patterns, seqslen: int, out_npz: str, verify: bool = True) -> Tuple[int, int]:
-    """One-time TFRecord -> ``.npz`` conversion (``seqs_i`` int64, ``seqs_t`` float32)."""
+CALENDAR_FIELDS = ("seqs_month", "seqs_day", "seqs_weekday", "seqs_hour")
+
+
+def load_calendar(patterns, seqslen: int, verify: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The four calendar fields of every record of the matching files, int64 ``[N, seqslen+1]`` each, in the order of
+    ``CALENDAR_FIELDS`` (month 1-12, day 1-31, weekday Monday = 0, hour 0-23; 0 in every field at padding) — what TimelyREC reads
+    (``RegressivePostProcessor(has_datetime=True)``).  Record order is ``load_sequences``'s.  A file without the fields raises
+    ``KeyError``: ``calendar_from_timestamps`` derives them."""
+    T = seqslen + 1
+    cols: List[List[np.ndarray]] = [[] for _ in CALENDAR_FIELDS]
+    for path in expand(patterns):
+        if path.endswith(".npz"):
+            z = np.load(path)
+            for col, name in zip(cols, CALENDAR_FIELDS):
+                if name not in z.files:
+                    raise KeyError(f"{path}: no calendar field {name}")
+                a = z[name].astype(np.int64)
+                if a.ndim != 2 or a.shape[1] != T:
+                    raise ValueError(f"{path}: {name} has shape {a.shape}, the model expects seqslen+1 = {T} positions")
+                col.append(a)
+            continue
+        for rec in read_tfrecord(path, verify=verify):
+            ex = parse_example(rec)
+            for col, name in zip(cols, CALENDAR_FIELDS):
+                if name not in ex:
+                    raise KeyError(f"{path}: record without calendar field {name}")
+                a = ex[name]
+                if a.shape[0] != T:
+                    raise ValueError(f"{path}: record with {a.shape[0]} values of {name}, expected {T}")
+                col.append(a[None].astype(np.int64))
+    return tuple(np.concatenate(col, 0) for col in cols)
+
+
+def calendar_from_timestamps(ts, ids=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """(month, day, weekday, hour) int64 arrays of the shape of ``ts`` from epoch seconds read as UTC (numpy ``datetime64``): month
+    1-12, day 1-31, weekday Monday = 0, hour 0-23 — the fields pandas' datetime accessors give the reference's data scripts.
+    ``ids`` (same shape): every field is 0 where the token is padding (id 0), as in the reference's files.  For data sets whose
+    records carry no calendar fields."""
+    sec = np.floor(np.asarray(ts, dtype=np.float64)).astype(np.int64)
+    t = sec.astype("datetime64[s]")
+    months = t.astype("datetime64[M]")
+    days = t.astype("datetime64[D]")
+    month = months.astype(np.int64) % 12 + 1
+    day = (days - months.astype("datetime64[D]")).astype(np.int64) + 1
+    weekday = (days.astype(np.int64) + 3) % 7           # 1970-01-01 was a Thursday
+    hour = (t - days.astype("datetime64[s]")).astype(np.int64) // 3600
+    out = [month, day, weekday, hour]
+    if ids is not None:
+        keep = (np.asarray(ids) != 0).astype(np.int64)
+        out = [a * keep for a in out]
+    return tuple(a.astype(np.int64) for a in out)
+
+
+def convert(patterns, seqslen: int, out_npz: str, verify: bool = True, calendar: bool = False) -> Tuple[int, int]:
+    """One-time TFRecord -> ``.npz`` conversion (``seqs_i`` int64, ``seqs_t`` float32).  ``calendar``: the four calendar fields
+    (``CALENDAR_FIELDS``, int64) are written as well."""
     ids, ts = load_sequences(patterns, seqslen, verify=verify)
-    np.savez_compressed(out_npz, seqs_i=ids, seqs_t=ts)
+    extra = dict(zip(CALENDAR_FIELDS, load_calendar(patterns, seqslen, verify=verify))) if calendar else {}
+    np.savez_compressed(out_npz, seqs_i=ids, seqs_t=ts, **extra)
     return ids.shape
 
 
@@ -274,5 +329,6 @@ if __name__ == "__main__":
     ap.add_argument("--input", required=True, help="file pattern(s), comma separated")
     ap.add_argument("--seqslen", type=int, required=True)
     ap.add_argument("--output", required=True)
+    ap.add_argument("--calendar", action="store_true", help="also write seqs_month / seqs_day / seqs_weekday / seqs_hour (TimelyREC)")
     a = ap.parse_args()
-    print("converted", convert(a.input, a.seqslen, a.output))
+    print("converted", convert(a.input, a.seqslen, a.output, calendar=a.calendar))

@@ -1,6 +1,7 @@
 """Mirror of src/module/sequential.py: MultiHeadAttention (Vaswani et al., the unit of SASRec) on the generic masked attention
 kernel in its plain-head form (Dq == Dv, csrc/k_tattn.hip), and the GRU layer S2PNM puts in front of it (the reference's
-compat/cudnn_rnn.py CudnnGRU) on the recurrence kernel csrc/k_gru.hip."""
+compat/cudnn_rnn.py CudnnGRU) on the recurrence kernel csrc/k_gru.hip; TimelyREC's MATEncoder and TAHEncoder on csrc/k_mate.hip
+and csrc/k_tahe.hip."""
 from __future__ import annotations
 
 import torch
@@ -43,6 +44,48 @@ class MultiHeadAttention(nn.Module):
         kv = ops.LinearFn.apply(keys, self.kv_kernel, self.kv_bias, self.compute(self.kv_kernel), False)
         return ops.PlainAttnFn.apply(q, kv, queries[:, :, :C], ids, self.num_heads, drop if is_training else ops.NO_DROP,
                                      bool(causality))
+
+
+class MATEncoder(nn.Module):
+    """sequential.py:210-237, the multi-aspect time encoder of TimelyREC for its four calendar granularities at once.  The
+    reference builds one encoder per granularity and hands it materialised slots; here the slots are never built: ``kernel``
+    [C, 4C] holds the four bias-free user projections (``month_mate`` | ``daymate`` | ``weekday_mate`` | ``hour_mate`` as column
+    blocks: one GEMM) and the slot attention runs inside csrc/k_mate.hip together with the gated combination of TimelyREC.py:126-135
+    (``combine`` [C, C], bias-free).
+
+    ``forward(idx, tables, users)``: idx int64 [4,B,T] (month - 1 | day - 1 | weekday | hour), tables = the four
+    coding.Embedding modules, users [B,T,C] -> the combined period information [B,T,C]."""
+
+    def __init__(self, num_units, window_ratio=0.2, gen=None):
+        super().__init__()
+        if not 0.0 < float(window_ratio) <= 0.5:
+            raise ValueError(f"MATEncoder: window_ratio={window_ratio} unsupported; the HIP kernel takes 0 < window_ratio <= 0.5 "
+                             "(--window_ratio)")
+        self.num_units, self.window_ratio = num_units, float(window_ratio)
+        self.windows = ops.mate_windows(window_ratio)
+        self.kernel = nn.Parameter(torch.cat([glorot_uniform_(torch.empty(num_units, num_units), gen) for _ in range(4)], dim=1))
+        self.combine = nn.Parameter(glorot_uniform_(torch.empty(num_units, num_units), gen))
+        self.register_buffer("no_bias", torch.zeros(4 * num_units), persistent=False)     # (tf.layers.dense(use_bias=False))
+        self.compute = lambda p: p  # replaced by the owning model (bf16 shadow lookup)
+
+    def forward(self, idx, tables, users):
+        C = self.num_units
+        u = ops.LinearFn.apply(users, self.kernel, self.no_bias, self.compute(self.kernel), False)
+        pq = ops.LinearFn.apply(users, self.combine, self.no_bias[:C], self.compute(self.combine), False)
+        masters = [t.lookup_table for t in tables]
+        return ops.MateFn.apply(idx, *masters, *[self.compute(m) for m in masters], u, pq, self.windows)
+
+
+class TAHEncoder(nn.Module):
+    """sequential.py:240-265, the time-aware history encoder of TimelyREC: ``forward(queries, keys, histories)`` with the
+    reference's arguments.  The reference calls it with the same tensor twice (TimelyREC.py:147, "queries and keys are
+    identical"), and that is the only form the kernel (csrc/k_tahe.hip) takes: the l2 normalisation, the cosine weights
+    (1 + cos) / 2 under the causal mask (diagonal kept) and the weighted sum of the histories."""
+
+    def forward(self, queries, keys, histories):
+        if keys is not queries:
+            raise ValueError("TAHEncoder: the HIP kernel takes queries is keys (TimelyREC.py:147)")
+        return ops.TaheFn.apply(queries, histories)
 
 
 class GRU(nn.Module):

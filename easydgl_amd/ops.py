@@ -1767,6 +1767,152 @@ class SigmoidFn(torch.autograd.Function):
         return dx
 
 
+# ------------------------------------------------------------------------------------------------
+# TimelyREC: the multi-aspect time encoder and the time-aware history encoder
+# ------------------------------------------------------------------------------------------------
+MATE_RANGES = (12, 31, 7, 24)      # month, day, weekday, hour
+
+
+def mate_windows(window_ratio: float):
+    """TimelyREC.py:59: W_g = max(int(M_g * window_ratio + 0.5), 1) + 1 for month, day, weekday, hour."""
+    return tuple(max(int(m * float(window_ratio) + 0.5), 1) + 1 for m in MATE_RANGES)
+
+
+def _seq3(name, t, B, T, C, dtype):
+    if not t.is_cuda:
+        raise _lib.EdglError("easydgl_amd ops run on the GPU only (got a CPU tensor); there is no CPU fallback")
+    if t.dtype != dtype or tuple(t.shape) != (B, T, C) or not t.is_contiguous():
+        raise _lib.EdglError(f"{name} must be a contiguous {dtype} [{B}, {T}, {C}] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+class MateFn(torch.autograd.Function):
+    """Calendar slots, slot attention and the gated combination of TimelyREC (TimelyREC.py:57-77,108-135; edgl_mate_fwd / bwd):
+    R [B,T,C] from idx int64 [4,B,T] (month - 1 | day - 1 | weekday | hour), the four tables (masters f32 and compute copies), u
+    [B,T,4C] = U [Wu_month | Wu_day | Wu_weekday | Wu_hour] and pq [B,T,C] = U Wc.  `windows`: mate_windows(window_ratio).  Saved:
+    the slot probabilities and the gates; the backward recomputes the slots and returns d_u, d_pq and the table gradients, summed
+    in a fixed order (no atomics): FLAGS.deterministic needs no second form."""
+
+    @staticmethod
+    def forward(ctx, idx, month, day, weekday, hour, month_c, day_c, weekday_c, hour_c, u, pq, windows):
+        B, T, C = pq.shape
+        u, pq = u.contiguous(), pq.contiguous()
+        code = _code(pq)
+        _seq3("MateFn: u", u, B, T, 4 * C, pq.dtype)
+        if idx.dtype != torch.int64 or tuple(idx.shape) != (4, B, T) or not idx.is_contiguous():
+            raise _lib.EdglError(f"MateFn: idx must be a contiguous int64 [4, {B}, {T}] tensor, got {idx.dtype} {tuple(idx.shape)}")
+        tabs = (month_c, day_c, weekday_c, hour_c)
+        for t, m in zip(tabs, MATE_RANGES):
+            if t.dtype != pq.dtype or tuple(t.shape) != (m, C):
+                raise _lib.EdglError(f"MateFn: a calendar table must be {pq.dtype} [{m}, {C}], got {t.dtype} {tuple(t.shape)}")
+        w = tuple(int(x) for x in windows)
+        nsv = int(lib.edgl_mate_saved_floats(*w))
+        if nsv <= 0:
+            raise _lib.EdglError(f"MateFn: windows {w} unsupported (window_ratio in (0, 0.5])")
+        R = torch.empty((B, T, C), device=pq.device, dtype=pq.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty((B, T, nsv), device=pq.device, dtype=torch.float32) if need else None
+        check(lib.edgl_mate_fwd(_ptr(idx), *[_ptr(t) for t in tabs], _ptr(u), _ptr(pq), B, T, C, *w, _ptr(R), _ptr(saved), code,
+                                _stream()), "edgl_mate_fwd")
+        ctx.save_for_backward(idx, month_c, day_c, weekday_c, hour_c, u, pq, saved)
+        ctx.meta = (B, T, C, w, code)
+        return R
+
+    @staticmethod
+    def backward(ctx, d_R):
+        idx, month_c, day_c, weekday_c, hour_c, u, pq, saved = ctx.saved_tensors
+        B, T, C, w, code = ctx.meta
+        d_R = d_R.contiguous()
+        d_u, d_pq = torch.empty_like(u), torch.empty_like(pq)
+        d_tab = torch.empty((sum(MATE_RANGES), C), device=pq.device, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_mate_bwd_workspace(B, T, C, *w)), device=pq.device, dtype=torch.float32)
+        check(lib.edgl_mate_bwd(_ptr(idx), _ptr(month_c), _ptr(day_c), _ptr(weekday_c), _ptr(hour_c), _ptr(u), _ptr(pq), _ptr(saved),
+                                _ptr(d_R), B, T, C, *w, _ptr(d_u), _ptr(d_pq), _ptr(d_tab), _ptr(ws), code, _stream()), "edgl_mate_bwd")
+        d_m, d_d, d_w, d_h = torch.split(d_tab, MATE_RANGES, dim=0)
+        return None, d_m, d_d, d_w, d_h, None, None, None, None, d_u, d_pq, None
+
+
+class TaheFn(torch.autograd.Function):
+    """hist[q] = sum_{k <= q} ((1 + n_q . n_k) / 2) Hs[k] with n = l2_normalize(R) (sequential.py:247-265; edgl_tahe_fwd / bwd):
+    R, Hs [B,T,C] -> hist [B,T,C].  R is both the queries and the keys: one d_R.  No atomics anywhere."""
+
+    @staticmethod
+    def forward(ctx, R, Hs):
+        B, T, C = R.shape
+        R, Hs = R.contiguous(), Hs.contiguous()
+        code = _code(R)
+        _seq3("TaheFn: Hs", Hs, B, T, C, R.dtype)
+        hist = torch.empty_like(R)
+        check(lib.edgl_tahe_fwd(_ptr(R), _ptr(Hs), B, T, C, _ptr(hist), code, _stream()), "edgl_tahe_fwd")
+        ctx.save_for_backward(R, Hs)
+        return hist
+
+    @staticmethod
+    def backward(ctx, d_hist):
+        R, Hs = ctx.saved_tensors
+        B, T, C = R.shape
+        d_hist = d_hist.contiguous()
+        d_R, d_Hs = torch.empty_like(R), torch.empty_like(Hs)
+        check(lib.edgl_tahe_bwd(_ptr(R), _ptr(Hs), _ptr(d_hist), B, T, C, _ptr(d_R), _ptr(d_Hs), _code(R), _stream()), "edgl_tahe_bwd")
+        return d_R, d_Hs
+
+
+class Cat3Fn(torch.autograd.Function):
+    """[a | b | c] along the channels (TimelyREC.py:150; edgl_cat3): three [.., C] tensors -> [.., 3C]."""
+
+    @staticmethod
+    def forward(ctx, a, b, c):
+        a, b, c = a.contiguous(), b.contiguous(), c.contiguous()
+        C = a.shape[-1]
+        if b.shape != a.shape or c.shape != a.shape or b.dtype != a.dtype or c.dtype != a.dtype:
+            raise _lib.EdglError("Cat3Fn: the three inputs must agree in shape and dtype")
+        out = torch.empty(a.shape[:-1] + (3 * C,), device=a.device, dtype=a.dtype)
+        check(lib.edgl_cat3(_ptr(a), _ptr(b), _ptr(c), a.numel() // C, C, _ptr(out), 0, _code(a), _stream()), "edgl_cat3")
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        d_out = d_out.contiguous()
+        C = d_out.shape[-1] // 3
+        shape = d_out.shape[:-1] + (C,)
+        da, db, dc = (torch.empty(shape, device=d_out.device, dtype=d_out.dtype) for _ in range(3))
+        check(lib.edgl_cat3(_ptr(da), _ptr(db), _ptr(dc), d_out.numel() // (3 * C), C, _ptr(d_out), 1, _code(d_out), _stream()),
+              "edgl_cat3")
+        return da, db, dc
+
+
+class TaheMixFn(torch.autograd.Function):
+    """Hs = (emb + te_weight * tcode) * (ids != 0) (TimelyREC.py:139-146; edgl_tahe_mix_fwd / bwd): emb, tcode [B,T,C], te_weight
+    the trainable f32 scalar.  d_te is a sum of per-workgroup partials in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, emb, tcode, te_weight, ids):
+        emb, tcode = emb.contiguous(), tcode.contiguous()
+        C = emb.shape[-1]
+        rows = emb.numel() // C
+        if tcode.dtype != emb.dtype or tcode.shape != emb.shape or te_weight.dtype != torch.float32 or te_weight.numel() != 1:
+            raise _lib.EdglError("TaheMixFn: tcode must match emb and te_weight must be one f32 scalar")
+        if ids.dtype != torch.int64 or ids.numel() != rows or not ids.is_contiguous():
+            raise _lib.EdglError("TaheMixFn: ids must be a contiguous int64 tensor with one id per row")
+        out = torch.empty_like(emb)
+        check(lib.edgl_tahe_mix_fwd(_ptr(emb), _ptr(tcode), _ptr(te_weight), _ptr(ids), rows, C, _ptr(out), _code(emb), _stream()),
+              "edgl_tahe_mix_fwd")
+        ctx.save_for_backward(tcode, ids)
+        ctx.meta = (rows, C, te_weight.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        tcode, ids = ctx.saved_tensors
+        rows, C, tshape = ctx.meta
+        d_out = d_out.contiguous()
+        d_emb = torch.empty_like(d_out)
+        d_te = torch.empty(1, device=d_out.device, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_tahe_mix_bwd_workspace(rows)), device=d_out.device, dtype=torch.float32)
+        check(lib.edgl_tahe_mix_bwd(_ptr(d_out), _ptr(tcode), _ptr(ids), rows, C, _ptr(d_emb), _ptr(d_te), _ptr(ws), _code(d_out),
+                                    _stream()), "edgl_tahe_mix_bwd")
+        return d_emb, None, d_te.view(tshape), None
+
+
 def clip_by_global_norm(grad: torch.Tensor, clip: float) -> None:
     """grad (the flat f32 gradient arena) *= clip / max(||grad||, clip), in place: tf.clip_by_global_norm over every gradient.  The
     sum of squares and the factor stay on the device (edgl_l2_loss with l2 = 2, edgl_clip_scale): no host read, graph-capturable."""

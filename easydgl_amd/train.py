@@ -2,7 +2,8 @@
 (``src/util.py:14-58``), on the HIP model.
 
 Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM (regressive batches,
-``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``).
+``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``); TimelyREC is fed regressively with the four
+calendar fields of its records (``has_datetime=True``), derived from ``seqs_t`` where the files lack them.
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
 ``--num_items --num_units --num_heads --num_blocks --seqslen --time_scale --masklen --mark --ct_reg --batch_size
 --num_epochs --learning_rate --l2_reg --hidden_dropout_rate --attention_probs_dropout_rate --eval_per_steps
@@ -34,7 +35,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC or S2PNM (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM or TimelyREC (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512
@@ -44,6 +45,8 @@ def args(argv=None):
     p.add_argument("--num_blocks", type=int, default=3)
     p.add_argument("--seqslen", type=int, default=30)
     p.add_argument("--time_scale", type=float, default=1)
+    p.add_argument("--window_ratio", type=float, default=0.2,
+                   help="TimelyREC: the calendar-slot window of a granularity is max(int(range * window_ratio + 0.5), 1) + 1; in (0, 0.5]")
     p.add_argument("--masklen", type=int, default=6)
     p.add_argument("--timelen", type=int, default=256)
     p.add_argument("--mark", type=str, help="mark data file (pickled csr matrix or .npy)")
@@ -208,15 +211,34 @@ def regressive_batch(tok, tim, is_training: bool):
     return {"seqs_i": tok[:, :-1].contiguous(), "seqs_t": tim}, (tok[:, 1:].contiguous() if is_training else tok)
 
 
+def regressive_calendar_batch(tok, tim, cal, is_training: bool):
+    """regressive_batch with RegressivePostProcessor(has_datetime=True)'s four calendar fields (dataloader.py:95-108; TimelyREC):
+    `cal` = (month, day, weekday, hour) int64 [B, T+1]; the features see field[:-1]."""
+    feats, labels = regressive_batch(tok, tim, is_training)
+    for name, a in zip(("seqs_month", "seqs_day", "seqs_weekday", "seqs_hour"), cal):
+        feats[name] = a[:, :-1].contiguous()
+    return feats, labels
+
+
+def load_calendar_or_derive(patterns, seqslen, ids, ts, split):
+    """The split's calendar fields from its files, or — files without them — derived from the timestamps (UTC), with one log line."""
+    from . import formats as F
+    try:
+        return F.load_calendar(patterns, seqslen)
+    except KeyError:
+        logging.info("   %s: no calendar fields in the files; derived from seqs_t (UTC)", split)
+        return F.calendar_from_timestamps(ts, ids)
+
+
 def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False, negatives: int = 0,
-             neg_seed: int = 0, neg_dist=None) -> Dict[str, float]:
+             neg_seed: int = 0, neg_dist=None, calendar=None) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
     prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
     (--device_data) — the batches are then assembled on the device, in file order.  `by_rank`: the metrics from the label's rank
     (model.eval_step(by_rank=True)) — the same H / N values plus "MRR".  `negatives` > 0: the sampled-negative protocol —
     the label ranked among that many negatives per sequence, keyed by (neg_seed, step 0, the sequence's index in the split): every
     pass over a split ranks against the same lists, whatever the batch size; cut-offs (1, 5, 10).  `neg_dist` (ops.NegDist): those
-    negatives are drawn by its weights."""
+    negatives are drawn by its weights.  `calendar`: the split's four calendar arrays (TimelyREC)."""
     import torch
     from . import data as D
     if negatives > 0:
@@ -243,7 +265,11 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_r
     for lo in range(0, n, batch_size):
         tok = torch.as_tensor(ids[lo:lo + batch_size]).cuda()
         tim = torch.as_tensor(ts[lo:lo + batch_size]).cuda()
-        feats, labels = D.device_mask_last(tok, tim, model.mask) if masked else regressive_batch(tok, tim, False)
+        if calendar is not None:
+            cal = [torch.as_tensor(a[lo:lo + batch_size]).cuda() for a in calendar]
+            feats, labels = regressive_calendar_batch(tok, tim, cal, False)
+        else:
+            feats, labels = D.device_mask_last(tok, tim, model.mask) if masked else regressive_batch(tok, tim, False)
         step(feats, labels)
     return model.metrics()
 
@@ -262,6 +288,17 @@ def run(FLAGS) -> Dict[str, float]:
     vl_i, vl_t = F.load_sequences(FLAGS.valid, FLAGS.seqslen)
     te_i, te_t = F.load_sequences(FLAGS.test, FLAGS.seqslen)
     logging.info("   train %d, valid %d, test %d sequences of %d positions", len(tr_i), len(vl_i), len(te_i), tr_i.shape[1])
+
+    cals = None
+    if FLAGS.model == "TimelyREC":
+        # the on-device loader and graph capture know nothing of the calendar fields (out of scope)
+        if getattr(FLAGS, "device_data", False):
+            raise ValueError("--device_data with --model TimelyREC: the on-device loader does not carry the calendar fields")
+        if getattr(FLAGS, "graph", False):
+            raise ValueError("--graph with --model TimelyREC: its step is not captured into a graph; run without --graph")
+        cals = {"train": load_calendar_or_derive(FLAGS.train, FLAGS.seqslen, tr_i, tr_t, "train"),
+                "valid": load_calendar_or_derive(FLAGS.valid, FLAGS.seqslen, vl_i, vl_t, "valid"),
+                "test": load_calendar_or_derive(FLAGS.test, FLAGS.seqslen, te_i, te_t, "test")}
 
     logging.info("2. create neural model")
     if getattr(FLAGS, "mark", None) and isinstance(FLAGS.mark, str):
@@ -358,6 +395,8 @@ def run(FLAGS) -> Dict[str, float]:
                 if masked:
                     feats, labels = D.device_mask_random(tok, tim, model.mask, FLAGS.masklen, mask_state)
                     mask_state[1] += 1
+                elif cals is not None:
+                    feats, labels = regressive_calendar_batch(tok, tim, [torch.as_tensor(a[idx]).cuda() for a in cals["train"]], True)
                 else:
                     feats, labels = regressive_batch(tok, tim, True)
             if engine is not None and len(idx) == bs:
@@ -389,9 +428,11 @@ def run(FLAGS) -> Dict[str, float]:
             break
         if epoch % FLAGS.eval_per_steps:
             continue
-        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed, eval_dist)
+        vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed, eval_dist,
+                      None if cals is None else cals["valid"])
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
-        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed, eval_dist)
+        te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed, eval_dist,
+                      None if cals is None else cals["test"])
         if stopper.step(running_loss, vl[select_on], vl, te):
             break
     return stopper.summary()

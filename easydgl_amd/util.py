@@ -21,4 +21,7 @@ def ranking(FLAGS):
     if FLAGS.model == "S2PNM":
         from .model import S2PNM
         return S2PNM(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "TimelyREC":
+        from .model import TimelyREC
+        return TimelyREC(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

@@ -1092,6 +1092,44 @@ int edgl_sigmoid_fwd(const void* x, void* y, long n, int dtype, void* stream);
 int edgl_sigmoid_bwd(const void* dy, const void* y, void* dx, long n, int dtype, void* stream);
 int edgl_clip_scale(float* grad, long n, const float* sumsq, float clip, void* stream);
 
+/* ---- TimelyREC: multi-aspect time encoder and time-aware history encoder (k_mate.hip, k_tahe.hip) -------------
+ * MATE — calendar slots, slot attention and the gated combination (TimelyREC.py:57-77,108-135; sequential.py:220-237) in one op.
+ * Granularities month, day, weekday, hour: ranges M = 12, 31, 7, 24, tables E_g [M_g, C] `dtype`, windows W_g = w_month .. w_hour
+ * (max(int(M * window_ratio + 0.5), 1) + 1 with window_ratio in (0, 0.5]: 2 <= W_g <= M_g / 2 + 2).
+ *   idx int64 [4][B][T]: the calendar index of every position, month - 1 | day - 1 | weekday | hour; an index outside [0, M) reads a
+ *     zero row for e (the padding's -1) and enters the window rows by floor-mod M;
+ *   u [B,T,4C] = U [Wu_month | Wu_day | Wu_weekday | Wu_hour], pq [B,T,C] = U Wc (plain GEMMs);
+ *   cs[s][w] = sum_{s' <= s} E[(f[s'] + w) mod M] + E[(f[s'] - w) mod M], slot_0 = e, slot_w = (e + cs_w) / (2w + 1),
+ *   p = softmax_w((e * u) . (slot_w * u) / sqrt(C)), period = sum_w p_w slot_w * u, R = sum_g sigmoid(pq . period_g) period_g.
+ * edgl_mate_fwd: R [B,T,C]; saved f32 [B,T,edgl_mate_saved_floats] (NULL: inference) = p of the four granularities, then the four gates.
+ * edgl_mate_bwd: d_u [B,T,4C], d_pq [B,T,C] `dtype`; d_tables f32 [74, C] (overwritten): rows 0-11 month, 12-42 day, 43-49 weekday,
+ *   50-73 hour.  workspace: edgl_mate_bwd_workspace floats.  The slots are recomputed; the table gradient is accumulated per
+ *   workgroup in LDS over 64-channel slices and summed from slabs in a fixed order: no atomics, the same bits in every call.
+ * 1 <= T <= 128, C a power of two in [32, 512]; anything else is EDGL_ERR_SHAPE before a launch.
+ * TAHE — hist[q] = sum_{k <= q} ((1 + n_q . n_k) / 2) Hs[k], n = l2_normalize(R) (x * rsqrt(max(sum x^2, 1e-12))); R, Hs, hist
+ * [B,T,C] `dtype`; same T and C range.  edgl_tahe_bwd: d_R (both operands of the cosine, one gradient) and d_Hs.  No atomics.
+ * edgl_tahe_mix_fwd: out [rows,C] = (emb + te_weight[0] * tcode) * (ids != 0); edgl_tahe_mix_bwd: d_emb = d_out * mask and
+ *   d_te f32 [1] = sum d_out * tcode over the unmasked rows, from per-workgroup partials (workspace: edgl_tahe_mix_bwd_workspace
+ *   floats) in a fixed order. */
+int edgl_mate_saved_floats(int w_month, int w_day, int w_weekday, int w_hour);
+int edgl_mate_fwd(const int64_t* idx, const void* month_tab, const void* day_tab, const void* weekday_tab, const void* hour_tab,
+                  const void* u, const void* pq, int B, int T, int C, int w_month, int w_day, int w_weekday, int w_hour, void* R,
+                  float* saved, int dtype, void* stream);
+long edgl_mate_bwd_workspace(int B, int T, int C, int w_month, int w_day, int w_weekday, int w_hour);
+int edgl_mate_bwd(const int64_t* idx, const void* month_tab, const void* day_tab, const void* weekday_tab, const void* hour_tab,
+                  const void* u, const void* pq, const float* saved, const void* d_R, int B, int T, int C, int w_month, int w_day,
+                  int w_weekday, int w_hour, void* d_u, void* d_pq, float* d_tables, float* workspace, int dtype, void* stream);
+int edgl_tahe_fwd(const void* R, const void* Hs, int B, int T, int C, void* hist, int dtype, void* stream);
+int edgl_tahe_bwd(const void* R, const void* Hs, const void* d_hist, int B, int T, int C, void* d_R, void* d_Hs, int dtype,
+                  void* stream);
+int edgl_tahe_mix_fwd(const void* emb, const void* tcode, const float* te_weight, const int64_t* ids, long rows, int C, void* out,
+                      int dtype, void* stream);
+/* cat [rows,3C] = [a | b | c] (split == 0: the head's input, TimelyREC.py:150) or a, b, c <- the three blocks of cat (split != 0). */
+int edgl_cat3(void* a, void* b, void* c, long rows, int C, void* cat, int split, int dtype, void* stream);
+long edgl_tahe_mix_bwd_workspace(long rows);
+int edgl_tahe_mix_bwd(const void* d_out, const void* tcode, const int64_t* ids, long rows, int C, void* d_emb, float* d_te,
+                      float* workspace, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
