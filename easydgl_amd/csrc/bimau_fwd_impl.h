@@ -415,7 +415,7 @@ int launch_fwd_e(FwdP p, hipStream_t st) {
         if (p.dbits && p.rate > 0.f) kern = sk ? bimau_fwd_kernel<T, DT, NT, EC, PHASE, true, (NT >= 2)> : bimau_fwd_kernel<T, DT, NT, EC, PHASE, true>;
         else if (sk) kern = bimau_fwd_kernel<T, DT, NT, EC, PHASE, false, (NT >= 2)>;
     }
-    if (smem > 48 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(kern, smem, "edgl_bimau_fwd");
     const long jobs = (long)p.B * p.H;
     hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
     EDGL_LAUNCH_CHECK();

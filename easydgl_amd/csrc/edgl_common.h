@@ -37,6 +37,15 @@ extern "C" void edgl_set_error(const char* fmt, ...);
         }                                                                \
     } while (0)
 
+// A kernel launched with more than 48 KB of dynamic LDS calls this first (k_misc.hip): raises the kernel's limit on the current
+// device unless it already holds `bytes` there (lds_limit.h).  EDGL_OK, or EDGL_ERR_LAUNCH with the error text set; `who` names the caller.
+int edgl_lds_limit(const void* kern, size_t bytes, const char* who);
+#define EDGL_LDS_LIMIT(kern, bytes, who)                                           \
+    do {                                                                           \
+        const int rc_ = edgl_lds_limit((const void*)(kern), (size_t)(bytes), (who)); \
+        if (rc_ != EDGL_OK) return rc_;                                            \
+    } while (0)
+
 static inline int edgl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // grid of a grid-stride kernel over n elements, 256 threads per workgroup
 static inline int grid_for(long n) { const long g = (n + 255) / 256; return (int)(g < 4096 ? g : 4096); }

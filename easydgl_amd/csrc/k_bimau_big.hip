@@ -469,7 +469,7 @@ int run_intensity_fwd(const FwdP& p, hipStream_t st) {
     ip.z_out = p.z_out; ip.lam = p.lam;
     const size_t smem = (size_t)MarkChunk<T, DT, false>::BYTES * (big_double_buffer<T, DT>() ? 2 : 1);
     auto k = intensity_fwd_big_kernel<T, DT>;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(k, smem, "edgl_bimau_fwd");
     const long ntile = (long)p.B * p.H * ((p.T + 15) / 16);
     hipLaunchKernelGGL(k, dim3(row_blocks(ntile, 8)), dim3(256), smem, st, ip);
     EDGL_LAUNCH_CHECK();
@@ -499,13 +499,13 @@ int run_intensity_bwd_big(const BwdP& p, long dsc_rows, hipStream_t st) {
     const long ntile = jobs * ((p.T + 15) / 16);
     const size_t smem_r = (size_t)MarkChunk<T, DT, true>::BYTES * (big_double_buffer<T, DT>() ? 2 : 1);
     auto kr = intensity_bwd_rows_big_kernel<T, DT>;
-    hipFuncSetAttribute((const void*)kr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r);
+    EDGL_LDS_LIMIT(kr, smem_r, "edgl_bimau_bwd");
     hipLaunchKernelGGL(kr, dim3(row_blocks(ntile, 8)), dim3(256), smem_r, st, ip);
     EDGL_LAUNCH_CHECK();
     constexpr int NC = WGroup<DT>::NJ * 16;
     const size_t smem_w = (size_t)NC * (dh + 4) * sizeof(T) + (size_t)(3 * NC + (dh + 3) * NC) * sizeof(float);
     auto kw = intensity_bwd_weights_big_kernel<T, DT>;
-    hipFuncSetAttribute((const void*)kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_w);
+    EDGL_LDS_LIMIT(kw, smem_w, "edgl_bimau_bwd");
     hipLaunchKernelGGL(kw, dim3(RS, (JE + NC - 1) / NC), dim3(256), smem_w, st, ip);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -529,7 +529,7 @@ int bwd_big(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling
         EDGL_REQUIRE(smem <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_bimau_bwd: sweep 1 needs %zu B of LDS (dh=%d T=%d)", smem, dh, p.T);
         p.waves = waves;
         auto kern = bimau_bwd_sweep1_kernel<T, DT, NT, 0, false>;
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT(kern, smem, "edgl_bimau_bwd");
         hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         EDGL_LAUNCH_CHECK();
     }
@@ -550,13 +550,13 @@ int bwd_big(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscaling
             // register file (378-521 spilled registers) — two launches, each keeping the tiles of one 64-channel slice
             auto k0 = bimau_bwd_sweep2_kernel<T, DT, NT, 0, 1, false, -1, false, 2, 0>;
             auto k1 = bimau_bwd_sweep2_kernel<T, DT, NT, 0, 1, false, -1, false, 2, 1>;
-            hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            EDGL_LDS_LIMIT(k0, smem, "edgl_bimau_bwd");
+            EDGL_LDS_LIMIT(k1, smem, "edgl_bimau_bwd");
             hipLaunchKernelGGL(k0, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
             hipLaunchKernelGGL(k1, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         } else {
             auto kern = bimau_bwd_sweep2_kernel<T, DT, NT, 0, 1, false>;
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            EDGL_LDS_LIMIT(kern, smem, "edgl_bimau_bwd");
             hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         }
         edgl_prof_end(EDGL_KERNEL_BIMAU_BWD, st);

@@ -390,7 +390,7 @@ int launch_intensity_bwd(const BwdP& p, long dsc_rows, hipStream_t st) {
     // (a compile-time mark count — no guards around the mark blocks — lets the scheduler hoist the LDS operand reads of all eight
     //  blocks: 168 registers no longer hold them, 25-37 spilled inside the tile loop, 81 -> 180 us.  Run-time E it is.)
     auto kb = intensity_bwd_kernel<T, DT, 0>;
-    hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_b);
+    EDGL_LDS_LIMIT(kb, smem_b, "edgl_bimau_bwd");
     hipLaunchKernelGGL(kb, dim3(KY_BLOCKS, KY_NY), dim3(256), smem_b, st, mp);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -432,7 +432,7 @@ int launch_bwd(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscal
                 }
             }
         }
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT(kern, smem, "edgl_bimau_bwd");
         hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         EDGL_LAUNCH_CHECK();
     }
@@ -460,7 +460,7 @@ int launch_bwd(BwdP p, char* ws, float* dW1, float* db1, float* dw, float* dscal
                 else if (sk) kern = bimau_bwd_sweep2_kernel<T, DT, NT, 16, KY_NY, true, 0, false, 1, 0, SKC>;
             }
         }
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT(kern, smem, "edgl_bimau_bwd");
         edgl_prof_begin(EDGL_KERNEL_BIMAU_BWD, st);
         hipLaunchKernelGGL(kern, dim3((unsigned)((jobs + waves - 1) / waves)), dim3(64 * waves), smem, st, p);
         edgl_prof_end(EDGL_KERNEL_BIMAU_BWD, st);

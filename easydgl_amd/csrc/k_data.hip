@@ -304,10 +304,10 @@ extern "C" int edgl_embed_pos_bwd_ct(const int64_t* ids, const void* dx0, int B,
     const size_t smem = (size_t)srows * C * sizeof(float);
     dim3 grid((unsigned)(((long)B * T + srows - 1) / srows));
     if (dtype == EDGL_F32) {
-        hipFuncSetAttribute((const void*)embed_pos_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT(embed_pos_bwd_kernel<float>, smem, "edgl_embed_pos_bwd");
         hipLaunchKernelGGL((embed_pos_bwd_kernel<float>), grid, dim3(256), smem, st, p);
     } else {
-        hipFuncSetAttribute((const void*)embed_pos_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT(embed_pos_bwd_kernel<bf16>, smem, "edgl_embed_pos_bwd");
         hipLaunchKernelGGL((embed_pos_bwd_kernel<bf16>), grid, dim3(256), smem, st, p);
     }
     EDGL_LAUNCH_CHECK();

@@ -541,10 +541,10 @@ static int encode_bwd_impl(const int64_t* ids, const uint8_t* marks, const void*
             if (C % 128 == 0) hipLaunchKernelGGL((encode_scatter_mfma_kernel<8>), dim3(nbm, C / 128), dim3(256), 0, st, p, rb);
             else hipLaunchKernelGGL((encode_scatter_mfma_kernel<4>), dim3(nbm), dim3(256), 0, st, p, rb);
         } else if (dtype == EDGL_F32) {
-            hipFuncSetAttribute((const void*)encode_scatter_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s);
+            EDGL_LDS_LIMIT(encode_scatter_kernel<float>, smem_s, "edgl_encode_bwd");
             hipLaunchKernelGGL((encode_scatter_kernel<float>), dim3(nb), dim3(256), smem_s, st, p);
         } else {
-            hipFuncSetAttribute((const void*)encode_scatter_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s);
+            EDGL_LDS_LIMIT(encode_scatter_kernel<bf16>, smem_s, "edgl_encode_bwd");
             hipLaunchKernelGGL((encode_scatter_kernel<bf16>), dim3(nb), dim3(256), smem_s, st, p);
         }
         EDGL_LAUNCH_CHECK();

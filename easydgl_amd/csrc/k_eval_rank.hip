@@ -294,7 +294,7 @@ int launch(P p, const Plan& pl, hipStream_t st) {
     auto k = rank_sweep_kernel<C, NZ, NWS>;
     const int lds = G_::bytes(pl.tps * NZ);
     EDGL_REQUIRE(lds <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_score_rank_fused: %d B of LDS", lds);
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    EDGL_LDS_LIMIT(k, lds, "edgl_score_rank_fused");
     hipLaunchKernelGGL(k, grid, dim3(G_::NTHR), lds, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;

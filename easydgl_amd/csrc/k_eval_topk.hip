@@ -425,8 +425,8 @@ int launch(P p, const Plan& pl, hipStream_t st) {
     auto k2 = eval_sweep_kernel<C, NZ, NWS, true>;
     const int be = G_::bytes_emit(pl.tps * NZ);
     EDGL_REQUIRE(be <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_score_topk_fused: %d B of LDS", be);
-    hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, G_::BYTES_GMAX);
-    hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, be);
+    EDGL_LDS_LIMIT(k1, G_::BYTES_GMAX, "edgl_score_topk_fused");
+    EDGL_LDS_LIMIT(k2, be, "edgl_score_topk_fused");
     hipLaunchKernelGGL(k1, grid, dim3(NTHR), G_::BYTES_GMAX, st, p);
     hipLaunchKernelGGL(eval_thr_kernel, dim3((p.R + 3) / 4), dim3(256), 0, st, p.gmax, p.R, p.G, p.K + p.T, p.thr, p.count);
     hipLaunchKernelGGL(k2, grid, dim3(NTHR), be, st, p);

@@ -765,7 +765,7 @@ static int launch_tile_nn(const StripP& p, hipStream_t st) {
     constexpr size_t a_el = (size_t)G_BM * G_LDK, b_el = B_KC ? (size_t)G_BN * G_LDK : (size_t)G_BK * G_LDN;
     const size_t smem = std::max((EPI ? 2 : 1) * (a_el + b_el) * sizeof(bf16), (size_t)G_BM * G_LDO * sizeof(bf16));
     auto k = tile_nn_kernel<B_KC, EPI>;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(k, smem, "edgl_gemm (tile)");
     const int nbm = (p.M + G_BM - 1) / G_BM, nbn = p.N / G_BN;
     hipLaunchKernelGGL(k, dim3((unsigned)xcd_grid(nbm * nbn)), dim3(G_NT), smem, st, p);
     EDGL_LAUNCH_CHECK();
@@ -925,7 +925,7 @@ static int launch_stream(const StripP& p, hipStream_t st) {
                         (fstage ? (size_t)8 * 16 * (64 + 4) * sizeof(float) : (size_t)8 * 16 * (64 + 8) * sizeof(bf16));
     if (smem > 160 * 1024) return 0;
     auto k = strip_stream_kernel<NKB, B_KC>;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(k, smem, "edgl_gemm (stream)");
     hipLaunchKernelGGL(k, dim3((p.M + 255) / 256), dim3(W_NT), smem, st, p);
     EDGL_LAUNCH_CHECK();
     return 1;
@@ -940,7 +940,7 @@ static int launch_strip(const StripP& p, hipStream_t st) {
                         (fstage ? (size_t)8 * 16 * (64 + 4) * sizeof(float) : (size_t)8 * 16 * (64 + 8) * sizeof(bf16));
     if (smem > 160 * 1024) return 0;
     auto k = strip_gemm_kernel<NKB, B_KC>;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(k, smem, "edgl_gemm (strip)");
     const int nparts = (p.N + 127) / 128;
     const int per_cu = std::max(1, (int)((160 * 1024) / smem));
     const int nstrip8 = (p.M + 255) / 256;
@@ -1030,7 +1030,7 @@ static int tn_flush(hipStream_t st) {
     int splits[TN_MAX_JOBS];
     const int blocks = tn_group_layout(g_tn_q, n, tn_cus(), &g, splits);
     const size_t tn_lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
-    hipFuncSetAttribute((const void*)tn_gemm_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn_lds);
+    EDGL_LDS_LIMIT(tn_gemm_group_kernel, tn_lds, "edgl_gemm_dw (grouped)");
     hipLaunchKernelGGL(tn_gemm_group_kernel, dim3(xcd_grid(blocks)), dim3(T_NT), tn_lds, st, g);
     EDGL_LAUNCH_CHECK();
     for (int i = 0; i < n; ++i) {
@@ -1073,7 +1073,7 @@ int edgl_gemm2_try_tn(const void* X, const void* Y, float* C, int R, int Kf, int
         return 1;
     }
     const size_t lds = (size_t)2 * T_BR * (128 + 16) * sizeof(bf16);
-    hipFuncSetAttribute((const void*)tn_gemm_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    EDGL_LDS_LIMIT(tn_gemm_kernel<128>, lds, "edgl_gemm_dw");
     p.tiles_n = (N + 127) / 128; p.tiles_k = (Kf + 127) / 128; p.nblocks = p.tiles_n * p.tiles_k * splits;
     hipLaunchKernelGGL(tn_gemm_kernel<128>, dim3(xcd_grid(p.nblocks)), dim3(T_NT), lds, st, p);
     EDGL_LAUNCH_CHECK();
@@ -1158,7 +1158,7 @@ extern "C" int edgl_dx_encode_bwd_label(const void* dqkvt, const void* W, int ld
     if (nred < 0) return nred;
     StripP p{(const bf16*)dqkvt, (const bf16*)W, dx0_out, B * T, 3 * C, 4 * C, lda, ldb, 3 * C, EpiP{nullptr, nullptr, 0}};
     const size_t smem = std::max((size_t)2 * G_BM * G_LDK * sizeof(bf16), (size_t)DXE_LDS);
-    hipFuncSetAttribute((const void*)dx_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(dx_encode_kernel, smem, "edgl_dx_encode_bwd_label");
     g_tn_n -= tn_n;      // (the queue has left: a later edgl_gemm_dw_defer(0) finds it empty)
     hipLaunchKernelGGL(dx_encode_kernel, dim3((unsigned)(tn_blocks + x.gemm_blocks + x.lab_blocks + nred)), dim3(G_NT), smem, st, p, x, rb, tn.g, tn_blocks);
     EDGL_LAUNCH_CHECK();

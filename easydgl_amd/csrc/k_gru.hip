@@ -227,12 +227,13 @@ int gru_fwd_t(const GruFwdP& p, void* pack, const void* R, hipStream_t st) {
     const size_t smem = (res ? pack_bytes : 0) + (size_t)GRU_TB * p.C * sizeof(float) + (size_t)2 * GRU_TB * d.ldo * sizeof(T);
     const dim3 grid((unsigned)((p.B + GRU_TB - 1) / GRU_TB));
     if (res) {
-        (void)hipFuncSetAttribute((const void*)gru_seq_fwd_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT((gru_seq_fwd_kernel<T, true>), smem, "edgl_gru_seq_fwd");
         hipLaunchKernelGGL((gru_seq_fwd_kernel<T, true>), grid, dim3(GRU_THREADS), smem, st, p);
     } else {
-        (void)hipFuncSetAttribute((const void*)gru_seq_fwd_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT((gru_seq_fwd_kernel<T, false>), smem, "edgl_gru_seq_fwd");
         hipLaunchKernelGGL((gru_seq_fwd_kernel<T, false>), grid, dim3(GRU_THREADS), smem, st, p);
     }
+    EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
 
@@ -246,12 +247,13 @@ int gru_bwd_t(const GruBwdP& p, void* pack, const void* R, hipStream_t st) {
     const size_t smem = (res ? pack_bytes : 0) + (size_t)GRU_TB * p.C * sizeof(float) + (size_t)GRU_TB * d.ldo2 * sizeof(T);
     const dim3 grid((unsigned)((p.B + GRU_TB - 1) / GRU_TB));
     if (res) {
-        (void)hipFuncSetAttribute((const void*)gru_seq_bwd_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT((gru_seq_bwd_kernel<T, true>), smem, "edgl_gru_seq_bwd");
         hipLaunchKernelGGL((gru_seq_bwd_kernel<T, true>), grid, dim3(GRU_THREADS), smem, st, p);
     } else {
-        (void)hipFuncSetAttribute((const void*)gru_seq_bwd_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        EDGL_LDS_LIMIT((gru_seq_bwd_kernel<T, false>), smem, "edgl_gru_seq_bwd");
         hipLaunchKernelGGL((gru_seq_bwd_kernel<T, false>), grid, dim3(GRU_THREADS), smem, st, p);
     }
+    EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
 
@@ -273,10 +275,7 @@ extern "C" int edgl_gru_seq_fwd(const void* xp, const void* R, const float* b_R,
     const int rc = gru_check("edgl_gru_seq_fwd", B, T, C, dtype);
     if (rc != EDGL_OK) return rc;
     GruFwdP p{xp, pack, b_R, B, T, C, h, saved, hprev_c};
-    const int r2 = dtype == EDGL_F32 ? gru_fwd_t<float>(p, pack, R, (hipStream_t)stream) : gru_fwd_t<bf16>(p, pack, R, (hipStream_t)stream);
-    if (r2 != EDGL_OK) return r2;
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
+    return dtype == EDGL_F32 ? gru_fwd_t<float>(p, pack, R, (hipStream_t)stream) : gru_fwd_t<bf16>(p, pack, R, (hipStream_t)stream);
 }
 
 extern "C" int edgl_gru_seq_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* d_gh,
@@ -285,8 +284,5 @@ extern "C" int edgl_gru_seq_bwd(const void* d_h, const void* R, const float* sav
     const int rc = gru_check("edgl_gru_seq_bwd", B, T, C, dtype);
     if (rc != EDGL_OK) return rc;
     GruBwdP p{d_h, pack, saved, B, T, C, d_xp, d_gh};
-    const int r2 = dtype == EDGL_F32 ? gru_bwd_t<float>(p, pack, R, (hipStream_t)stream) : gru_bwd_t<bf16>(p, pack, R, (hipStream_t)stream);
-    if (r2 != EDGL_OK) return r2;
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
+    return dtype == EDGL_F32 ? gru_bwd_t<float>(p, pack, R, (hipStream_t)stream) : gru_bwd_t<bf16>(p, pack, R, (hipStream_t)stream);
 }

@@ -276,25 +276,12 @@ int mate_fill(const char* who, MateP& p, int B, int T, int C, int w0, int w1, in
     return EDGL_OK;
 }
 
-template <typename K>
-int mate_lds_attr(K kern, int slot, size_t smem) {
-    static size_t set_for[4][16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (smem > 48 * 1024 && set_for[slot][dev] < smem) {
-        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        EDGL_REQUIRE(e == hipSuccess, EDGL_ERR_LAUNCH, "edgl_mate: cannot raise the LDS limit: %s", hipGetErrorString(e));
-        set_for[slot][dev] = 160 * 1024;
-    }
-    return EDGL_OK;
-}
-
 template <typename T, bool BWD>
-int mate_launch_pos(const MateP& p, int slot, hipStream_t st) {
+int mate_launch_pos(const MateP& p, hipStream_t st) {
     const size_t smem = (size_t)(p.WT + MATE_G) * p.C * sizeof(float);
-    const int rc = mate_lds_attr(mate_pos_kernel<T, BWD>, slot, smem);
-    if (rc != EDGL_OK) return rc;
+    EDGL_LDS_LIMIT((mate_pos_kernel<T, BWD>), smem, BWD ? "edgl_mate_bwd" : "edgl_mate_fwd");
     hipLaunchKernelGGL((mate_pos_kernel<T, BWD>), dim3(p.B), dim3(256), smem, st, p);
+    EDGL_LAUNCH_CHECK();
     return EDGL_OK;
 }
 
@@ -317,10 +304,7 @@ extern "C" int edgl_mate_fwd(const int64_t* idx, const void* month_tab, const vo
     if (rc != EDGL_OK) return rc;
     p.idx = idx; p.tab[0] = month_tab; p.tab[1] = day_tab; p.tab[2] = weekday_tab; p.tab[3] = hour_tab;
     p.u = u; p.pq = pq; p.R = R; p.saved = saved;
-    const int r2 = dtype == EDGL_F32 ? mate_launch_pos<float, false>(p, 0, (hipStream_t)stream) : mate_launch_pos<bf16, false>(p, 1, (hipStream_t)stream);
-    if (r2 != EDGL_OK) return r2;
-    EDGL_LAUNCH_CHECK();
-    return EDGL_OK;
+    return dtype == EDGL_F32 ? mate_launch_pos<float, false>(p, (hipStream_t)stream) : mate_launch_pos<bf16, false>(p, (hipStream_t)stream);
 }
 
 extern "C" long edgl_mate_bwd_workspace(int B, int T, int C, int w_month, int w_day, int w_weekday, int w_hour) {
@@ -343,7 +327,7 @@ extern "C" int edgl_mate_bwd(const int64_t* idx, const void* month_tab, const vo
     p.u = u; p.pq = pq; p.dR = d_R; p.saved = const_cast<float*>(saved);
     p.coef = workspace; p.slabs = workspace + (long)B * T * p.NSV;
     p.R = d_pq; p.d_u = d_u;
-    const int r2 = dtype == EDGL_F32 ? mate_launch_pos<float, true>(p, 2, st) : mate_launch_pos<bf16, true>(p, 3, st);
+    const int r2 = dtype == EDGL_F32 ? mate_launch_pos<float, true>(p, st) : mate_launch_pos<bf16, true>(p, st);
     if (r2 != EDGL_OK) return r2;
     const int P = mate_slab_count(B);
     const dim3 grid(P, (C + MATE_CS - 1) / MATE_CS);

@@ -5,6 +5,7 @@
 #include <cstdio>
 
 #include "edgl_common.h"
+#include "lds_limit.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -17,6 +18,18 @@ extern "C" void edgl_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* edgl_last_error(void) { return g_err; }
+
+int edgl_lds_limit(const void* kern, size_t bytes, const char* who) {
+    static LdsLimitMemo memo;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    const int e = memo.ensure(kern, dev, bytes, [](const void* k, size_t b) {
+        return (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);   // hipSuccess is 0
+    });
+    if (e == 0) return EDGL_OK;
+    edgl_set_error("%s: cannot raise the dynamic-LDS limit to %zu B: %s", who, bytes, hipGetErrorString((hipError_t)e));
+    return EDGL_ERR_LAUNCH;
+}
 
 // ---- one-shot event bracket -----------------------------------------------------------------------------------
 namespace {

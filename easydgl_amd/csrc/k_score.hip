@@ -1267,7 +1267,7 @@ int run_fwd(ScoreP p, hipStream_t st) {
     const size_t smem = 2 * (S::Z_BYTES + S::ZB * sizeof(float));
     static_assert(2 * (S::Z_BYTES + S::ZB * sizeof(float)) <= 160 * 1024, "forward tile images exceed the LDS");
     auto k = score_fwd_kernel<T, CT>;
-    hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(k, smem, "edgl_score_lse_fwd");
     hipLaunchKernelGGL(k, dim3(xblocks_of(p.R, XB) * p.nchunk), dim3(SNT), smem, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -1340,11 +1340,11 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
             if (rc) return rc;
         } else if (nw == 8) {
             auto k = score_bwd_kernel<T, CT, RY, 8, CO>;
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_nw);
+            EDGL_LDS_LIMIT(k, smem_nw, "edgl_score backward (row pass)");
             hipLaunchKernelGGL(k, dim3(G, CT / CO), dim3(512), smem_nw, st, q);
         } else {
             auto k = score_bwd_kernel<T, CT, RY, 4>;
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_nw);
+            EDGL_LDS_LIMIT(k, smem_nw, "edgl_score backward (row pass)");
             hipLaunchKernelGGL(k, dim3(G), dim3(256), smem_nw, st, q);
         }
         edgl_prof_end(EDGL_KERNEL_SCORE_BWD_ROWS, st);
@@ -1407,11 +1407,11 @@ int run_bwd_mode(ScoreP p, const BwdPlan& plan, float* ws, void* d_rows, float* 
             }
         } else if (nw == 8) {
             auto k = score_bwd_kernel<T, CT, ROLE_W, 8, CO>;
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_nw);
+            EDGL_LDS_LIMIT(k, smem_nw, "edgl_score backward (table pass)");
             hipLaunchKernelGGL(k, dim3(xblocks_of(p.i1 - p.i0, xb), q.nchunk, CT / CO), dim3(512), smem_nw, st, q);
         } else {
             auto k = score_bwd_kernel<T, CT, ROLE_W, 4>;
-            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_nw);
+            EDGL_LDS_LIMIT(k, smem_nw, "edgl_score backward (table pass)");
             hipLaunchKernelGGL(k, dim3(xblocks_of(p.i1 - p.i0, xb), q.nchunk), dim3(256), smem_nw, st, q);
         }
         EDGL_LAUNCH_CHECK();

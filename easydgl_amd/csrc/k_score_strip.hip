@@ -603,8 +603,7 @@ int edgl_strip_rows(const void* rows, const void* table, const float* out_bias, 
     p.rows = (const bf16*)rows; p.table = (const bf16*)table; p.out_bias = out_bias; p.R = R; p.I = I; p.i0 = i0; p.i1 = i1;
     p.nvalid = nvalid; p.slabs = slabs; p.part = part; p.stamps = g_strip_stamps;
     auto k = strip::strip_kernel<strip::ROLE_YF>;
-    static std::atomic<uint64_t> attr_done;
-    edgl_strip_set_smem_attr((const void*)k, strip::SMEM, attr_done);
+    EDGL_LDS_LIMIT(k, strip::SMEM, "edgl_strip_rows");
     hipLaunchKernelGGL(k, dim3(G), dim3(strip::NTHR), strip::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -618,8 +617,7 @@ int edgl_strip_table(const void* rows, const void* table, const float* out_bias,
     p.rows = (const bf16*)rows; p.table = (const bf16*)table; p.out_bias = out_bias; p.R = R; p.I = I; p.i0 = i0; p.i1 = i1;
     p.nvalid = nvalid; p.coef = coef; p.row_lse = row_lse; p.slabs = slabs; p.bias_slabs = bias_slabs; p.stamps = g_strip_stamps;
     auto k = strip::strip_kernel<strip::ROLE_W>;
-    static std::atomic<uint64_t> attr_done;
-    edgl_strip_set_smem_attr((const void*)k, strip::SMEM, attr_done);
+    EDGL_LDS_LIMIT(k, strip::SMEM, "edgl_strip_table");
     hipLaunchKernelGGL(k, dim3((i1 - i0 + strip::XB - 1) / strip::XB, nchunk), dim3(strip::NTHR), strip::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;

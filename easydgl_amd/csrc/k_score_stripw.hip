@@ -879,15 +879,13 @@ int edgl_stripw_rows(const void* rows, const void* table, const float* out_bias,
     p.nvalid = nvalid; p.slabs = slabs; p.part = part; p.cinfo = info_ws; p.ncinfo = n;
     if (C == 512) {
         auto k5 = stripw::stripw5_kernel<stripw::ROLE_YF>;
-        static std::atomic<uint64_t> attr_done5;
-        edgl_strip_set_smem_attr((const void*)k5, stripw::C5::SMEM, attr_done5);
+        EDGL_LDS_LIMIT(k5, stripw::C5::SMEM, "edgl_stripw_rows");
         hipLaunchKernelGGL(k5, dim3(2 * G), dim3(stripw::NTHR), stripw::C5::SMEM, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
     }
     auto k = stripw::stripw_kernel<stripw::ROLE_YF, 256>;
-    static std::atomic<uint64_t> attr_done;
-    edgl_strip_set_smem_attr((const void*)k, stripw::W<256>::SMEM, attr_done);
+    EDGL_LDS_LIMIT(k, stripw::W<256>::SMEM, "edgl_stripw_rows");
     hipLaunchKernelGGL(k, dim3(G), dim3(stripw::NTHR), stripw::W<256>::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -905,15 +903,13 @@ int edgl_stripw_table(const void* rows, const void* table, const float* out_bias
     p.nvalid = nvalid; p.slabs = slabs; p.bias_slabs = bias_slabs; p.cinfo = info_ws; p.ncinfo = n;
     if (C == 512) {
         auto k5 = stripw::stripw5_kernel<stripw::ROLE_W>;
-        static std::atomic<uint64_t> attr_done5;
-        edgl_strip_set_smem_attr((const void*)k5, stripw::C5::SMEM, attr_done5);
+        EDGL_LDS_LIMIT(k5, stripw::C5::SMEM, "edgl_stripw_table");
         hipLaunchKernelGGL(k5, dim3((i1 - i0 + stripw::XB - 1) / stripw::XB, nchunk, 2), dim3(stripw::NTHR), stripw::C5::SMEM, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
     }
     auto k = stripw::stripw_kernel<stripw::ROLE_W, 256>;
-    static std::atomic<uint64_t> attr_done;
-    edgl_strip_set_smem_attr((const void*)k, stripw::W<256>::SMEM, attr_done);
+    EDGL_LDS_LIMIT(k, stripw::W<256>::SMEM, "edgl_stripw_table");
     hipLaunchKernelGGL(k, dim3((i1 - i0 + stripw::XB - 1) / stripw::XB, nchunk), dim3(stripw::NTHR), stripw::W<256>::SMEM, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;

@@ -301,20 +301,6 @@ int tahe_check(const char* who, int B, int T, int C, int dtype) {
     return EDGL_OK;
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device): the attribute is per device
-template <typename K>
-int tahe_lds_attr(K kern, int slot, size_t smem) {
-    static size_t set_for[4][16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (smem > 48 * 1024 && set_for[slot][dev] < smem) {
-        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        EDGL_REQUIRE(e == hipSuccess, EDGL_ERR_LAUNCH, "edgl_tahe: cannot raise the LDS limit: %s", hipGetErrorString(e));
-        set_for[slot][dev] = 160 * 1024;
-    }
-    return EDGL_OK;
-}
-
 }  // namespace
 
 extern "C" int edgl_tahe_fwd(const void* R, const void* Hs, int B, int T, int C, void* hist, int dtype, void* stream) {
@@ -325,12 +311,10 @@ extern "C" int edgl_tahe_fwd(const void* R, const void* Hs, int B, int T, int C,
     const size_t smem = tahe_smem(T, false);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == EDGL_F32) {
-        const int r2 = tahe_lds_attr(tahe_fwd_kernel<float>, 0, smem);
-        if (r2 != EDGL_OK) return r2;
+        EDGL_LDS_LIMIT(tahe_fwd_kernel<float>, smem, "edgl_tahe_fwd");
         hipLaunchKernelGGL((tahe_fwd_kernel<float>), dim3(B), dim3(TAHE_THREADS), smem, st, p);
     } else {
-        const int r2 = tahe_lds_attr(tahe_fwd_kernel<bf16>, 1, smem);
-        if (r2 != EDGL_OK) return r2;
+        EDGL_LDS_LIMIT(tahe_fwd_kernel<bf16>, smem, "edgl_tahe_fwd");
         hipLaunchKernelGGL((tahe_fwd_kernel<bf16>), dim3(B), dim3(TAHE_THREADS), smem, st, p);
     }
     EDGL_LAUNCH_CHECK();
@@ -346,12 +330,10 @@ extern "C" int edgl_tahe_bwd(const void* R, const void* Hs, const void* d_hist, 
     const size_t smem = tahe_smem(T, true);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == EDGL_F32) {
-        const int r2 = tahe_lds_attr(tahe_bwd_kernel<float>, 2, smem);
-        if (r2 != EDGL_OK) return r2;
+        EDGL_LDS_LIMIT(tahe_bwd_kernel<float>, smem, "edgl_tahe_bwd");
         hipLaunchKernelGGL((tahe_bwd_kernel<float>), dim3(B), dim3(TAHE_THREADS), smem, st, p);
     } else {
-        const int r2 = tahe_lds_attr(tahe_bwd_kernel<bf16>, 3, smem);
-        if (r2 != EDGL_OK) return r2;
+        EDGL_LDS_LIMIT(tahe_bwd_kernel<bf16>, smem, "edgl_tahe_bwd");
         hipLaunchKernelGGL((tahe_bwd_kernel<bf16>), dim3(B), dim3(TAHE_THREADS), smem, st, p);
     }
     EDGL_LAUNCH_CHECK();

@@ -13,7 +13,6 @@
 // LayerNorm reads them, two-pass moments, the same dropout element indices), so both paths produce the same tensors.
 // bf16, C in {64, 128}, T <= 112.
 #include "edgl_common.h"
-#include <mutex>      // std::once_flag
 
 #ifdef EDGL_PHASE_TIMING
 __device__ unsigned long long g_phase_cycles[16];   // see edgl_common.h (PH_MARK); read back with edgl_debug_phase_cycles_tail
@@ -1602,33 +1601,6 @@ extern "C" int edgl_tail_variant(int variant) {
     return prev;
 }
 
-// The dynamic-LDS limit of every tail kernel, raised once per device (a once-flag each), not on every launch
-static bool tail_lds_attrs() {
-    constexpr int MAXDEV = 64;
-    static std::once_flag once[MAXDEV];
-    static bool ok[MAXDEV] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return false;
-    std::call_once(once[dev], [dev] {
-        bool good = true;
-        auto set = [&](const void* f, size_t bytes) { good = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess && good; };
-        set((const void*)tail_fwd_kernel<8, 2>, TailGeom<8>::SMEM_FWD); set((const void*)tail_fwd_kernel<8, 4>, TailGeom<8>::SMEM_FWD);
-        set((const void*)tail_fwd_kernel<8, MAXRT>, TailGeom<8>::SMEM_FWD);
-        set((const void*)tail_fwd_kernel<4, 2>, TailGeom<4>::SMEM_FWD); set((const void*)tail_fwd_kernel<4, 4>, TailGeom<4>::SMEM_FWD);
-        set((const void*)tail_fwd_kernel<4, MAXRT>, TailGeom<4>::SMEM_FWD);
-        set((const void*)tail_bwd_kernel<8, 2>, TailGeom<8>::SMEM_BWD); set((const void*)tail_bwd_kernel<8, 4>, TailGeom<8>::SMEM_BWD);
-        set((const void*)tail_bwd_kernel<8, MAXRT>, TailGeom<8>::SMEM_BWD);
-        set((const void*)tail_bwd_kernel<4, 2>, TailGeom<4>::SMEM_BWD); set((const void*)tail_bwd_kernel<4, 4>, TailGeom<4>::SMEM_BWD);
-        set((const void*)tail_bwd_kernel<4, MAXRT>, TailGeom<4>::SMEM_BWD);
-        set((const void*)t2::tail2_fwd_kernel<2>, t2::SMEM_FWD); set((const void*)t2::tail2_fwd_kernel<4>, t2::SMEM_FWD);
-        set((const void*)t2::tail2_fwd_kernel<MAXRT>, t2::SMEM_FWD);
-        set((const void*)t2::tail2_bwd_kernel<2>, t2::SMEM_BWD_ALL); set((const void*)t2::tail2_bwd_kernel<4>, t2::SMEM_BWD_ALL);
-        set((const void*)t2::tail2_bwd_kernel<MAXRT>, t2::SMEM_BWD_ALL);
-        ok[dev] = good;
-    });
-    return ok[dev];      // (a failed set is reported by every launch, not retried)
-}
-
 extern "C" long edgl_tail_pack_elems(int C) { return 6L * C * C; }
 
 extern "C" int edgl_tail_supported(int T, int C, int dtype) { return dtype == EDGL_BF16 && (C == 64 || C == 128) && T >= 1 && T <= 16 * MAXRT; }
@@ -1667,7 +1639,7 @@ extern "C" int edgl_tail_fwd_ct(const void* att, const void* xin, int ld_x, cons
     const int nrt = (T + 15) / 16;
     if (tail2_enabled() && C == 128 && T <= t2::TMAX) {      // two workgroups per CU (see namespace t2)
         auto k2 = nrt <= 2 ? t2::tail2_fwd_kernel<2> : nrt <= 4 ? t2::tail2_fwd_kernel<4> : t2::tail2_fwd_kernel<MAXRT>;
-        EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_fwd (two per CU): hipFuncSetAttribute failed on this device");
+        EDGL_LDS_LIMIT(k2, t2::SMEM_FWD, "edgl_tail_fwd (two per CU)");
         hipLaunchKernelGGL(k2, dim3(B), dim3(t2::NTHR), t2::SMEM_FWD, st, p);
         EDGL_LAUNCH_CHECK();
         return EDGL_OK;
@@ -1675,7 +1647,7 @@ extern "C" int edgl_tail_fwd_ct(const void* att, const void* xin, int ld_x, cons
     auto k = C == 128 ? (nrt <= 2 ? tail_fwd_kernel<8, 2> : nrt <= 4 ? tail_fwd_kernel<8, 4> : tail_fwd_kernel<8, MAXRT>)
                       : (nrt <= 2 ? tail_fwd_kernel<4, 2> : nrt <= 4 ? tail_fwd_kernel<4, 4> : tail_fwd_kernel<4, MAXRT>);
     const size_t smem = C == 128 ? TailGeom<8>::SMEM_FWD : TailGeom<4>::SMEM_FWD;
-    EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_fwd (one per CU): hipFuncSetAttribute failed on this device");
+    EDGL_LDS_LIMIT(k, smem, "edgl_tail_fwd (one per CU)");
     hipLaunchKernelGGL(k, dim3(B), dim3(C == 128 ? 512 : 256), smem, st, p);
     EDGL_LAUNCH_CHECK();
     return EDGL_OK;
@@ -1714,15 +1686,16 @@ extern "C" int edgl_tail_bwd_ct(const void* xin, int ld_x, const void* ao, const
                (bf16*)d_pre_t, (bf16*)d_o, (bf16*)d_pre_f, (bf16*)d_ao, (bf16*)d_res1, (bf16*)d_att, part1, part2, part3, dh_pad, dh_true};
     hipStream_t st = (hipStream_t)stream;
     const int nrt = (T + 15) / 16;
-    EDGL_REQUIRE(tail_lds_attrs(), EDGL_ERR_LAUNCH, "edgl_tail_bwd: hipFuncSetAttribute failed on this device");
     // two workgroups per CU (see namespace t2); the unstaged head path (M > 112) keeps the one-per-CU kernel
     if (tail2_enabled() && C == 128 && T <= t2::TMAX && (!head || M <= MAXRT * 16)) {
         auto k2 = nrt <= 2 ? t2::tail2_bwd_kernel<2> : nrt <= 4 ? t2::tail2_bwd_kernel<4> : t2::tail2_bwd_kernel<MAXRT>;
+        EDGL_LDS_LIMIT(k2, t2::SMEM_BWD_ALL, "edgl_tail_bwd (two per CU)");
         hipLaunchKernelGGL(k2, dim3(B), dim3(t2::NTHR), t2::SMEM_BWD_ALL, st, p);
     } else {
         auto k = C == 128 ? (nrt <= 2 ? tail_bwd_kernel<8, 2> : nrt <= 4 ? tail_bwd_kernel<8, 4> : tail_bwd_kernel<8, MAXRT>)
                           : (nrt <= 2 ? tail_bwd_kernel<4, 2> : nrt <= 4 ? tail_bwd_kernel<4, 4> : tail_bwd_kernel<4, MAXRT>);
         const size_t smem = C == 128 ? TailGeom<8>::SMEM_BWD : TailGeom<4>::SMEM_BWD;
+        EDGL_LDS_LIMIT(k, smem, "edgl_tail_bwd (one per CU)");
         hipLaunchKernelGGL(k, dim3(B), dim3(C == 128 ? 512 : 256), smem, st, p);
     }
     EDGL_LAUNCH_CHECK();

@@ -615,7 +615,7 @@ template <typename K>
 int launch_ti(K kern, const TaP& p, const TiP& t, size_t wave_bytes, hipStream_t st) {
     const size_t smem = 4 * wave_bytes;
     EDGL_REQUIRE(smem <= 160 * 1024, EDGL_ERR_SHAPE, "edgl_tiattn: timelen %d needs %zu B of LDS", t.timelen, smem);
-    if (smem > 48 * 1024) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    EDGL_LDS_LIMIT(kern, smem, "edgl_tiattn");
     return launch_jobs(kern, p, 1, 4, smem, st, t);
 }
 constexpr int TI_SPLITS = 32;      // row splits of the interval-table gradients

@@ -2,8 +2,6 @@
 // (k_score_strip.hip, k_score_stripw.hip), so that a drifted prototype is a compile error and not a silent overload.
 #pragma once
 
-#include <atomic>
-
 #include "edgl_common.h"
 
 // k_score_strip.hip: one-wave-per-SIMD form of the two product passes (bf16, C = 128)
@@ -25,18 +23,3 @@ int edgl_stripw_table(const void* rows, const void* table, const float* out_bias
 // k_score_stripw.hip: the one-hot term the ROLE_W pass of either file leaves out, C = 128 / 256 / 512
 int edgl_strip_label_scatter(const void* rows, const int64_t* labels, const float* coef, const int32_t* nvalid, int R, int C, int i0,
                              int i1, const float* gscale, float* d_table, float* d_bias, hipStream_t st);
-
-// The dynamic-LDS attribute of a kernel is PER DEVICE: `done` is the memo of ONE kernel, a bit per device ordinal, set with an
-// atomic so that two host threads driving different GPUs neither skip nor race it (a process-wide bool left the second device
-// without the attribute).
-inline void edgl_strip_set_smem_attr(const void* kern, int bytes, std::atomic<uint64_t>& done) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {   // unknown ordinal: set it on every launch
-        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        return;
-    }
-    const uint64_t bit = 1ull << dev;
-    if (done.load(std::memory_order_acquire) & bit) return;
-    hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done.fetch_or(bit, std::memory_order_release);
-}

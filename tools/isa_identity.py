@@ -37,6 +37,11 @@ def short_name(mangled):
     return "::".join(parts) + ("<%s>" % ", ".join(re.findall(r"Li(\d+)E", t.group(1))) if t else "")
 
 
+def label(demangled):
+    """the name without its argument list; "(anonymous namespace)::" goes first, or the cut at the first parenthesis leaves nothing"""
+    return re.sub(r"\(.*", "", demangled.replace("(anonymous namespace)::", ""))
+
+
 def norm(line):
     line = line.split(";")[0].rstrip()
     s = line.strip()
@@ -101,7 +106,7 @@ def main():
         for a, b in aliases:
             if partner is None and (a in name or a in dm[name]):
                 partner = next((n for n in new if b in n or b in dm[n]), None)
-        short = re.sub(r"\(.*", "", dm[name])
+        short = label(dm[name])
         fo = old[name]
         res_o = " ".join(fo.get(s, "-") for _, s in RES)
         if partner is None:
@@ -113,10 +118,10 @@ def main():
         same = fo["body"] == fn["body"] and fo["desc"] == fn["desc"]
         bad += not same
         if partner != name:
-            short += " -> " + re.sub(r"\(.*", "", dm[partner])
+            short += " -> " + label(dm[partner])
         print("%-80s %6d %9s  %s -> %s" % (short, fo["n"], "yes" if same else "NO", res_o, " ".join(fn.get(s, "-") for _, s in RES)))
     for name in sorted(set(new) - used, key=lambda n: dm[n]):
-        print("%-80s %6d %9s  (new function)" % (re.sub(r"\(.*", "", dm[name]), new[name]["n"], "NEW"))
+        print("%-80s %6d %9s  (new function)" % (label(dm[name]), new[name]["n"], "NEW"))
         bad += 1
     sys.exit(1 if bad else 0)
 
