@@ -23,6 +23,7 @@ MAU_CAUSAL, MAU_NO_DIAG, MAU_DIAG_ZERO = 1, 2, 4
 MAU_NO_SKIP = 8      # host-side hint (include/easydgl_hip.h): the unskipped BiMAU kernels
 MAU_STREAM = 16      # host-side hint: the key-streamed BiMAU kernels at a shape the in-register kernels also take
 TATTN_CAUSAL = 1
+LOSS_SOFTMAX, LOSS_BCE, LOSS_BPR = 0, 1, 2    # EDGL_LOSS_*: the objective over sampled slots
 TATTN_ORDERED = 2    # interval attention: the LDS bins filled in a fixed order, no f32 atomics
 
 P, I, F, L, U32, I64, U64 = c_void_p, c_int, c_float, c_long, c_uint32, c_int64, c_uint64
@@ -141,6 +142,10 @@ SIGNATURES = {
     "edgl_shared_ce_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "edgl_shared_ce_fwd_q": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, I, P]),
     "edgl_shared_ce_bwd": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
+    "edgl_sampled_row_loss": (I, [P, P, P, P, I, I, I, I, P, P, P, P]),
+    "edgl_sampled_loss_finish": (I, [P, P, P, P, I, I, P, P, P]),
+    "edgl_cand_ce_bwd_form": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, I, I, P]),
+    "edgl_shared_ce_bwd_form": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, I, I, P]),
     "edgl_rank_metrics_from_rank_rows": (I, [P, I, P, I, P, P]),
     "edgl_topk_merge": (I, [P, P, I, I, I, P, P, P]),
     "edgl_rank_metrics": (I, [P, I, I, P, P, P]),

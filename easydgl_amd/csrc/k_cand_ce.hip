@@ -32,7 +32,12 @@
 // Rows with label 0 leave by a block-uniform exit (no compaction: a row's list never depends on which other rows are weighted); their
 // vals read -inf, their lse / label_val 0 and their d_rows / dv are written as zeros.  A label outside [0, I) is a caller error and
 // the row is skipped the same way.
+//
+// Other objectives over the same slots (sampled_dv.h): the forward is unchanged (its lse is not used), the row losses come
+// from k_sampled_loss.hip, and cand_ce_bwd_kernel<.., FORM> forms dv by the form's rule in its two sweeps — everything behind dv
+// is the code above.  FORM = softmax is today's kernel, bit for bit.
 #include "edgl_common.h"
+#include "sampled_dv.h"
 #include "cand_gather.h"
 
 namespace cce {
@@ -45,7 +50,8 @@ struct P {
     const void* rows; const void* table; const float* bias; const int32_t* cand; const int64_t* labels;
     const float* logq;                                               // forward only: [I] or NULL
     int R, C, I, N;
-    float* vals; float* label_val; float* lse;                       // forward: outputs; backward: vals / lse are inputs
+    float* vals; float* label_val; float* lse;                       // forward: outputs; backward: vals / lse are inputs (lse: the
+                                                                     // row auxiliary of a form other than softmax)
     const float* coef; const float* gscale;
     void* d_rows; float* dv; float* d_table; float* d_bias;
 };
@@ -147,7 +153,8 @@ __global__ __launch_bounds__(256) void cand_ce_fwd_kernel(P p) {
     }
 }
 
-template <typename T, int G, int PPL>
+// FORM: the objective whose dv is formed (sampled_dv.h); L is lse[r] (softmax) or the row auxiliary (bpr: sum_s sigma(v_s - v_0))
+template <typename T, int G, int PPL, int FORM>
 __global__ __launch_bounds__(256) void cand_ce_bwd_kernel(P p) {
     constexpr int VEC = 16 / sizeof(T);
     constexpr int RPW = 64 / G;
@@ -183,7 +190,8 @@ __global__ __launch_bounds__(256) void cand_ce_bwd_kernel(P p) {
             for (int e = 0; e < VEC; ++e) acc[pp][e] = fmaf(d, z[e], acc[pp][e]);
         }
     };
-    const float dv0 = gc * (__expf(vrow[0] - L) - 1.0f);
+    const float v0 = vrow[0];
+    const float dv0 = sdv::dv_label<FORM>(gc, v0, L);
     if (wave == 0 && grp == 0) {              // the label slot: the first term of wave 0's first lane group
         uint4 w[PPL];
         load_pieces<T, G, PPL>(table, y, p.C, gl, w);
@@ -220,7 +228,7 @@ __global__ __launch_bounds__(256) void cand_ce_bwd_kernel(P p) {
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
             const bool live = v[u] > -INFINITY;               // (the forward's test: empty, past I and accidental hits read -inf)
-            const float d = live ? gc * __expf(v[u] - L) : 0.0f;
+            const float d = live ? sdv::dv_slot<FORM>(gc, v[u], v0, L) : 0.0f;
             add_row(w[u], live && c[u] > 0, d);
             const int n = slot_of(base, u);
             if (gl == 0 && n < N) dvrow[1 + n] = d;
@@ -265,7 +273,7 @@ __global__ __launch_bounds__(256) void cand_ce_bwd_kernel(P p) {
         const float v = vrow[s0];
         const int c = s0 == 0 ? y : crow[s0 - 1];
         if (!(v > -INFINITY) || c < 1 || c >= p.I) continue;  // dead slot, or item 0 (its table row and bias are no parameters)
-        const float d = s0 == 0 ? dv0 : gc * __expf(v - L);   // (the bits written to dv)
+        const float d = s0 == 0 ? dv0 : sdv::dv_slot<FORM>(gc, v, v0, L);     // (the bits written to dv)
         float* dst = p.d_table + (long)c * p.C;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -290,8 +298,10 @@ __global__ __launch_bounds__(256) void cand_ce_keys_kernel(const int32_t* cand, 
 }
 
 template <typename T, int G, int PPL>
-int launch(const P& p, bool bwd, hipStream_t st) {
-    if (bwd) hipLaunchKernelGGL((cand_ce_bwd_kernel<T, G, PPL>), dim3((unsigned)p.R), dim3(256), 0, st, p);
+int launch(const P& p, bool bwd, int form, hipStream_t st) {
+    if (bwd && form == sdv::BCE) hipLaunchKernelGGL((cand_ce_bwd_kernel<T, G, PPL, sdv::BCE>), dim3((unsigned)p.R), dim3(256), 0, st, p);
+    else if (bwd && form == sdv::BPR) hipLaunchKernelGGL((cand_ce_bwd_kernel<T, G, PPL, sdv::BPR>), dim3((unsigned)p.R), dim3(256), 0, st, p);
+    else if (bwd) hipLaunchKernelGGL((cand_ce_bwd_kernel<T, G, PPL, sdv::SOFTMAX>), dim3((unsigned)p.R), dim3(256), 0, st, p);
     else if (p.logq) hipLaunchKernelGGL((cand_ce_fwd_kernel<T, G, PPL, true>), dim3((unsigned)p.R), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((cand_ce_fwd_kernel<T, G, PPL, false>), dim3((unsigned)p.R), dim3(256), 0, st, p);
     EDGL_LAUNCH_CHECK();
@@ -299,19 +309,19 @@ int launch(const P& p, bool bwd, hipStream_t st) {
 }
 
 template <typename T>
-int dispatch(const P& p, bool bwd, hipStream_t st) {
+int dispatch(const P& p, bool bwd, int form, hipStream_t st) {
     const int pieces = p.C / (int)(16 / sizeof(T));
     if constexpr (sizeof(T) == 4) {           // (only f32 rows exceed 64 pieces; only bf16 rows have two)
-        if (pieces > 64) return launch<T, 64, 2>(p, bwd, st);
+        if (pieces > 64) return launch<T, 64, 2>(p, bwd, form, st);
     }
     switch (group_of(pieces)) {
         case 2:
-            if constexpr (sizeof(T) == 2) return launch<T, 2, 1>(p, bwd, st);
-        case 4: return launch<T, 4, 1>(p, bwd, st);
-        case 8: return launch<T, 8, 1>(p, bwd, st);
-        case 16: return launch<T, 16, 1>(p, bwd, st);
-        case 32: return launch<T, 32, 1>(p, bwd, st);
-        default: return launch<T, 64, 1>(p, bwd, st);
+            if constexpr (sizeof(T) == 2) return launch<T, 2, 1>(p, bwd, form, st);
+        case 4: return launch<T, 4, 1>(p, bwd, form, st);
+        case 8: return launch<T, 8, 1>(p, bwd, form, st);
+        case 16: return launch<T, 16, 1>(p, bwd, form, st);
+        case 32: return launch<T, 32, 1>(p, bwd, form, st);
+        default: return launch<T, 64, 1>(p, bwd, form, st);
     }
 }
 
@@ -339,7 +349,7 @@ extern "C" int edgl_cand_ce_fwd_q(const void* rows, const void* table, const flo
     p.logq = logq;
     p.vals = vals; p.label_val = label_val; p.lse = row_lse;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_BF16 ? cce::dispatch<bf16>(p, false, st) : cce::dispatch<float>(p, false, st);
+    return dtype == EDGL_BF16 ? cce::dispatch<bf16>(p, false, 0, st) : cce::dispatch<float>(p, false, 0, st);
 }
 
 extern "C" int edgl_cand_ce_fwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
@@ -347,11 +357,17 @@ extern "C" int edgl_cand_ce_fwd(const void* rows, const void* table, const float
     return edgl_cand_ce_fwd_q(rows, table, out_bias, nullptr, cand, labels, R, C, I, N, vals, label_val, row_lse, dtype, stream);
 }
 
-extern "C" int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
-                                const float* vals, const float* row_lse, const float* coef, const float* gscale, int R, int C, int I,
-                                int N, void* d_rows, float* dv, float* d_table, float* d_bias, int dtype, void* stream) {
+// form: EDGL_LOSS_SOFTMAX (row_aux = row_lse; edgl_cand_ce_bwd forwards here), EDGL_LOSS_BCE, EDGL_LOSS_BPR (row_aux of
+// edgl_sampled_row_loss)
+extern "C" int edgl_cand_ce_bwd_form(const void* rows, const void* table, const float* out_bias, const int32_t* cand,
+                                     const int64_t* labels, const float* vals, const float* row_aux, const float* coef,
+                                     const float* gscale, int R, int C, int I, int N, void* d_rows, float* dv, float* d_table,
+                                     float* d_bias, int form, int dtype, void* stream) {
+    const float* row_lse = row_aux;
     const int rc = cce::check_shape("edgl_cand_ce_bwd", rows, table, R, C, I, N, dtype);
     if (rc) return rc;
+    EDGL_REQUIRE(form >= sdv::SOFTMAX && form <= sdv::BPR, EDGL_ERR_SHAPE, "edgl_cand_ce_bwd: form %d (0 <= form <= %d: softmax, bce, bpr)",
+                 form, sdv::BPR);
     EDGL_REQUIRE(rows && table && out_bias && cand && labels && vals && row_lse && coef && d_rows && dv, EDGL_ERR_NULL,
                  "edgl_cand_ce_bwd: null pointer");
     EDGL_REQUIRE(!d_table == !d_bias, EDGL_ERR_NULL, "edgl_cand_ce_bwd: d_table and d_bias go together (both NULL: dv only)");
@@ -361,7 +377,14 @@ extern "C" int edgl_cand_ce_bwd(const void* rows, const void* table, const float
     p.vals = const_cast<float*>(vals); p.lse = const_cast<float*>(row_lse); p.coef = coef; p.gscale = gscale;
     p.d_rows = d_rows; p.dv = dv; p.d_table = d_table; p.d_bias = d_bias;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_BF16 ? cce::dispatch<bf16>(p, true, st) : cce::dispatch<float>(p, true, st);
+    return dtype == EDGL_BF16 ? cce::dispatch<bf16>(p, true, form, st) : cce::dispatch<float>(p, true, form, st);
+}
+
+extern "C" int edgl_cand_ce_bwd(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
+                                const float* vals, const float* row_lse, const float* coef, const float* gscale, int R, int C, int I,
+                                int N, void* d_rows, float* dv, float* d_table, float* d_bias, int dtype, void* stream) {
+    return edgl_cand_ce_bwd_form(rows, table, out_bias, cand, labels, vals, row_lse, coef, gscale, R, C, I, N, d_rows, dv, d_table,
+                                 d_bias, EDGL_LOSS_SOFTMAX, dtype, stream);
 }
 
 extern "C" int edgl_cand_ce_table_det(const void* rows, const int32_t* cand, const int64_t* labels, const float* dv, int R, int C, int I,

@@ -34,8 +34,13 @@
 //   deterministic label term: an ordered sum over a k_segsum.hip plan of the labels (edgl_segsum_cand with two entries per row:
 //                         the label with dv_label, and a dropped key 0).
 // Rows of weight 0 (label outside [1, I), or at / past nvalid[0] of a compacted batch): vals -inf, label_val = lse = 0, d_rows zero.
+//
+// Other objectives over the same slots (sampled_dv.h): the forward is unchanged (its lse is not used), the row losses come
+// from k_sampled_loss.hip and shared_dv_kernel<T, FORM> forms dv and dv_label by the form's rule; everything behind dv is the code
+// above.  FORM = softmax is today's kernel, bit for bit.
 #include "cand_gather.h"
 #include "gemm_tile.h"
+#include "sampled_dv.h"
 
 namespace sce {
 
@@ -237,7 +242,9 @@ __device__ __forceinline__ void store_quad(T* dst, const float (&x)[4]) {
 }
 
 // dvt [R, Sp] (compute dtype), dvl[2 r] = dv_label, dvl[2 r + 1] = 0, keys[2 r] = the label of a weighted row (else 0), keys[2 r + 1] = 0
-template <typename T>
+// FORM: the objective whose dv is formed (sampled_dv.h); L is lse[r] (softmax) or the row auxiliary of another form.
+// The pad columns s >= S and the dead slots are written as zeros whatever the form.
+template <typename T, int FORM>
 __global__ __launch_bounds__(256) void shared_dv_kernel(P p) {
     const int q4 = p.Sp >> 2, nlive = nlive_of(p);
     const long n = (long)p.R * q4;
@@ -248,15 +255,16 @@ __global__ __launch_bounds__(256) void shared_dv_kernel(P p) {
         const int64_t y = p.labels[r];
         const bool w = r < nlive && y >= 1 && y < p.I;
         const float gc = w ? g * p.coef[r] : 0.0f, L = p.lse[r];
+        const float v0 = FORM == sdv::BPR ? p.label_val[r] : 0.0f;
         float d[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float v = (w && s + k < p.S) ? p.vals[(long)r * p.S + s + k] : -INFINITY;
-            d[k] = v > -INFINITY ? gc * __expf(v - L) : 0.0f;         // (the forward's test: dead slots read -inf)
+            d[k] = v > -INFINITY ? sdv::dv_slot<FORM>(gc, v, v0, L) : 0.0f;       // (the forward's test: dead slots read -inf)
         }
         store_quad<T>(dvt + (long)r * p.Sp + s, d);
         if (s == 0) {
-            *reinterpret_cast<float2*>(p.dvl + 2L * r) = make_float2(w ? gc * (__expf(p.label_val[r] - L) - 1.0f) : 0.0f, 0.0f);
+            *reinterpret_cast<float2*>(p.dvl + 2L * r) = make_float2(w ? sdv::dv_label<FORM>(gc, p.label_val[r], L) : 0.0f, 0.0f);
             if (p.keys) { p.keys[2L * r] = w ? y : 0; p.keys[2L * r + 1] = 0; }
         }
     }
@@ -379,11 +387,14 @@ inline Layout layout(int R, int C, int S, int dtype) {
 }
 
 template <typename T>
-int backward(P p, float* ws, void* plan, int dtype, hipStream_t st) {
+int backward(P p, float* ws, void* plan, int form, int dtype, hipStream_t st) {
     const Layout L = layout(p.R, p.C, p.S, dtype);
     p.dvt = ws + L.dvt; p.ws_rows = ws + L.rows; p.slab = ws + L.slab; p.bsum = ws + L.bsum; p.dvl = ws + L.dvl;
     float* libws = ws + L.lib;
-    hipLaunchKernelGGL((shared_dv_kernel<T>), dim3((unsigned)grid_for((long)p.R * (p.Sp / 4))), dim3(256), 0, st, p);
+    const dim3 dvgrid((unsigned)grid_for((long)p.R * (p.Sp / 4)));
+    if (form == sdv::BCE) hipLaunchKernelGGL((shared_dv_kernel<T, sdv::BCE>), dvgrid, dim3(256), 0, st, p);
+    else if (form == sdv::BPR) hipLaunchKernelGGL((shared_dv_kernel<T, sdv::BPR>), dvgrid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((shared_dv_kernel<T, sdv::SOFTMAX>), dvgrid, dim3(256), 0, st, p);
     hipLaunchKernelGGL((shared_rows_kernel<T>), dim3((unsigned)grid_for((long)p.Sp * p.C / 4)), dim3(256), 0, st, p);
     EDGL_LAUNCH_CHECK();
     // d_rows [R, C] = dv [R, Sp] W_S [Sp, C]
@@ -448,12 +459,18 @@ extern "C" int edgl_shared_ce_fwd(const void* rows, const void* table, const flo
     return edgl_shared_ce_fwd_q(rows, table, out_bias, nullptr, shared, labels, nvalid, R, C, I, S, vals, label_val, row_lse, dtype, stream);
 }
 
-extern "C" int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,
-                                  const float* label_val, const float* row_lse, const float* coef, const float* gscale,
-                                  const int32_t* nvalid, int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias,
-                                  float* workspace, int64_t* keys, void* plan, int dtype, void* stream) {
+// form: EDGL_LOSS_SOFTMAX (row_aux = row_lse; edgl_shared_ce_bwd forwards here), EDGL_LOSS_BCE, EDGL_LOSS_BPR (row_aux of
+// edgl_sampled_row_loss)
+extern "C" int edgl_shared_ce_bwd_form(const void* rows, const void* table, const int32_t* shared, const int64_t* labels,
+                                       const float* vals, const float* label_val, const float* row_aux, const float* coef,
+                                       const float* gscale, const int32_t* nvalid, int R, int C, int I, int S, void* d_rows,
+                                       float* d_table, float* d_bias, float* workspace, int64_t* keys, void* plan, int form, int dtype,
+                                       void* stream) {
+    const float* row_lse = row_aux;
     const int rc = sce::check_shape("edgl_shared_ce_bwd", R, C, I, S, dtype);
     if (rc) return rc;
+    EDGL_REQUIRE(form >= sdv::SOFTMAX && form <= sdv::BPR, EDGL_ERR_SHAPE,
+                 "edgl_shared_ce_bwd: form %d (0 <= form <= %d: softmax, bce, bpr)", form, sdv::BPR);
     EDGL_REQUIRE(rows && table && shared && labels && vals && label_val && row_lse && coef && d_rows && d_table && d_bias, EDGL_ERR_NULL,
                  "edgl_shared_ce_bwd: null pointer");
     EDGL_REQUIRE(workspace, EDGL_ERR_WORKSPACE, "edgl_shared_ce_bwd: needs edgl_shared_ce_workspace(R, C, S, dtype) floats");
@@ -466,5 +483,14 @@ extern "C" int edgl_shared_ce_bwd(const void* rows, const void* table, const int
     p.vals = const_cast<float*>(vals); p.label_val = const_cast<float*>(label_val); p.lse = const_cast<float*>(row_lse);
     p.coef = coef; p.gscale = gscale; p.d_rows = d_rows; p.d_table = d_table; p.d_bias = d_bias; p.keys = keys; p.det = plan ? 1 : 0;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == EDGL_BF16 ? sce::backward<bf16>(p, workspace, plan, dtype, st) : sce::backward<float>(p, workspace, plan, dtype, st);
+    return dtype == EDGL_BF16 ? sce::backward<bf16>(p, workspace, plan, form, dtype, st)
+                              : sce::backward<float>(p, workspace, plan, form, dtype, st);
+}
+
+extern "C" int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,
+                                  const float* label_val, const float* row_lse, const float* coef, const float* gscale,
+                                  const int32_t* nvalid, int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias,
+                                  float* workspace, int64_t* keys, void* plan, int dtype, void* stream) {
+    return edgl_shared_ce_bwd_form(rows, table, shared, labels, vals, label_val, row_lse, coef, gscale, nvalid, R, C, I, S, d_rows,
+                                   d_table, d_bias, workspace, keys, plan, EDGL_LOSS_SOFTMAX, dtype, stream);
 }

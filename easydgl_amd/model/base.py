@@ -89,6 +89,13 @@ class Sequential(nn.Module):
         if self.neg_sampler != "uniform" and self.train_negatives <= 0 and self.shared_negatives <= 0:
             raise ValueError(f"neg_sampler={self.neg_sampler!r} needs train_negatives > 0 or shared_negatives > 0: the full softmax "
                              "draws no negatives")
+        # the objective over the sampled slots: softmax, or bce / bpr over the same lists and values
+        self.sampled_loss = str(getattr(FLAGS, "sampled_loss", None) or "softmax")
+        if self.sampled_loss not in ops.LOSS_FORMS:
+            raise ValueError(f"sampled_loss={self.sampled_loss!r}: one of {', '.join(ops.LOSS_FORMS)}")
+        if self.sampled_loss != "softmax" and self.train_negatives <= 0 and self.shared_negatives <= 0:
+            raise ValueError(f"sampled_loss={self.sampled_loss!r} needs train_negatives > 0 or shared_negatives > 0: the objective is "
+                             "defined over sampled negatives, the full softmax draws none")
         self._neg_dist = None   # ops.NegDist over [1, _negatives_hi()): set_negative_weights (log_uniform: built at the first draw)
         # lazy row-wise Adam for the item table: the table's gradient lands in place in the gradient arena and the
         # optimizer walks only the rows the step used
@@ -535,7 +542,9 @@ class Sequential(nn.Module):
         `shared` (int32 [S], one list for every row) or FLAGS.shared_negatives = S > 0: each row's label and the step's ONE list
         (ops.SharedCEFn), drawn once through the same sampler, keyed by (train_neg_seed, neg_step).
         FLAGS.neg_sampler other than "uniform" (DESIGN 4.16): the lists are drawn by the model's weights (set_negative_weights) and
-        every sampled loss — a caller's `candidates` / `shared` too — subtracts log Q(c) from the label's and every slot's logit."""
+        every sampled loss — a caller's `candidates` / `shared` too — subtracts log Q(c) from the label's and every slot's logit.
+        FLAGS.sampled_loss other than "softmax" (DESIGN 4.19): binary cross-entropy or BPR over the same slots and values, for the
+        model's own lists and a caller's alike; lists, log-Q, lazy_adam and deterministic are untouched by the objective."""
         tab = self.item_embs.lookup_table
         if candidates is not None and shared is not None:
             raise ValueError("_score_ce: both `candidates` and `shared` are given: one estimator per call")
@@ -545,6 +554,15 @@ class Sequential(nn.Module):
         # FLAGS.neg_sampler: a non-uniform sampler corrects every sampled loss by log Q, a caller's list included
         dist = self._negative_dist() if sampled else None
         tail = () if dist is None else (dist.logq_on(labels.device),)
+        if sampled and self.sampled_loss != "softmax":
+            tail = (None if dist is None else tail[0], self.sampled_loss)
+            if candidates is None and shared is None:
+                candidates = self._sample(None, labels, self.train_negatives, self.train_neg_seed, self.neg_step, 0, dist)
+            if self.lazy_adam:
+                self._lazy_lists = (labels, candidates, shared)
+            fn, lists = (ops.SharedCEFn, shared) if shared is not None else (ops.SampledCEFn, candidates)
+            return fn.apply(rows, tab, self.output_bias, self.compute(tab), labels, lists, self.deterministic,
+                            self._lazy_grad if self.lazy_adam else None, *tail)
         if shared is not None:
             if self.lazy_adam:
                 self._lazy_lists = (labels, None, shared)

@@ -620,6 +620,61 @@ def _logq_arg(logq, I, device, who):
     return logq
 
 
+LOSS_FORMS = {"softmax": _lib.LOSS_SOFTMAX, "bce": _lib.LOSS_BCE, "bpr": _lib.LOSS_BPR}
+
+
+def _loss_form(form, who):
+    """The code of a sampled objective: "softmax" (the default), "bce" or "bpr"."""
+    if form not in LOSS_FORMS:
+        raise ValueError(f"{who}: form must be one of {sorted(LOSS_FORMS)} (got {form!r})")
+    return LOSS_FORMS[form]
+
+
+def _apply_form(base, args, form):
+    """`.apply` of SampledCEFn / SharedCEFn: the nine arguments of `forward`, then the objective — a tenth positional argument or
+    `form=` ("softmax", the default, "bce", "bpr").  `forward` itself keeps its signature: the objective selects a
+    variant of the function (`_form_variant`) whose forward hands it on, so a call without it is the call it always was."""
+    if len(args) > 9:
+        if form is not None or len(args) > 10:
+            raise TypeError(f"{base.__name__}.apply: at most ten positional arguments, the last of them the form")
+        args, form = args[:9], args[9]
+    code = _loss_form("softmax" if form is None else form, base.__name__)
+    fn = base if code == _lib.LOSS_SOFTMAX else _form_variant(base, form)
+    return super(base, fn).apply(*args)
+
+
+_FORM_VARIANTS = {}
+
+
+def _form_variant(base, form):
+    """The autograd function of `base` (SampledCEFn / SharedCEFn) under another objective: the same forward and backward bodies."""
+    if (base, form) not in _FORM_VARIANTS:
+        class Variant(base):
+            @staticmethod
+            def forward(ctx, *args):
+                return base._forward(ctx, form, *args)
+        Variant.__name__ = Variant.__qualname__ = f"{base.__name__}[{form}]"
+        _FORM_VARIANTS[(base, form)] = Variant
+    return _FORM_VARIANTS[(base, form)]
+
+
+def sampled_row_loss(vals, label_val, labels, nvalid, I, form):
+    """(loss f32 [1], coef f32 [R], row_aux f32 [R], row_loss f32 [R]) of the bce / bpr objective over the values a sampled forward
+    wrote (edgl_sampled_row_loss + edgl_sampled_loss_finish): vals f32 [R, N + 1] with slot 0 the label (label_val None, cand_ce_fwd's)
+    or vals f32 [R, S] with label_val (shared_ce_fwd's).  row_aux goes to the backward where lse went."""
+    code = _loss_form(form, "sampled_row_loss")
+    R = vals.shape[0]
+    S = vals.shape[1] - (1 if label_val is None else 0)
+    dev = vals.device
+    row_loss, row_aux, row_scale, coef = (torch.empty(R, device=dev, dtype=torch.float32) for _ in range(4))
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    check(lib.edgl_sampled_row_loss(_ptr(vals), _ptr(label_val), _ptr(labels), _ptr(nvalid), R, S, I, code, _ptr(row_loss),
+                                    _ptr(row_aux), _ptr(row_scale), _stream()), "edgl_sampled_row_loss")
+    check(lib.edgl_sampled_loss_finish(_ptr(row_loss), _ptr(row_scale), _ptr(labels), _ptr(nvalid), R, I, _ptr(loss), _ptr(coef),
+                                       _stream()), "edgl_sampled_loss_finish")
+    return loss, coef, row_aux, row_loss
+
+
 def cand_ce_fwd(rows, table_c, out_bias, cand, labels, logq=None):
     """(vals f32 [R, N + 1], label_val f32 [R], lse f32 [R]) of edgl_cand_ce_fwd: slot 0 is the label, slot 1 + n is cand[r, n]
     (int32 [R, N]); -inf at an empty slot, an id >= I and an accidental hit (cand[r, n] == labels[r]); rows of label 0 are skipped
@@ -658,19 +713,34 @@ class SampledCEFn(torch.autograd.Function):
     d_table_out (f32 [I, C]): the backward ADDS the table gradient into it (both entry points add), allocates no
     [I, C] tensor and returns None for the table master; d_bias stays a dense f32 [I - 1].
     logq (f32 [I]): the log-Q correction of a weighted sampler, subtracted from the label's and every live slot's
-    value in the forward; a constant, so the backward is the same code on the corrected vals / lse."""
+    value in the forward; a constant, so the backward is the same code on the corrected vals / lse.
+    form ("softmax", "bce", "bpr"): the objective over the same slots and values, a tenth positional argument of
+    `.apply` (or `form=`; _apply_form).  bce / bpr take their loss and coef from sampled_row_loss and their dv from
+    edgl_cand_ce_bwd_form; the gradient contract above holds for every form."""
+
+    @classmethod
+    def apply(cls, *args, form=None):
+        return _apply_form(SampledCEFn, args, form)
 
     @staticmethod
     def forward(ctx, rows, table_master, out_bias, table_c, labels, cand, deterministic=False, d_table_out=None, logq=None):
+        return SampledCEFn._forward(ctx, "softmax", rows, table_master, out_bias, table_c, labels, cand, deterministic, d_table_out, logq)
+
+    @staticmethod
+    def _forward(ctx, form, rows, table_master, out_bias, table_c, labels, cand, deterministic=False, d_table_out=None, logq=None):
         ctx.deterministic = bool(deterministic)
+        ctx.form = _loss_form(form, "SampledCEFn")
         ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SampledCEFn")
         rows, labels, cand = rows.contiguous(), labels.reshape(-1).contiguous(), cand.contiguous()
         vals, label_val, lse = cand_ce_fwd(rows, table_c, out_bias, cand, labels, logq)
         R = rows.shape[0]
-        loss = torch.empty(1, device=rows.device, dtype=torch.float32)
-        coef = torch.empty(R, device=rows.device, dtype=torch.float32)
-        check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
-              "edgl_ce_loss_fwd")
+        if ctx.form == _lib.LOSS_SOFTMAX:
+            loss = torch.empty(1, device=rows.device, dtype=torch.float32)
+            coef = torch.empty(R, device=rows.device, dtype=torch.float32)
+            check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
+                  "edgl_ce_loss_fwd")
+        else:
+            loss, coef, lse, _ = sampled_row_loss(vals, None, labels, None, table_c.shape[0], form)      # (lse: the row auxiliary)
         ctx.save_for_backward(rows, table_c, out_bias, labels, cand, vals, lse, coef)
         return loss.reshape(())
 
@@ -687,9 +757,14 @@ class SampledCEFn(torch.autograd.Function):
         d_table = ctx.d_table_out if in_place else torch.zeros((I, C), device=dev, dtype=torch.float32)
         d_bias = torch.zeros(I - 1, device=dev, dtype=torch.float32)
         det = ctx.deterministic
-        check(lib.edgl_cand_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), _ptr(vals), _ptr(lse),
-                                   _ptr(coef), _ptr(g), R, C, I, N, _ptr(d_rows), _ptr(dv), None if det else _ptr(d_table),
-                                   None if det else _ptr(d_bias), _code(rows), _stream()), "edgl_cand_ce_bwd")
+        if ctx.form == _lib.LOSS_SOFTMAX:
+            check(lib.edgl_cand_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), _ptr(vals), _ptr(lse),
+                                       _ptr(coef), _ptr(g), R, C, I, N, _ptr(d_rows), _ptr(dv), None if det else _ptr(d_table),
+                                       None if det else _ptr(d_bias), _code(rows), _stream()), "edgl_cand_ce_bwd")
+        else:
+            check(lib.edgl_cand_ce_bwd_form(_ptr(rows), _ptr(table_c), _ptr(out_bias), _ptr(cand), _ptr(labels), _ptr(vals), _ptr(lse),
+                                            _ptr(coef), _ptr(g), R, C, I, N, _ptr(d_rows), _ptr(dv), None if det else _ptr(d_table),
+                                            None if det else _ptr(d_bias), ctx.form, _code(rows), _stream()), "edgl_cand_ce_bwd_form")
         if det:
             n = R * (N + 1)
             keys = torch.empty(n, device=dev, dtype=torch.int64)
@@ -748,11 +823,22 @@ class SharedCEFn(torch.autograd.Function):
     first, as in ScoreCEFn: the list does not depend on the row, so that changes nothing but the work.
     deterministic: no float atomics — repeated ids are summed in slot order, the label term over a k_segsum.hip plan.
     d_table_out (f32 [I, C]): the backward ADDS the table gradient into it and returns None for the table master.
-    logq (f32 [I]): the log-Q correction of a weighted sampler, as in SampledCEFn."""
+    logq (f32 [I]): the log-Q correction of a weighted sampler, as in SampledCEFn.
+    form ("softmax", "bce", "bpr"): the objective, as in SampledCEFn: a tenth positional argument of `.apply`
+    (edgl_shared_ce_bwd_form)."""
+
+    @classmethod
+    def apply(cls, *args, form=None):
+        return _apply_form(SharedCEFn, args, form)
 
     @staticmethod
     def forward(ctx, rows, table_master, out_bias, table_c, labels, shared, deterministic=False, d_table_out=None, logq=None):
+        return SharedCEFn._forward(ctx, "softmax", rows, table_master, out_bias, table_c, labels, shared, deterministic, d_table_out, logq)
+
+    @staticmethod
+    def _forward(ctx, form, rows, table_master, out_bias, table_c, labels, shared, deterministic=False, d_table_out=None, logq=None):
         ctx.deterministic = bool(deterministic)
+        ctx.form = _loss_form(form, "SharedCEFn")
         ctx.d_table_out = _table_out(d_table_out, table_master.shape, "SharedCEFn")
         rows, labels, shared = rows.contiguous(), labels.reshape(-1).contiguous(), shared.contiguous()
         _shared_ce_check(rows, table_c, shared, labels)
@@ -761,10 +847,13 @@ class SharedCEFn(torch.autograd.Function):
         rows, labels, _perm, inv, nvalid = compact_rows(rows, labels)
         vals, label_val, lse = _shared_ce_fwd(rows, table_c, out_bias, shared, labels, nvalid, logq)
         R = rows.shape[0]
-        loss = torch.empty(1, device=rows.device, dtype=torch.float32)
-        coef = torch.empty(R, device=rows.device, dtype=torch.float32)
-        check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
-              "edgl_ce_loss_fwd")
+        if ctx.form == _lib.LOSS_SOFTMAX:
+            loss = torch.empty(1, device=rows.device, dtype=torch.float32)
+            coef = torch.empty(R, device=rows.device, dtype=torch.float32)
+            check(lib.edgl_ce_loss_fwd(_ptr(lse), _ptr(label_val), _ptr(labels), R, _ptr(loss), _ptr(coef), _stream()),
+                  "edgl_ce_loss_fwd")
+        else:
+            loss, coef, lse, _ = sampled_row_loss(vals, label_val, labels, nvalid, table_c.shape[0], form)   # (lse: the row auxiliary)
         ctx.save_for_backward(rows, table_c, labels, shared, vals, label_val, lse, coef, inv, nvalid)
         return loss.reshape(())
 
@@ -785,9 +874,15 @@ class SharedCEFn(torch.autograd.Function):
         if ctx.deterministic:
             keys = torch.empty(2 * R, device=dev, dtype=torch.int64)
             plan = segsum_plan_buffer(2 * R, I, dev)
-        check(lib.edgl_shared_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(shared), _ptr(labels), _ptr(vals), _ptr(label_val), _ptr(lse),
-                                     _ptr(coef), _ptr(g), _ptr(nvalid), R, C, I, S, _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
-                                     _ptr(ws), _ptr(keys), _ptr(plan), code, _stream()), "edgl_shared_ce_bwd")
+        if ctx.form == _lib.LOSS_SOFTMAX:
+            check(lib.edgl_shared_ce_bwd(_ptr(rows), _ptr(table_c), _ptr(shared), _ptr(labels), _ptr(vals), _ptr(label_val), _ptr(lse),
+                                         _ptr(coef), _ptr(g), _ptr(nvalid), R, C, I, S, _ptr(d_rows_c), _ptr(d_table), _ptr(d_bias),
+                                         _ptr(ws), _ptr(keys), _ptr(plan), code, _stream()), "edgl_shared_ce_bwd")
+        else:
+            check(lib.edgl_shared_ce_bwd_form(_ptr(rows), _ptr(table_c), _ptr(shared), _ptr(labels), _ptr(vals), _ptr(label_val),
+                                              _ptr(lse), _ptr(coef), _ptr(g), _ptr(nvalid), R, C, I, S, _ptr(d_rows_c), _ptr(d_table),
+                                              _ptr(d_bias), _ptr(ws), _ptr(keys), _ptr(plan), ctx.form, code, _stream()),
+                  "edgl_shared_ce_bwd_form")
         check(lib.edgl_scatter_rows(_ptr(d_rows_c), _ptr(inv), R, C, _ptr(d_rows), code, _stream()), "edgl_scatter_rows")
         return d_rows, None if in_place else d_table, d_bias, None, None, None, None, None, None
 

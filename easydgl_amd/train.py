@@ -99,12 +99,18 @@ def args(argv=None):
                         "4.16).  popularity: (count + 1)^neg_alpha over the item counts of the training split; log_uniform: "
                         "TensorFlow's default, for ids sorted by falling frequency.  Both subtract log Q(c) from every sampled logit")
     p.add_argument("--neg_alpha", type=float, default=0.75, help="exponent of the popularity sampler (word2vec: 0.75)")
+    p.add_argument("--sampled_loss", choices=("softmax", "bce", "bpr"), default="softmax",
+                   help="with --train_negatives / --shared_negatives: the objective over the sampled negatives (DESIGN 4.19).  bce: "
+                        "binary cross-entropy, the negatives summed (SASRec / TiSASRec / TGAT as published; with a weighted sampler, "
+                        "tf.nn.nce_loss without its constant); bpr: the pairwise loss, averaged over a position's negatives")
     p.add_argument("--eval_neg_sampler", choices=("uniform", "popularity"), default="uniform",
                    help="with --eval_negatives: draw the evaluation negatives by (count + 1)^neg_alpha over the training split's item "
                         "counts — the popularity-sampled protocol; ranking uses the raw logits")
     a = p.parse_args(argv)
     if a.neg_sampler != "uniform" and a.train_negatives <= 0 and a.shared_negatives <= 0:
         p.error("--neg_sampler needs --train_negatives N > 0 or --shared_negatives S > 0: the full softmax draws no negatives")
+    if a.sampled_loss != "softmax" and a.train_negatives <= 0 and a.shared_negatives <= 0:
+        p.error("--sampled_loss needs --train_negatives N > 0 or --shared_negatives S > 0: the objective is defined over sampled negatives")
     if a.eval_neg_sampler != "uniform" and a.eval_negatives <= 0:
         p.error("--eval_neg_sampler needs --eval_negatives N > 0")
     if a.train_negatives > 0 and a.shared_negatives > 0:
@@ -176,7 +182,8 @@ def save_checkpoint(model, path: str) -> None:
     torch.save({"arena": model._arena.detach().cpu(), "adam_m": model._adam_m.cpu(), "adam_v": model._adam_v.cpu(),
                 "adam_state": model._adam_state.cpu(), "rng_state": model._rng_state.cpu(),
                 "offsets": dict(model._offsets), "neg_step": int(getattr(model, "neg_step", 0)),
-                "neg_sampler": str(getattr(model, "neg_sampler", "uniform")), "neg_alpha": float(getattr(model, "neg_alpha", 0.75))},
+                "neg_sampler": str(getattr(model, "neg_sampler", "uniform")), "neg_alpha": float(getattr(model, "neg_alpha", 0.75)),
+                "sampled_loss": str(getattr(model, "sampled_loss", "softmax"))},
                path)
 
 
@@ -191,6 +198,11 @@ def load_checkpoint(model, path: str) -> None:
     if saved[0] != mine[0] or (saved[0] == "popularity" and saved[1] != mine[1]):
         raise ValueError(f"checkpoint was trained with neg_sampler={saved[0]!r} neg_alpha={saved[1]}, the model has "
                          f"neg_sampler={mine[0]!r} neg_alpha={mine[1]}: a resumed run keeps its negative sampler")
+    # (optional field, DESIGN 4.19: a file from before it existed was trained with the softmax)
+    saved_loss, my_loss = str(ck.get("sampled_loss", "softmax")), str(getattr(model, "sampled_loss", "softmax"))
+    if saved_loss != my_loss:
+        raise ValueError(f"checkpoint was trained with sampled_loss={saved_loss!r}, the model has sampled_loss={my_loss!r}: a resumed "
+                         "run keeps its objective")
     with torch.no_grad():
         model._arena.copy_(ck["arena"])
         model._adam_m.copy_(ck["adam_m"])

@@ -627,6 +627,43 @@ int edgl_shared_ce_bwd(const void* rows, const void* table, const int32_t* share
                        int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias, float* workspace, int64_t* keys,
                        void* plan, int dtype, void* stream);
 
+/* ---- K5e: binary cross-entropy and BPR over the same sampled slots (csrc/k_sampled_loss.hip, sampled_dv.h) ---------
+ * The slots, their liveness and their values are those of edgl_cand_ce_fwd[_q] / edgl_shared_ce_fwd[_q]: the forwards are the same
+ * calls (their row_lse output is not used).  Row r is weighted iff 1 <= labels[r] < I and r < nvalid[0] (nvalid NULL = R); v0 is the
+ * label's value, L_r the live list slots, n_r their number, W the number of weighted rows.
+ *   EDGL_LOSS_BCE   l_r = softplus(-v0) + sum_{s in L_r} softplus(v_s)       dl/dv0 = sigma(v0) - 1       dl/dv_s = sigma(v_s)
+ *   EDGL_LOSS_BPR   l_r = (1 / n_r) sum_{s in L_r} softplus(v_s - v0)        dl/dv_s = sigma(v_s - v0) / n_r,  dl/dv0 = -sum_s dl/dv_s
+ *                   (n_r = 0: l_r = 0 and every derivative 0)
+ *   loss = sum over the weighted rows of l_r / (W + 1e-5), the denominator of edgl_ce_loss_fwd; rows of weight 0 add nothing.
+ *   With a log-Q term in the values, bce is tf.nn.nce_loss up to its constant log N, which is not applied.
+ *   edgl_sampled_row_loss     per row: row_loss = l_r, row_aux (bpr: sum_s sigma(v_s - v0); bce: 0), row_scale (bce: 1; bpr: 1 / n_r
+ *                             or 0), all f32 [R]; zeros for a row of weight 0.  label_val NULL: vals is f32 [R, S + 1] with slot 0 the
+ *                             label (edgl_cand_ce_fwd's, S = N); label_val given: vals is f32 [R, S] (edgl_shared_ce_fwd's).  One wave
+ *                             per row, no atomics, the order of every sum a function of S alone: a row's outputs depend on neither
+ *                             R nor the other rows.
+ *   edgl_sampled_loss_finish  loss_out[0] and coef f32 [R] = row_scale[r] / (W + 1e-5) (0 for a row of weight 0), one workgroup,
+ *                             a fixed order.
+ *   edgl_cand_ce_bwd_form / edgl_shared_ce_bwd_form   edgl_cand_ce_bwd / edgl_shared_ce_bwd with dv = g coef[r] dl_r/dv of `form`;
+ *                             row_aux stands where row_lse went (EDGL_LOSS_SOFTMAX: it IS row_lse, and the call is the one without
+ *                             _form, bit for bit).  Everything behind dv — d_rows, the table / bias sums in both modes, dv f32
+ *                             [R, N + 1], the zero pad columns of the shared path — is unchanged.
+ * edgl_sampled_row_loss: R >= 1, 1 <= S <= 8192, R (S + 8) < 2^31, I > 1, form bce or bpr; the _form calls: the shape rule of their
+ * family and 0 <= form <= 2; anything else is EDGL_ERR_SHAPE with the bound in the text, before any launch. */
+#define EDGL_LOSS_SOFTMAX 0
+#define EDGL_LOSS_BCE 1
+#define EDGL_LOSS_BPR 2
+int edgl_sampled_row_loss(const float* vals, const float* label_val, const int64_t* labels, const int32_t* nvalid, int R, int S, int I,
+                          int form, float* row_loss, float* row_aux, float* row_scale, void* stream);
+int edgl_sampled_loss_finish(const float* row_loss, const float* row_scale, const int64_t* labels, const int32_t* nvalid, int R, int I,
+                             float* loss_out, float* coef, void* stream);
+int edgl_cand_ce_bwd_form(const void* rows, const void* table, const float* out_bias, const int32_t* cand, const int64_t* labels,
+                          const float* vals, const float* row_aux, const float* coef, const float* gscale, int R, int C, int I, int N,
+                          void* d_rows, float* dv, float* d_table, float* d_bias, int form, int dtype, void* stream);
+int edgl_shared_ce_bwd_form(const void* rows, const void* table, const int32_t* shared, const int64_t* labels, const float* vals,
+                            const float* label_val, const float* row_aux, const float* coef, const float* gscale, const int32_t* nvalid,
+                            int R, int C, int I, int S, void* d_rows, float* d_table, float* d_bias, float* workspace, int64_t* keys,
+                            void* plan, int form, int dtype, void* stream);
+
 /* ---- K5, "flash" form (used by the static training engine): the forward scoring pass already accumulates the row
  * gradients, so the [R, I] logits are computed twice per step instead of three times.
  * edgl_score_flash_fwd: one pass over the item rows [i0, i1) gives row_lse (as edgl_score_lse_fwd), label_logit, and keeps

@@ -26,6 +26,10 @@ per shape the per-row step at N = 100 and the shared step at S = 1024 — the pa
 unset and this tree's with FLAGS.neg_sampler = popularity (counts = bincount of the batch's Zipf ids) — then the uniform against
 the alias draw and the loss forward without / with the gathered logq; `metrics`: H10 / N10 on the synthetic Zipf task of
 tests/metric_parity.py after `--metric_steps` equal steps under uniform negatives, popularity with log-Q and popularity without.
+Section `losses` (`--sections losses`, which keeps what stands in front of it): per shape of the shared section and
+model, `train_step` under FLAGS.sampled_loss = softmax / bce / bpr at N = 100 per row and at S = 1024 shared, the loss op alone
+(forward + backward on the model's scored rows), and H10 / N10 of the three objectives on the synthetic Zipf task after
+`--metric_steps` equal steps.  Nothing is gated on these numbers.
 Needs a GPU: there is no fallback."""
 import argparse
 import os
@@ -52,6 +56,8 @@ SHARED_HEADING = "one negative list per step, shared by every row (DESIGN 4.15)"
 POP_HEADING = "popularity-weighted negatives with the log-Q correction (DESIGN 4.16)"
 METRIC_HEADING = "ranking metrics under the three samplers (DESIGN 4.16)"
 POP_N, POP_S = 100, 1024
+LOSS_HEADING = "objectives over the sampled negatives: softmax, bce, bpr (DESIGN 4.19)"
+LOSS_FORMS = ("softmax", "bce", "bpr")
 HBM_RATE = 5.0e12         # bytes per second of streamed reads / writes (a round figure for the [R, S] traffic's floor)
 ATOMIC_RATE = 1.3e12      # bytes of f32 atomic adds per second, chip-wide
 
@@ -355,6 +361,74 @@ def metrics_section(args, lines):
     lines.append("")
 
 
+def form_op_call(model, rows, labels, lists, form):
+    tab = model.item_embs.lookup_table
+    r = rows.detach().requires_grad_(True)
+    fn = ops.SharedCEFn if lists.dim() == 1 else ops.SampledCEFn
+    loss = fn.apply(r, tab, model.output_bias, model.compute(tab), labels, lists, False, None, None, form)
+    torch.autograd.grad(loss, (r, tab, model.output_bias))
+
+
+def losses_section(args, lines):
+    """the step and the loss op under the three objectives, per-row lists at N = 100 and one shared list of S = 1024, all
+    in this session of this tree; then the ranking metrics of the three objectives after equal steps."""
+    import numpy as np
+    from oracle import easydgl_oracle as O
+    from tests import metric_parity as MP
+    lines += [f"{LOSS_HEADING}: ms per call, median (min .. max) of {args.rounds} rounds x {args.steps} calls, one session of this tree; "
+              f"bf16, dropout 0.1 / 0.1; N = {POP_N} per row, S = {POP_S} shared; uniform negatives, atomic table gradient", ""]
+    for name in args.models.split(","):
+        for B, L, C, num_items in SHAPES:
+            lines.append(f"{name}  {B} x {L} x {C}, {num_items} items")
+            for tag, N, S in ((f"N = {POP_N}", POP_N, 0), (f"S = {POP_S}", 0, POP_S)):
+                model, feats, labels = build(name, B, L, C, num_items, N, False, S)
+                lab = labels.reshape(-1).contiguous()
+                rows = scored_rows(name, model, feats)
+                lists = (model._sample(None, lab, N, model.train_neg_seed, 0, 0, None) if N else model.draw_shared_negatives(lab.device))
+                for form in LOSS_FORMS:
+                    model.sampled_loss = form
+                    step = rounds_of(lambda: model.train_step(feats, labels), args.rounds, args.steps)
+                    op = rounds_of(lambda: form_op_call(model, rows, lab, lists, form), args.rounds, args.steps)
+                    lines.append(f"  {tag:9s} {form:8s} train_step {fmt(step)}   loss op fwd + bwd {fmt(op)}")
+                    print(lines[-1], flush=True)
+                model = feats = labels = rows = lists = None
+                torch.cuda.empty_cache()
+            lines.append("")
+    num_items, seqslen, batch, steps, n_eval, S = 400, 20, 128, args.metric_steps, 2048, 32
+    cfg = O.Config(num_items=num_items, seqslen=seqslen, num_units=32, num_heads=2, num_blocks=1, masklen=4, time_scale=86400.0,
+                   ct_reg=1e-3, l2_reg=1e-4, learning_rate=2e-3, num_events=4)
+    rng = np.random.default_rng(11)
+    params0 = O.init_params(cfg, rng)
+    mt = O.synthetic_mark_table(cfg.num_items, cfg.num_events, multi_hot=True)
+    tr_i, tr_t = MP.make_sequences(cfg, batch * steps, rng)
+    ev_i, ev_t = MP.make_sequences(cfg, n_eval, rng)
+    batches = [O.mask_random(cfg, tr_i[s * batch:(s + 1) * batch], tr_t[s * batch:(s + 1) * batch],
+                             O.draw_masked_positions(cfg, batch, rng)) for s in range(steps)]
+    efeats, elabels = O.mask_last(cfg, ev_i, ev_t)
+    lines += [f"ranking metrics of the three objectives: EasyDGL f32, {num_items} items, {steps} steps of {batch} sequences, "
+              f"shared_negatives = {S}, uniform negatives, full-catalogue ranking of {n_eval} held-out sequences", ""]
+    for form in LOSS_FORMS:
+        F = SimpleNamespace(model="EasyDGL", num_items=cfg.num_items, num_units=cfg.num_units, num_heads=cfg.num_heads,
+                            num_blocks=cfg.num_blocks, seqslen=cfg.seqslen, masklen=cfg.masklen, time_scale=cfg.time_scale,
+                            learning_rate=cfg.learning_rate, l2_reg=cfg.l2_reg, ct_reg=cfg.ct_reg, hidden_dropout_rate=0.0,
+                            attention_probs_dropout_rate=0.0, mark_table=mt, compute_dtype="f32", num_train_steps=None,
+                            num_warmup_steps=None, shared_negatives=S, train_neg_seed=1, sampled_loss=form)
+        m = easydgl_amd.ranking(F).finalize("cuda")
+        m.load_tf_variables(params0)
+        for feats, labels in batches:
+            f = {k: torch.as_tensor(np.asarray(v)).cuda().contiguous() for k, v in feats.items()}
+            loss = m.train_step(f, torch.as_tensor(labels).cuda())
+        m.reset_metrics()
+        for lo in range(0, n_eval, 256):
+            ef = {k: torch.as_tensor(np.asarray(v[lo:lo + 256])).cuda().contiguous() for k, v in efeats.items()}
+            m.eval_step(ef, torch.as_tensor(elabels[lo:lo + 256]).cuda(), mask_seen=True)
+        got = m.metrics()
+        lines.append(f"  {form:8s} H10 {got['H10']:.4f}  N10 {got['N10']:.4f}  H50 {got['H50']:.4f}  N50 {got['N50']:.4f}  last loss "
+                     f"{float(loss):.4f}")
+        print(lines[-1], flush=True)
+    lines.append("")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--metric_steps", type=int, default=300, help="section metrics: training steps of every run")
@@ -372,6 +446,20 @@ def main():
     sections = args.sections.split(",")
     if sections == ["baseline"]:
         return baseline_section(args)
+    if sections == ["losses"]:      # keep what stands in front of the losses section
+        lines = []
+        if os.path.exists(args.out):
+            old = open(args.out).read().split("\n")
+            lines = old[:next((i for i, ln in enumerate(old) if ln.startswith(LOSS_HEADING)), len(old))]
+            while lines and not lines[-1]:
+                lines.pop()
+            lines.append("")
+        losses_section(args, lines)
+        os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines))
+        print("wrote", args.out)
+        return
     if set(sections) <= {"popularity", "metrics"}:      # keep what stands in front of the first section asked for, replace the rest
         lines = []
         if os.path.exists(args.out):
