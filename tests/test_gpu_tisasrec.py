@@ -1,5 +1,6 @@
-"""SURVEY §8 row a-15 (config 5): the interval-bucket attention kernels (edgl_tiattn_*) and the TiSASRec model class, through
-the C ABI, against oracle/baselines_ref.py (float64).  Tolerances: f32 path 1e-4 / 1e-3 (gradients); bf16 path 3e-2 / max-norm 1e-1 AND relative L2 8e-2 per gradient tensor."""
+"""SURVEY §8 row a-15 (config 5): the TiSASRec model class — and through it the interval-bucket attention kernels (edgl_tiattn_*)
+— against oracle/baselines_ref.py (float64).  The kernels themselves, through the C ABI at their edge shapes against a float64
+reference on their own operands: tests/test_gpu_tiattn.py.  Tolerances: f32 path 1e-4 / 1e-3 (gradients); bf16 path 3e-2 / max-norm 1e-1 AND relative L2 8e-2 per gradient tensor."""
 from types import SimpleNamespace
 
 import numpy as np
