@@ -12,8 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libeasydgl_hip.so")
 SOURCES = ["k_misc.hip", "k_tpp.hip", "k_optim.hip", "k_adam_rows.hip", "k_reduce.hip", "k_data.hip", "k_encode.hip", "k_gemm.hip", "k_gemm2.hip", "k_layernorm.hip", "k_bimau_fwd.hip", "k_bimau_bwd.hip", "k_bimau_big.hip", "k_bimau_stream.hip",
-           "k_score.hip", "k_ce.hip", "k_score_strip.hip", "k_score_stripw.hip", "k_eval_tile.hip", "k_eval_topk.hip", "k_eval_rank.hip", "k_eval_cand.hip", "k_cand_ce.hip", "k_shared_ce.hip", "k_sampled_loss.hip", "k_tattn.hip", "k_tiattn.hip", "k_timefn.hip", "k_coding.hip", "k_tail.hip", "k_segsum.hip", "k_gru.hip", "k_s2pnm.hip", "k_mate.hip", "k_tahe.hip"]
-HEADERS = ["edgl_common.h", "lds_limit.h", "batch_prep.h", "tpp_math.h", "score_plan.h", "topk_select.h", "gemm_tile.h", "bimau_common.h", "bimau_fwd_impl.h", "bimau_bwd_impl.h", "red_batch.h", "tn_group.h", "encode_scatter.h", "strip_mma.h", "score_strip.h", "eval_sweep.h", "cand_gather.h", "sampled_dv.h", "tattn_common.h", os.path.join("..", "..", "include", "easydgl_hip.h")]
+           "k_score.hip", "k_ce.hip", "k_score_strip.hip", "k_score_stripw.hip", "k_eval_tile.hip", "k_eval_topk.hip", "k_eval_rank.hip", "k_eval_cand.hip", "k_cand_ce.hip", "k_shared_ce.hip", "k_sampled_loss.hip", "k_tattn.hip", "k_tiattn.hip", "k_timefn.hip", "k_coding.hip", "k_tail_fwd.hip", "k_tail_bwd.hip", "k_segsum.hip", "k_gru.hip", "k_s2pnm.hip", "k_mate.hip", "k_tahe.hip"]
+HEADERS = ["edgl_common.h", "lds_limit.h", "batch_prep.h", "tpp_math.h", "score_plan.h", "topk_select.h", "gemm_tile.h", "bimau_common.h", "bimau_fwd_impl.h", "bimau_bwd_impl.h", "red_batch.h", "tn_group.h", "encode_scatter.h", "strip_mma.h", "score_strip.h", "eval_sweep.h", "cand_gather.h", "sampled_dv.h", "tattn_common.h", "tail_common.h", "tail2_common.h", os.path.join("..", "..", "include", "easydgl_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (no v_accvgpr_read/write traffic around every VALU consumer);
 # gfx950's register file is unified, so nothing is lost by not using AGPRs.  Per file: hipcc 7.2 crashes on k_score.hip

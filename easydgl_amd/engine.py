@@ -173,7 +173,7 @@ class TrainEngine:
         self.tpp_desc = torch.zeros(int(lib.edgl_tpp_prep_bytes(B, T, M)), device=dev, dtype=torch.uint8) if self.fused_tpp else None
         self.zero_resid = torch.zeros((B, T, C), device=dev, dtype=self.dt) if self.mgroups else None
         self.pre_t, self.so, self.st3 = e(B, T, C), e(B, T, C), e(B, 2, dtype=f32)
-        # fused per-sample block tail (csrc/k_tail.hip): one launch for dense -> LN -> GELU-dense -> dense -> LN (-> head)
+        # fused per-sample block tail (csrc/k_tail_fwd.hip): one launch for dense -> LN -> GELU-dense -> dense -> LN (-> head)
         # (the head of the fused tail and the fused TPP kernel hold the masked positions of a sample in LDS: M <= 256, T <= 1024 —
         # the bound of the key-streamed BiMAU kernels too (edgl_bimau_form: T <= 208 ... 64 in registers, T <= 1024 streamed).  Beyond
         # their own bounds the optional forms are simply not taken: fused TPP and stored keep bits T <= 128, fused tail T <= 112;
@@ -683,7 +683,7 @@ class TrainEngine:
             if self.fused_tail:
                 # the five weight-gradient products of the block run as one grouped launch after the BiMAU backward
                 check(lib.edgl_gemm_dw_defer(1, st), "edgl_gemm_dw_defer")
-                # one launch: LN3' -> GELU' -> dX(Wt) -> LN2' -> dX(Wout) * GELU' -> dX(Wi) -> LN1' -> dX(Wo)  (csrc/k_tail.hip)
+                # one launch: LN3' -> GELU' -> dX(Wt) -> LN2' -> dX(Wout) * GELU' -> dX(Wi) -> LN1' -> dX(Wo)  (csrc/k_tail_bwd.hip)
                 last = i == len(self.blk) - 1
                 tl = m.transform_ln
                 check(lib.edgl_tail_bwd_ct(x_in.data_ptr(), cin, _ptr(b["ao"]), _ptr(b["a1"]), _ptr(b["pre_f"]), _ptr(b["o"]),

@@ -181,7 +181,7 @@ class EasyDGL(Sequential):
             att, lam = blk.attention(layer_in, layer_in, ids, spans, marks, is_training,
                                      drop=self._drop(self.attention_probs_dropout_rate, 10 + 4 * i, is_training))
             lams.append(lam)
-            if fused_eval:      # inference: the block tail (and the head behind the last block) as ONE launch (csrc/k_tail.hip)
+            if fused_eval:      # inference: the block tail (and the head behind the last block) as ONE launch (csrc/k_tail_fwd.hip)
                 last = i == len(self.layers) - 1
                 x, rows = self._eval_tail(blk, att.contiguous(), layer_in, gather_pos, last)
                 if last:

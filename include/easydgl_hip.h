@@ -1020,7 +1020,7 @@ long edgl_time_function_bwd_workspace(int C);
 int edgl_time_function_bwd(const float* x, long n, const float* freq, const float* phase, int C, const void* d_out,
                            float* d_freq, float* d_phase, float* workspace, int dtype, void* stream);
 
-/* ---- fused per-sample block tail — EasyDGL.py:110-139 in ONE launch (csrc/k_tail.hip) ----------------
+/* ---- fused per-sample block tail — EasyDGL.py:110-139 in ONE launch (csrc/k_tail_fwd.hip, csrc/k_tail_bwd.hip) ----------------
  * The reference's LayerNorm is joint over (T, C) per sample (Base.py:12-67), so a workgroup owning a sample runs
  *   ao = att.Wo + bo ; a1 = LN1(dropout(ao) + x_in) ; f = gelu(a1.Wi + bi) ; o = f.Wout + bout ; y = LN2(dropout(o) + a1)
  *   head != 0:  so = gelu(y.Wt + bt) ; hrows[b*M + j] = LN3(so)[masked_pos[b, j]]                     (EasyDGL.py:136-146)

@@ -186,7 +186,7 @@ PADDED_CASE = dict(num_units=50, num_heads=1, num_blocks=2, seqslen=30, masklen=
 
 @pytest.mark.parametrize("case,drop", [(1, 0.0), (2, 0.0), (2, 0.1), ("padded", 0.0), ("padded", 0.1)])
 def test_fused_block_tail_matches_the_unfused_kernels(case, drop):
-    """csrc/k_tail.hip (dense -> LN -> GELU-dense -> dense -> LN -> head in one launch per block) against the seven
+    """csrc/k_tail_fwd.hip / k_tail_bwd.hip (dense -> LN -> GELU-dense -> dense -> LN -> head in one launch per block) against the seven
     launches it replaces, on the same weights, batch and dropout stream: every saved tensor, the gathered head rows, the
     loss and the gradients.  bf16 only (C = 64 and the headline C = 128, T = 101); equal up to the last bf16 digit of the
     dense outputs (the two paths feed the MFMA its K slots in a different order)."""

@@ -255,7 +255,7 @@ def test_chunked_eval_scoring_matches_the_single_pass(monkeypatch):
 @pytest.mark.parametrize("blocks", [1, 2])
 def test_inference_through_the_fused_block_tail_matches_the_unfused_modules(blocks, monkeypatch):
     """Sequential.eval's forward (Base.py:150-163) at a shape the fused per-sample block tail takes (bf16, C = 128, T = 101): the head
-    rows of `EasyDGL.encoder` through csrc/k_tail.hip — one launch per block, as in the training engine — against the dense /
+    rows of `EasyDGL.encoder` through csrc/k_tail_fwd.hip — one launch per block, as in the training engine — against the dense /
     LayerNorm modules it replaces (equal up to the last bf16 digit of the dense outputs), and the same top-K lists up to near-ties."""
     prob = make_problem(seed=31, batch=8, num_items=2000, seqslen=100, num_units=128, num_heads=8, num_blocks=blocks, masklen=20,
                         num_events=16)

@@ -1,4 +1,4 @@
-"""The two-workgroups-per-CU form of the fused block tail (csrc/k_tail.hip, namespace t2: C = 128, T <= 101; three unpadded,
+"""The two-workgroups-per-CU form of the fused block tail (csrc/k_tail_fwd.hip and k_tail_bwd.hip, namespace t2 of tail2_common.h: C = 128, T <= 101; three unpadded,
 swizzled LDS images, <= 128 registers) against the one-workgroup-per-CU kernels it replaces at that shape: the SAME arithmetic in
 the same order, so every saved tensor, the gathered head rows, the loss and every gradient must agree BIT FOR BIT
 (EasyDGL.py:110-146 and its backward).  The one-per-CU kernels themselves are held to the unfused launches and to the fp64

@@ -1,4 +1,4 @@
-"""The forward of the two-per-CU block tail (csrc/k_tail.hip, t2::tail2_fwd_kernel) stores through a uniform base + 32-bit lane
+"""The forward of the two-per-CU block tail (csrc/k_tail_fwd.hip, t2::tail2_fwd_kernel) stores through a uniform base + 32-bit lane
 offsets that every store batch rebuilds (copy_out, gelu_pass, the lane's operand offsets behind each batch) — the form that keeps
 the kernel free of scratch (DESIGN rule 80).  Same addresses, same bytes: every tensor the forward writes, pre-filled with NaN, must
 come out bit for bit as from the one-per-CU kernel with no NaN left (the gathered head rows: no row left zero), at the sizes where

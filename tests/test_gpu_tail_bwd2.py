@@ -1,4 +1,4 @@
-"""The block-tail backward on half a CU (csrc/k_tail.hip, t2::tail2_bwd_kernel: C = 128, T <= 101, three swizzled LDS images, <= 128
+"""The block-tail backward on half a CU (csrc/k_tail_bwd.hip, t2::tail2_bwd_kernel: C = 128, T <= 101, three swizzled LDS images, <= 128
 registers, LayerNorm inputs as quads straight from global memory) against tail_bwd_kernel, the one-workgroup-per-CU kernel it replaces
 at that shape: the SAME arithmetic in the same order (rounding points, block-sum order, dropout element indices, chains summed in
 ascending j), so the six gradient tensors, the three per-sample LayerNorm partials and the six LayerNorm parameter gradients must

@@ -5,7 +5,7 @@
 # the library first.
 # usage: bash tools/build_variant.sh <name> "<extra flags>" <unit without .hip> ...
 #   bash tools/build_variant.sh timing -DSTRIP_TIMING k_score_strip              (tools/strip_probe.py)
-#   bash tools/build_variant.sh phase_k_tail -DEDGL_PHASE_TIMING k_tail          (tools/phase_probe*.py)
+#   bash tools/build_variant.sh phase_k_tail -DEDGL_PHASE_TIMING k_tail_fwd      (tools/phase_probe*.py; k_tail_bwd for the backward)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 N=$1; X=$2; shift 2

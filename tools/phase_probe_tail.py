@@ -1,8 +1,9 @@
 """Diagnostic: per-phase wave cycles of the fused tail kernels at the headline shape.  Library variants:
-  forward : bash tools/build_variant.sh phase_k_tail -DEDGL_PHASE_TIMING k_tail
+  forward : bash tools/build_variant.sh phase_k_tail -DEDGL_PHASE_TIMING k_tail_fwd
             -> python tools/phase_probe_tail.py tools/variants/lib_phase_k_tail.so
-  backward: bash tools/build_variant.sh phase_k_tail_bwd "-DEDGL_PHASE_TIMING -DEDGL_PHASE_BWD" k_tail
-            -> python tools/phase_probe_tail.py tools/variants/lib_phase_k_tail_bwd.so bwd"""
+  backward: bash tools/build_variant.sh phase_k_tail_bwd -DEDGL_PHASE_TIMING k_tail_bwd
+            -> python tools/phase_probe_tail.py tools/variants/lib_phase_k_tail_bwd.so bwd
+Each unit has its own slots and its own read-back (edgl_debug_phase_cycles_tail / edgl_debug_phase_cycles_tail_bwd)."""
 import ctypes
 import os
 import shutil
@@ -21,16 +22,17 @@ model, feats, labels = bench.make_model_and_batch(dict(bench.HEADLINE), "bf16", 
 eng = TrainEngine(model, 512, use_graph=False)
 eng.load_batch(feats, labels)
 raw = ctypes.CDLL(_lib.LIB_PATH)
+read_cycles = raw.edgl_debug_phase_cycles_tail_bwd if BWD else raw.edgl_debug_phase_cycles_tail
 buf = (ctypes.c_ulonglong * 16)()
 for _ in range(3):
     eng.step()
 torch.cuda.synchronize()
-raw.edgl_debug_phase_cycles_tail(buf, 1)
+read_cycles(buf, 1)
 n = 5
 for _ in range(n):
     eng.step()
 torch.cuda.synchronize()
-raw.edgl_debug_phase_cycles_tail(buf, 0)
+read_cycles(buf, 0)
 if BWD:
     names = ["head inputs + gathered row gradients", "LN3' + gelu' + dX(Wt)", "o, a1 -> z2", "LN2' + d_o", "hidden layer, two halves",
              "ao, x_in -> z1", "LN1' + d_ao + d_res1", "dX(Wo) + d_att"]
