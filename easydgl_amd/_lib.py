@@ -183,6 +183,10 @@ SIGNATURES = {
     "edgl_tattn_fwd": (I, [P, I, P, I, P, I, P, I, P, I, I, I, I, I, F, F, P, U32, P, I, P, I, I, P]),
     "edgl_tattn_bwd": (I, [P, I, P, I, P, I, P, P, I, P, I, I, I, I, I, F, F, P, U32, P, I, P, I, P, I, I, I, P]),
     "edgl_timefn_fwd": (I, [P, I, P, I, P, P, P, P, P, I, I, I, I, F, P, P, P, I, P]),
+    "edgl_tgattn_saved_bytes": (L, [I, I, I]),
+    "edgl_tgattn_bwd_workspace": (L, [I, I, I, I]),
+    "edgl_tgattn_fwd": (I, [P, P, P, P, I, P, P, P, I, I, I, I, F, F, F, P, U32, P, P, P, P, I, P]),
+    "edgl_tgattn_bwd": (I, [P, P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, F, F, F, P, U32, P, P, P, P, P, P, I, P]),
     "edgl_timefn_bwd_workspace": (L, [I]),
     "edgl_timefn_bwd": (I, [P, I, P, P, P, P, P, I, I, I, I, F, P, I, P, I, P, P, P, I, P]),
     "edgl_mask_rows": (I, [P, P, P, L, I, I, P]),

@@ -241,3 +241,47 @@ class TiMultiHeadAttention(nn.Module):
         return ops.TiAttnFn.apply(q, kv, queries, self.pcoding_K.pembs.lookup_table, self.pcoding_V.pembs.lookup_table, kt, vt,
                                   self.compute(kt), self.compute(vt), ids, ts, self.num_heads, self.time_scale, self.timelen,
                                   drop if is_training else ops.NO_DROP, float(getattr(self, "qk_scale", 0.0)), self.deterministic)
+
+
+class TgMultiHeadAttention(nn.Module):
+    """temporal.py:187-264 (TGREC, CIKM'21): queries and keys carry a time code, [x_q | Phi(0)] and [x_k | Phi(dt[q,k])], and the
+    code is projected with the keys AND the values.  ``q_kernel`` [2C,C] (dense), ``kv_kernel`` [2C,2C] (dense_1 | dense_2 as
+    column blocks; rows: x half, time half), ``o_kernel`` [C,2C] (dense_3), ``ln_gamma`` / ``ln_beta`` [2C] (ln); the time
+    function is the model's shared ``tcoding``.  ``forward(queries, intervals, is_training)`` with ``intervals`` = (ids [B,T],
+    ts [B,T] or [B,T+1]): the [B,T,T] span tensor and the three [B,T,T,.] projections are never built (ops.TgAttnFn).  Returns
+    [B,T,2C].  The trailing LayerNorm is over the last axis (normalize.py) and runs on the joint kernel with one row per sample;
+    that kernel's epsilon is 1e-12 where normalize.py has 1e-8 (a relative 5e-9 / variance in the scale)."""
+
+    def __init__(self, num_units, num_heads, dropout_rate, l2_reg, tcoding, gen=None):
+        super().__init__()
+        self.num_units, self.num_heads, self.dropout_rate, self.l2_reg = num_units, num_heads, dropout_rate, l2_reg
+        C = num_units
+        self.q_kernel = nn.Parameter(glorot_uniform_(torch.empty(2 * C, C), gen))
+        self.q_bias = nn.Parameter(torch.zeros(C))
+        self.kv_kernel = nn.Parameter(torch.cat([glorot_uniform_(torch.empty(2 * C, C), gen) for _ in range(2)], dim=1))
+        self.kv_bias = nn.Parameter(torch.zeros(2 * C))
+        self.o_kernel = nn.Parameter(glorot_uniform_(torch.empty(C, 2 * C), gen))
+        self.o_bias = nn.Parameter(torch.zeros(2 * C))
+        self.ln_beta = nn.Parameter(torch.zeros(2 * C))
+        self.ln_gamma = nn.Parameter(torch.ones(2 * C))
+        object.__setattr__(self, "tcoding", tcoding)   # shared with the model: not registered twice
+        self.compute = lambda p: p
+        self.time_scale = 1.0
+        self.violations = None
+
+    def forward(self, queries, intervals, is_training, causality=True, drop: ops.Drop = ops.NO_DROP):
+        if not causality:
+            raise NotImplementedError("the HIP temporal-graph attention implements the causal form TGREC uses (TGREC.py:62)")
+        ids, ts = intervals
+        B, T, C = queries.shape
+        zeros = torch.zeros((B, T), device=queries.device, dtype=torch.float32)
+        qt = self.tcoding.code(zeros).reshape(B, T, C).to(queries.dtype)                          # :209 Phi(0) = cos(phi)
+        xq = torch.cat([queries, qt], dim=-1)                                                     # :210-211
+        q = ops.LinearFn.apply(xq, self.q_kernel, self.q_bias, self.compute(self.q_kernel), False)                   # :218
+        kv = ops.LinearFn.apply(queries, self.kv_kernel[:C], self.kv_bias, self.compute(self.kv_kernel)[:C], False)  # :219-220, x half
+        o = ops.TgAttnFn.apply(q, kv, self.kv_kernel, self.compute(self.kv_kernel), self.tcoding.basis_freq, self.tcoding.phase,
+                               ids, ts, self.num_heads, self.time_scale, drop if is_training else ops.NO_DROP, self.violations)
+        out = ops.LinearFn.apply(o, self.o_kernel, self.o_bias, self.compute(self.o_kernel), False)                  # :261
+        y = ops.AddLayerNormFn.apply(out.reshape(B * T, 1, 2 * C), xq.reshape(B * T, 1, 2 * C), self.ln_gamma, self.ln_beta,
+                                     ops.NO_DROP, None)                                                              # :262-263
+        return y.reshape(B, T, 2 * C)

@@ -2119,3 +2119,79 @@ class TimeFunctionFn(torch.autograd.Function):
         check(lib.edgl_time_function_bwd(_ptr(x), x.numel(), _ptr(freq), _ptr(phase), C, _ptr(d_out), _ptr(both[:C]),
                                          _ptr(both[C:]), _ptr(ws), _code(d_out), _stream()), "edgl_time_function_bwd")
         return None, both[:C], both[C:], None
+
+
+# ------------------------------------------------------------------------------------------------
+# K12: temporal-graph attention with time-coded keys and values (TGREC; csrc/k_tgattn.hip)
+# ------------------------------------------------------------------------------------------------
+def _gemm_view(A, Bm, out, M, N, K, lda, ldb, ldc, b_kc, code, flags=0):
+    """edgl_gemm on column blocks of wider buffers (A k-contiguous): the row strides are the parents'."""
+    check(lib.edgl_gemm(_vptr(A), _vptr(Bm), _vptr(out), M, N, K, lda, ldb, ldc, 1, int(b_kc), None, None, flags, 1, None, code,
+                        _stream()), "edgl_gemm")
+
+
+def _dw_view(X, dY, R, Kf, N, ldx, ldy, code):
+    """f32 [Kf, N] = X[R, Kf]^T . dY[R, N] over column blocks (edgl_gemm_dw, fixed-order partial sums)."""
+    dw = torch.empty((Kf, N), device=X.device, dtype=torch.float32)
+    ws = torch.empty(lib.edgl_gemm_dw_workspace(R, Kf, N, code), device=X.device, dtype=torch.float32)
+    check(lib.edgl_gemm_dw(_vptr(X), _vptr(dY), _ptr(dw), None, R, Kf, N, ldx, ldy, 0, _ptr(ws), code, _stream()), "edgl_gemm_dw")
+    return dw
+
+
+class TgAttnFn(torch.autograd.Function):
+    """TgMultiHeadAttention between its dense layers (temporal.py:213-258): q [B,T,C] (the full query projection), kv [B,T,2C] =
+    x . Wkv[:C] + b (the x halves of K | V), Wkv [2C,2C] (rows: x half | time half; columns: K | V) whose time half enters here:
+    U_h = q_h . Wk_t[:,h]^T in front of the kernel, O_h = Ox_h + G_h . Wv_t[:,h] behind it (edgl_gemm per head), edgl_tgattn_*
+    in between.  No [B,T,T,.] tensor exists.  ts f32 [B,T] or [B,T+1] (the first T entries of a row are read)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, w_master, w_c, omega, phi, ids, ts, H, time_scale, drop: Drop, violations=None, qk_scale=0.0):
+        B, T, C = q.shape
+        dh, R = C // H, B * T
+        code = _code(q)
+        q2, kv = q.contiguous().view(R, C), kv.contiguous()
+        if ts.dtype != torch.float32 or ts.dim() != 2 or ts.shape[1] < T or ts.stride(1) != 1:
+            raise _lib.EdglError("TgAttnFn: ts must be float32 [B, T] or [B, T+1]")
+        wt = w_c[C:]                                                  # time half: [C, 2C], Wk_t | Wv_t
+        u = torch.empty((R, H, C), device=q.device, dtype=q.dtype)
+        for h in range(H):                                            # U_h[r, c] = sum_d q[r, h dh + d] Wk_t[c, h dh + d]
+            _gemm_view(q2[:, h * dh:], wt[:, h * dh:], u[:, h], R, C, dh, C, 2 * C, H * C, True, code)
+        ox = torch.empty((R, C), device=q.device, dtype=q.dtype)
+        g = torch.empty((R, H, C), device=q.device, dtype=q.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty(int(lib.edgl_tgattn_saved_bytes(B, T, H)), device=q.device, dtype=torch.uint8) if need else None
+        scale = float(qk_scale) if qk_scale else 1.0 / float(dh) ** 0.5                        # temporal.py:232
+        check(lib.edgl_tgattn_fwd(_ptr(q2), _ptr(u), _ptr(kv), _vptr(ts), ts.stride(0), _ptr(ids), _ptr(omega), _ptr(phi), B, T, H, C,
+                                  scale, float(time_scale), float(drop.rate), drop.ptr(), drop.stream_id, _ptr(ox), _ptr(g),
+                                  _ptr(saved), _ptr(violations), code, _stream()), "edgl_tgattn_fwd")
+        out = ox.clone() if need else ox
+        for h in range(H):                                            # O_h += G_h . Wv_t[:, h]
+            _gemm_view(g[:, h], wt[:, C + h * dh:], out[:, h * dh:], R, dh, C, H * C, 2 * C, C, False, code, _lib.EPI_ACCUM)
+        ctx.save_for_backward(q2, u, kv, w_c, omega, phi, ids, ts, ox, g, saved)
+        ctx.meta = (B, T, C, H, scale, float(time_scale), drop, code)
+        return out.view(B, T, C)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        q2, u, kv, w_c, omega, phi, ids, ts, ox, g, saved = ctx.saved_tensors
+        B, T, C, H, scale, time_scale, drop, code = ctx.meta
+        dh, R = C // H, B * T
+        wt = w_c[C:]
+        d_o = d_out.contiguous().view(R, C)
+        d_g = torch.empty_like(g)
+        for h in range(H):                                            # dG_h = dO_h . Wv_t[:, h]^T
+            _gemm_view(d_o[:, h * dh:], wt[:, C + h * dh:], d_g[:, h], R, C, dh, C, 2 * C, H * C, True, code)
+        d_q, d_u, d_kv = torch.empty_like(q2), torch.empty_like(u), torch.empty_like(kv)
+        both = torch.empty(2 * C, device=q2.device, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_tgattn_bwd_workspace(B, T, H, C)), device=q2.device, dtype=torch.float32)
+        check(lib.edgl_tgattn_bwd(_ptr(q2), _ptr(u), _ptr(kv), _vptr(ts), ts.stride(0), _ptr(ids), _ptr(omega), _ptr(phi), _ptr(ox),
+                                  _ptr(g), _ptr(d_o), _ptr(d_g), _ptr(saved), B, T, H, C, scale, time_scale, float(drop.rate),
+                                  drop.ptr(), drop.stream_id, _ptr(d_q), _ptr(d_u), _ptr(d_kv), _ptr(both[:C]), _ptr(both[C:]),
+                                  _ptr(ws), code, _stream()), "edgl_tgattn_bwd")
+        d_w = torch.zeros(w_c.shape, device=q2.device, dtype=torch.float32)      # the x half's gradient comes from its own dense op
+        for h in range(H):
+            sl = slice(h * dh, (h + 1) * dh)
+            _gemm_view(d_u[:, h], wt[:, h * dh:], d_q[:, h * dh:], R, dh, C, H * C, 2 * C, C, False, code, _lib.EPI_ACCUM)
+            d_w[C:, sl] = _dw_view(d_u[:, h], q2[:, h * dh:], R, C, dh, H * C, C, code)          # dWk_t[:, h] = dU_h^T . q_h
+            d_w[C:, C + h * dh:C + (h + 1) * dh] = _dw_view(g[:, h], d_o[:, h * dh:], R, C, dh, H * C, C, code)
+        return d_q.view(B, T, C), d_kv, d_w, None, both[:C], both[C:], None, None, None, None, None, None, None

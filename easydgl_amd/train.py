@@ -1,7 +1,7 @@
 """Train / evaluate driver — the role of the reference's ``src/main.py:78-151`` with ``util.EarlyStopping``
 (``src/util.py:14-58``), on the HIP model.
 
-Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM (regressive batches,
+Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC (regressive batches,
 ``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``); TimelyREC is fed regressively with the four
 calendar fields of its records (``has_datetime=True``), derived from ``seqs_t`` where the files lack them.
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
@@ -35,7 +35,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM or TimelyREC (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC or TGREC (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512
@@ -301,6 +301,10 @@ def run(FLAGS) -> Dict[str, float]:
     te_i, te_t = F.load_sequences(FLAGS.test, FLAGS.seqslen)
     logging.info("   train %d, valid %d, test %d sequences of %d positions", len(tr_i), len(vl_i), len(te_i), tr_i.shape[1])
 
+    if FLAGS.model == "TGREC":     # the factorised time code needs times that do not decrease at ANY position of a row, the
+        for name, tt in (("train", tr_t), ("valid", vl_t), ("test", te_t)):     # zeros under left padding included (model/tgrec.py)
+            if np.any(np.diff(tt[:, :FLAGS.seqslen], axis=1) < 0):
+                raise ValueError(f"{name}: timestamps decrease along a row; TGREC needs time-sorted records, padding first with time 0")
     cals = None
     if FLAGS.model == "TimelyREC":
         # the on-device loader and graph capture know nothing of the calendar fields (out of scope)

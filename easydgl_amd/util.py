@@ -24,4 +24,7 @@ def ranking(FLAGS):
     if FLAGS.model == "TimelyREC":
         from .model import TimelyREC
         return TimelyREC(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "TGREC":
+        from .model import TGREC
+        return TGREC(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

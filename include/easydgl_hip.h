@@ -947,6 +947,26 @@ long edgl_timefn_bwd_workspace(int C);
 int edgl_timefn_bwd(const void* q, int ldq, const float* ts, const float* omega, const float* phi, const void* d_qx,
                     const void* d_kx, int B, int T, int C, int H, float time_scale, void* d_q, int ld_dq, void* d_k,
                     int ld_dk, float* d_omega, float* d_phi, float* workspace, int dtype, void* stream);
+/* ---- K12: temporal-graph attention with time-coded keys and values (TGREC; csrc/k_tgattn.hip) ----------
+ * TgMultiHeadAttention.__call__ (temporal.py:204-258) between its dense layers.  q [B,T,C], u [B,T,H,C] (u_h = q_h . Wk_t[:,h]^T),
+ * kv [B,T,2C] (the x halves of K | V), ts f32 [B, ld_t] raw seconds (ld_t >= T; the times of the T input tokens, non-decreasing
+ * along the WHOLE row, zeros under left padding included), ids [B,T] (key masked where 0), omega / phi f32 [C].  Causal.
+ * Writes ox [B,T,C] (= P . Vx) and g [B,T,H,C] (= sum_k P[q,k] Phi(dt[q,k]); the caller adds g_h . Wv_t[:,h]), both `dtype`.
+ * saved (NULL for inference): edgl_tgattn_saved_bytes bytes.  violations (may be NULL): += positions whose time decreases.
+ * C in {32, 64, 128}, C/H in {16, 32, 64, 128}, T <= 1024, H*B*T*T < 2^32.
+ * edgl_tgattn_bwd: d_ox, d_g -> d_q, d_u, d_kv (`dtype`), d_omega, d_phi f32 [C] (overwritten; fixed-order sums, no f32
+ * atomics).  workspace >= edgl_tgattn_bwd_workspace(B, T, H, C) floats. */
+long edgl_tgattn_saved_bytes(int B, int T, int H);
+long edgl_tgattn_bwd_workspace(int B, int T, int H, int C);
+int edgl_tgattn_fwd(const void* q, const void* u, const void* kv, const float* ts, int ld_t, const int64_t* ids,
+                    const float* omega, const float* phi, int B, int T, int H, int C, float scale, float time_scale,
+                    float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* ox, void* g, void* saved,
+                    int* violations, int dtype, void* stream);
+int edgl_tgattn_bwd(const void* q, const void* u, const void* kv, const float* ts, int ld_t, const int64_t* ids,
+                    const float* omega, const float* phi, const void* ox, const void* g, const void* d_ox,
+                    const void* d_g, void* saved, int B, int T, int H, int C, float scale, float time_scale,
+                    float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, void* d_u, void* d_kv,
+                    float* d_omega, float* d_phi, float* workspace, int dtype, void* stream);
 /* y = x * (ids != 0) per row: `seqs_outs *= seqs_masks` (TGAT.py:58,70; TiSASREC.py:73); its own backward. */
 int edgl_mask_rows(const void* x, const int64_t* ids, void* y, long rows, int C, int dtype, void* stream);
 
