@@ -187,6 +187,14 @@ SIGNATURES = {
     "edgl_tgattn_bwd_workspace": (L, [I, I, I, I]),
     "edgl_tgattn_fwd": (I, [P, P, P, P, I, P, P, P, I, I, I, I, F, F, F, P, U32, P, P, P, P, I, P]),
     "edgl_tgattn_bwd": (I, [P, P, P, P, I, P, P, P, P, P, P, P, P, I, I, I, I, F, F, F, P, U32, P, P, P, P, P, P, I, P]),
+    "edgl_dconv_max_reach": (I, [I, I]),
+    "edgl_dconv_bwd_workspace": (L, [I, I, I, I]),
+    "edgl_dconv_ln_fwd": (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, I, P]),
+    "edgl_dconv_ln_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, P, P, I, P]),
+    "edgl_gelu_tanh_fwd": (I, [P, P, L, I, P]),
+    "edgl_gelu_tanh_bwd": (I, [P, P, P, L, I, P]),
+    "edgl_gather_relu_fwd": (I, [P, P, P, I, I, I, I, I, P]),
+    "edgl_gather_relu_bwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "edgl_timefn_bwd_workspace": (L, [I]),
     "edgl_timefn_bwd": (I, [P, I, P, P, P, P, P, I, I, I, I, F, P, I, P, I, P, P, P, I, P]),
     "edgl_mask_rows": (I, [P, P, P, L, I, I, P]),

@@ -33,6 +33,15 @@ def mask_random(tokens: torch.Tensor, timestamps: torch.Tensor, mask_id: int, ma
     return {"seqs_i": masked, "seqs_t": timestamps, "masked_positions": masked_positions}, labels
 
 
+def grec_mask_random(tokens: torch.Tensor, mask_id: int, masked_positions: torch.Tensor):
+    """GRECPostProcessor.mask_random (dataloader.py:118-144): the encoder sees the tokens with MASK at the drawn positions, the
+    decoder the tokens themselves; a masked token is predicted from the row in front of it (positions - 1, never negative:
+    draw_masked_positions leaves out position 0)."""
+    labels = tokens.gather(1, masked_positions)
+    masked = tokens.scatter(1, masked_positions, mask_id)
+    return {"seqs_i": tokens, "seqs_m": masked, "masked_positions": masked_positions - 1}, labels
+
+
 def device_mask_random(tokens: torch.Tensor, timestamps: torch.Tensor, mask_id: int, masklen: int, rng_state: torch.Tensor,
                        stream_id: int = 0x4d41534b):
     """MAUPostProcessor.mask_random for a whole device batch in ONE kernel (edgl_mask_random): draws `masklen`

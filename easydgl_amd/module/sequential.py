@@ -1,7 +1,7 @@
 """Mirror of src/module/sequential.py: MultiHeadAttention (Vaswani et al., the unit of SASRec) on the generic masked attention
 kernel in its plain-head form (Dq == Dv, csrc/k_tattn.hip), and the GRU layer S2PNM puts in front of it (the reference's
 compat/cudnn_rnn.py CudnnGRU) on the recurrence kernel csrc/k_gru.hip; TimelyREC's MATEncoder and TAHEncoder on csrc/k_mate.hip
-and csrc/k_tahe.hip."""
+and csrc/k_tahe.hip; GREC's MaskedCNN (two dilated convolutions, each with LayerNorm and ReLU, and a residual) on csrc/k_dconv.hip."""
 from __future__ import annotations
 
 import torch
@@ -110,3 +110,49 @@ class GRU(nn.Module):
     def forward(self, x):
         xp = ops.LinearFn.apply(x, self.w_kernel, self.w_bias, self.compute(self.w_kernel), False)
         return ops.GruSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel))
+
+
+def truncated_normal_(t: torch.Tensor, gen: torch.Generator, std: float = 0.02) -> torch.Tensor:
+    """tf.truncated_normal_initializer(stddev=std): N(0, std), a value beyond two standard deviations is drawn again."""
+    v = torch.randn(t.shape, generator=gen)
+    while True:
+        bad = v.abs() > 2.0
+        if not bool(bad.any()):
+            break
+        v[bad] = torch.randn(int(bad.sum()), generator=gen)
+    with torch.no_grad():
+        t.copy_(v * std)
+    return t
+
+
+class Conv1D(nn.Module):
+    """sequential.py:140-174, the parameters: ``weight`` [fw, in, out] (the reference's [1, fw, in, out] without the leading 1),
+    truncated normal (sigma 0.02), ``bias`` zeros.  The reference seeds every weight with seed=1, i.e. draws the SAME values for
+    every convolution of the model; that is not reproduced — each weight takes its own draws from the model's generator."""
+
+    def __init__(self, filter_width, out_channels, dilation, causality, gen=None):
+        super().__init__()
+        self.filter_width, self.dilation, self.causality = int(filter_width), int(dilation), bool(causality)
+        self.weight = nn.Parameter(truncated_normal_(torch.empty(self.filter_width, out_channels, out_channels), gen))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+
+
+class MaskedCNN(nn.Module):
+    """sequential.py:177-207 (Yuan et al., WWW'20): dconv0 (dilation d) -> ln0 -> relu -> dconv1 (dilation 2d) -> ln1 -> relu ->
+    + input, as two calls of ops.DConvLnFn (csrc/k_dconv.hip); the second adds the residual in its epilogue.  The LayerNorms are
+    normalize.py's (biased variance, epsilon 1e-8).  ``forward(features, is_training)`` keeps the reference's arguments."""
+
+    def __init__(self, filter_width, out_channels, dilation, causality, gen=None):
+        super().__init__()
+        self.dconv0 = Conv1D(filter_width, out_channels, dilation, causality, gen)
+        self.dconv1 = Conv1D(filter_width, out_channels, 2 * dilation, causality, gen)
+        self.ln0_gamma, self.ln0_beta = nn.Parameter(torch.ones(out_channels)), nn.Parameter(torch.zeros(out_channels))
+        self.ln1_gamma, self.ln1_beta = nn.Parameter(torch.ones(out_channels)), nn.Parameter(torch.zeros(out_channels))
+        self.compute = lambda p: p  # replaced by the owning model (bf16 shadow lookup)
+
+    def forward(self, features, is_training=False):
+        c0, c1 = self.dconv0, self.dconv1
+        y = ops.DConvLnFn.apply(features, c0.weight, c0.bias, self.ln0_gamma, self.ln0_beta, self.compute(c0.weight), c0.dilation,
+                                c0.causality, None)
+        return ops.DConvLnFn.apply(y, c1.weight, c1.bias, self.ln1_gamma, self.ln1_beta, self.compute(c1.weight), c1.dilation,
+                                   c1.causality, features)

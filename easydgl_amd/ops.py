@@ -2195,3 +2195,110 @@ class TgAttnFn(torch.autograd.Function):
             d_w[C:, sl] = _dw_view(d_u[:, h], q2[:, h * dh:], R, C, dh, H * C, C, code)          # dWk_t[:, h] = dU_h^T . q_h
             d_w[C:, C + h * dh:C + (h + 1) * dh] = _dw_view(g[:, h], d_o[:, h * dh:], R, C, dh, H * C, C, code)
         return d_q.view(B, T, C), d_kv, d_w, None, both[:C], both[C:], None, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# K13: dilated convolution with LayerNorm / ReLU epilogue (GREC; csrc/k_dconv.hip)
+# ------------------------------------------------------------------------------------------------
+def dconv_check(num_units: int, filter_width: int, dilation: int, dtype: torch.dtype, who: str = "DConvLnFn") -> None:
+    """Refuses, before any launch and with the flag names, a convolution whose halo (filter_width - 1) * dilation does not fit the
+    LDS image beside the kernel's row block (edgl_dconv_max_reach: derived from the LDS size, no dilation is hard-coded)."""
+    if not 1 <= int(filter_width) <= 5 or int(dilation) < 1:
+        raise ValueError(f"{who}: filter_width={filter_width} dilation={dilation} unsupported; the HIP convolution takes "
+                         "1 <= --filter_width <= 5 and --dilations >= 1")
+    most = int(lib.edgl_dconv_max_reach(int(num_units), _DT[dtype]))
+    if most < 0:
+        raise ValueError(f"{who}: num_units={num_units} unsupported; the HIP convolution takes a power of two in [32, 512] (--num_units)")
+    reach = (int(filter_width) - 1) * int(dilation)
+    if reach > most:
+        raise ValueError(f"{who}: (filter_width - 1) * dilation = {reach} rows of halo, but the LDS image holds {most} at "
+                         f"num_units={num_units} in {str(dtype).replace('torch.', '')}: lower --dilations, --filter_width or --num_units")
+
+
+class DConvLnFn(torch.autograd.Function):
+    """y = relu(layernorm(dilated_conv(x; W, bias, d, causal))) (+ r): Conv1D + layernorm + relu of MaskedCNN (sequential.py:140-207)
+    in one kernel.  x [B,T,C], w [fw,C,C] (tap, in, out), bias / gamma / beta [C] (f32 masters), w_c = w in the activation dtype,
+    r: optional residual [B,T,C] added behind the ReLU.  Saves z, the row mean / rstd and the packed ReLU mask the forward
+    decided from its f32 values (the backward reads those bits).  No f32 atomics: the gradients are bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, w_master, bias, gamma, beta, w_c, dilation, causal, r=None):
+        B, T, C = x.shape
+        fw = w_c.shape[0]
+        if tuple(w_c.shape) != (fw, C, C) or w_c.dtype != x.dtype:
+            raise _lib.EdglError(f"DConvLnFn: w_c must be [fw, {C}, {C}] in {x.dtype} (got {tuple(w_c.shape)} {w_c.dtype})")
+        dconv_check(C, fw, dilation, x.dtype)
+        if not 1 <= T <= 1024:
+            raise ValueError(f"DConvLnFn: T={T} unsupported; the HIP convolution takes 1 <= T <= 1024 (--seqslen)")
+        code = _code(x)
+        x, w_c = x.contiguous(), w_c.contiguous()
+        r = None if r is None else r.contiguous()
+        need = any(ctx.needs_input_grad)
+        y = torch.empty_like(x)
+        wt = torch.empty_like(w_c)
+        z = torch.empty_like(x) if need else None
+        stats = torch.empty((2, B * T), device=x.device, dtype=torch.float32) if need else None
+        mask = torch.empty(B * T * C // 4, device=x.device, dtype=torch.uint8) if need else None
+        check(lib.edgl_dconv_ln_fwd(_ptr(x), _ptr(w_c), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(r), B, T, C, fw, int(dilation),
+                                    int(bool(causal)), _ptr(wt), _ptr(y), _ptr(z), _ptr(stats), _ptr(mask), code, _stream()), "edgl_dconv_ln_fwd")
+        ctx.save_for_backward(x, w_c, gamma, beta, z, stats, mask)
+        ctx.meta = (B, T, C, fw, int(dilation), int(bool(causal)), code, r is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_c, gamma, beta, z, stats, mask = ctx.saved_tensors
+        B, T, C, fw, d, causal, code, has_r = ctx.meta
+        dy = dy.contiguous()
+        dz, dx = torch.empty_like(x), torch.empty_like(x)
+        dw = torch.empty((fw, C, C), device=x.device, dtype=torch.float32)
+        dvec = torch.empty(3 * C, device=x.device, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_dconv_bwd_workspace(B, T, C, fw)), device=x.device, dtype=torch.float32)
+        check(lib.edgl_dconv_ln_bwd(_ptr(x), _ptr(w_c), _ptr(gamma), _ptr(beta), _ptr(z), _ptr(stats), _ptr(mask), _ptr(dy), B, T, C, fw, d, causal,
+                                    _ptr(dz), _ptr(dx), _ptr(dw), _ptr(dvec), _ptr(ws), code, _stream()), "edgl_dconv_ln_bwd")
+        return dx, dw, dvec[2 * C:], dvec[:C], dvec[C:2 * C], None, None, None, (dy if has_r else None)
+
+
+class GeluTanhFn(torch.autograd.Function):
+    """The tanh form of GELU (GREC.py:14-26) as an op of its own behind a dense layer."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        check(lib.edgl_gelu_tanh_fwd(_ptr(x), _ptr(y), x.numel(), _code(x), _stream()), "edgl_gelu_tanh_fwd")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        check(lib.edgl_gelu_tanh_bwd(_ptr(x), _ptr(dy), _ptr(dx), x.numel(), _code(x), _stream()), "edgl_gelu_tanh_bwd")
+        return dx
+
+
+class GatherReluFn(torch.autograd.Function):
+    """relu(batch_gather(x, pos)) (GREC.py:88-97): x [B,T,C], pos int64 [B,M] -> [B,M,C]."""
+
+    @staticmethod
+    def forward(ctx, x, pos):
+        x, pos = x.contiguous(), pos.to(torch.int64).contiguous()
+        B, T, C = x.shape
+        M = pos.shape[1]
+        out = torch.empty((B, M, C), device=x.device, dtype=x.dtype)
+        check(lib.edgl_gather_relu_fwd(_ptr(x), _ptr(pos), _ptr(out), B, T, M, C, _code(x), _stream()), "edgl_gather_relu_fwd")
+        ctx.save_for_backward(out, pos)
+        ctx.T = T
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        out, pos = ctx.saved_tensors
+        B, M, C = out.shape
+        dout = dout.contiguous()
+        dx = torch.empty((B, ctx.T, C), device=out.device, dtype=out.dtype)
+        check(lib.edgl_gather_relu_bwd(_ptr(out), _ptr(dout), _ptr(pos), _ptr(dx), B, ctx.T, M, C, _code(out), _stream()),
+              "edgl_gather_relu_bwd")
+        return dx, None

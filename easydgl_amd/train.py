@@ -1,7 +1,7 @@
 """Train / evaluate driver — the role of the reference's ``src/main.py:78-151`` with ``util.EarlyStopping``
 (``src/util.py:14-58``), on the HIP model.
 
-Models: EasyDGL (masked batches, ``MAUPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC (regressive batches,
+Models: EasyDGL (masked batches, ``MAUPostProcessor``), GREC (host-side masked batches, ``GRECPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC (regressive batches,
 ``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``); TimelyREC is fed regressively with the four
 calendar fields of its records (``has_datetime=True``), derived from ``seqs_t`` where the files lack them.
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
@@ -35,7 +35,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC or TGREC (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC, TGREC or GREC (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512
@@ -49,6 +49,9 @@ def args(argv=None):
                    help="TimelyREC: the calendar-slot window of a granularity is max(int(range * window_ratio + 0.5), 1) + 1; in (0, 0.5]")
     p.add_argument("--masklen", type=int, default=6)
     p.add_argument("--timelen", type=int, default=256)
+    p.add_argument("--filter_width", type=int, default=3, help="GREC: taps of every dilated convolution (1 to 5)")
+    p.add_argument("--dilations", type=str, default="1,2,2,4",
+                   help="GREC: one unit of two convolutions (dilation d, then 2d) per entry, in the encoder and in the decoder")
     p.add_argument("--mark", type=str, help="mark data file (pickled csr matrix or .npy)")
     p.add_argument("--ct_reg", type=float, default=0.0)
     p.add_argument("--batch_size", type=int, default=128)
@@ -295,6 +298,12 @@ def run(FLAGS) -> Dict[str, float]:
 
     torch.manual_seed(FLAGS.seed)
     rng = np.random.default_rng(FLAGS.seed)
+    grec = FLAGS.model == "GREC"
+    if grec:     # host-side masked batches only (no device loader, no captured step, no lazy Adam)
+        for flag in ("device_data", "graph", "lazy_adam"):
+            if getattr(FLAGS, flag, False):
+                raise ValueError(f"--{flag} with --model GREC: not supported; its masked batches are drawn on the host and every "
+                                 "batch goes through model.train_step")
     logging.info("1. read data")
     tr_i, tr_t = F.load_sequences(FLAGS.train, FLAGS.seqslen)
     vl_i, vl_t = F.load_sequences(FLAGS.valid, FLAGS.seqslen)
@@ -385,6 +394,7 @@ def run(FLAGS) -> Dict[str, float]:
     ckpt = os.path.join(FLAGS.ckpt_dir, f"{FLAGS.model}.pt")
     stopper = EarlyStopping(FLAGS.model, patience=FLAGS.patience, saver=lambda: save_checkpoint(model, ckpt))
     mask_state = torch.tensor([FLAGS.seed, 0], dtype=torch.int64, device="cuda")   # (seed, batch counter) of the masker
+    mask_gen = torch.Generator().manual_seed(FLAGS.seed)      # GREC: the host-side draws of the masked positions
     gstep = None
 
     logging.info("3. train and evaluate model")
@@ -411,6 +421,9 @@ def run(FLAGS) -> Dict[str, float]:
                 if masked:
                     feats, labels = D.device_mask_random(tok, tim, model.mask, FLAGS.masklen, mask_state)
                     mask_state[1] += 1
+                elif grec:
+                    pos = D.draw_masked_positions(len(idx), tok.shape[1], FLAGS.masklen, mask_gen).cuda()
+                    feats, labels = D.grec_mask_random(tok, model.mask_id, pos)
                 elif cals is not None:
                     feats, labels = regressive_calendar_batch(tok, tim, [torch.as_tensor(a[idx]).cuda() for a in cals["train"]], True)
                 else:

@@ -27,4 +27,10 @@ def ranking(FLAGS):
     if FLAGS.model == "TGREC":
         from .model import TGREC
         return TGREC(FLAGS.num_items, FLAGS)
+    # GREC is built from a flags object that carries the model's flags (the driver's and every caller's that sets num_items); a
+    # namespace with nothing but the model name keeps the answer it had before the model existed (tests/test_cpu_seq_baselines.py
+    # pins it), i.e. it falls through to the refusal below
+    if FLAGS.model == "GREC" and hasattr(FLAGS, "num_items"):
+        from .model import GREC
+        return GREC(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

@@ -967,6 +967,35 @@ int edgl_tgattn_bwd(const void* q, const void* u, const void* kv, const float* t
                     const void* d_g, void* saved, int B, int T, int H, int C, float scale, float time_scale,
                     float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_q, void* d_u, void* d_kv,
                     float* d_omega, float* d_phi, float* workspace, int dtype, void* stream);
+/* ---- K13: dilated 1-D convolution with LayerNorm / ReLU epilogue (GREC; csrc/k_dconv.hip) ----------------
+ * Conv1D + layernorm + relu of MaskedCNN (sequential.py:140-207).  x [B,T,C] (`dtype`), w [fw,C,C] (`dtype`; tap, in, out),
+ * bias / gamma / beta f32 [C], dilation d >= 1, causal: left pad (fw-1) d, else SAME over (fw-1) d + 1; r (may be NULL): a
+ * residual [B,T,C] added behind the ReLU.  y = relu(gamma (z - mean) rstd + beta) + r with z = conv + bias, biased variance,
+ * eps 1e-8, all on the f32 accumulators.  wt: scratch of fw C C elements (`dtype`; the
+ * forward's [tap][out][in] copy of w).  z [B,T,C] (`dtype`), stats f32 [2, B*T] (mean | rstd) and mask (B*T*C/4 bytes: the ReLU decisions of
+ * the f32 values, four channels per byte — the backward reads these bits, it does not re-derive them from the rounded z) are
+ * saved for the backward, all three NULL for inference.  C a power of two in [32, 512], 1 <= T <= 1024, 1 <= fw <= 5, (fw-1) d <= edgl_dconv_max_reach(C,
+ * dtype) (what the 160 KB LDS image holds beside a 64-row block; -1: bad C / dtype); else EDGL_ERR_SHAPE before any launch.
+ * edgl_dconv_ln_bwd: dy -> dz [B,T,C] (`dtype`, d loss / d z), dx [B,T,C] (`dtype`), dw f32 [fw,C,C], dvec f32 [3C] =
+ * dgamma | dbeta | dbias (all overwritten; per-workgroup partials summed in a fixed order, no f32 atomics: the results are
+ * bitwise reproducible).  The residual's gradient is dy itself.  workspace >= edgl_dconv_bwd_workspace(B, T, C, fw) floats. */
+int edgl_dconv_max_reach(int C, int dtype);
+long edgl_dconv_bwd_workspace(int B, int T, int C, int fw);
+int edgl_dconv_ln_fwd(const void* x, const void* w, const float* bias, const float* gamma, const float* beta, const void* r,
+                      int B, int T, int C, int fw, int d, int causal, void* wt, void* y, void* z, float* stats, void* mask,
+                      int dtype, void* stream);
+int edgl_dconv_ln_bwd(const void* x, const void* w, const float* gamma, const float* beta, const void* z, const float* stats,
+                      const void* mask, const void* dy, int B, int T, int C, int fw, int d, int causal, void* dz, void* dx, float* dw,
+                      float* dvec, float* workspace, int dtype, void* stream);
+/* GREC's small row ops (k_dconv.hip).  y = tanh-GELU(x) (GREC.py:14-26) and dx = dy * GELU'(x), n elements.
+ * edgl_gather_relu_fwd: out[b,m,:] = relu(x[b, pos[b,m], :]), x [B,T,C], pos int64 [B,M] (a position outside [0,T) reads
+ * zeros); _bwd: dx [B,T,C] = the rows of dout where out > 0, summed per position in the order of m (every element of dx is
+ * written once: no atomics, repeated positions are fine). */
+int edgl_gelu_tanh_fwd(const void* x, void* y, long n, int dtype, void* stream);
+int edgl_gelu_tanh_bwd(const void* x, const void* dy, void* dx, long n, int dtype, void* stream);
+int edgl_gather_relu_fwd(const void* x, const int64_t* pos, void* out, int B, int T, int M, int C, int dtype, void* stream);
+int edgl_gather_relu_bwd(const void* out, const void* dout, const int64_t* pos, void* dx, int B, int T, int M, int C, int dtype,
+                         void* stream);
 /* y = x * (ids != 0) per row: `seqs_outs *= seqs_masks` (TGAT.py:58,70; TiSASREC.py:73); its own backward. */
 int edgl_mask_rows(const void* x, const int64_t* ids, void* y, long rows, int C, int dtype, void* stream);
 
