@@ -1,7 +1,8 @@
 """Mirror of src/module/sequential.py: MultiHeadAttention (Vaswani et al., the unit of SASRec) on the generic masked attention
 kernel in its plain-head form (Dq == Dv, csrc/k_tattn.hip), and the GRU layer S2PNM puts in front of it (the reference's
 compat/cudnn_rnn.py CudnnGRU) on the recurrence kernel csrc/k_gru.hip; TimelyREC's MATEncoder and TAHEncoder on csrc/k_mate.hip
-and csrc/k_tahe.hip; GREC's MaskedCNN (two dilated convolutions, each with LayerNorm and ReLU, and a residual) on csrc/k_dconv.hip."""
+and csrc/k_tahe.hip; GREC's MaskedCNN (two dilated convolutions, each with LayerNorm and ReLU, and a residual) on csrc/k_dconv.hip;
+BERT4REC's BERTAttention (bidirectional, key mask only, no residual) on csrc/k_battn.hip."""
 from __future__ import annotations
 
 import torch
@@ -123,6 +124,33 @@ def truncated_normal_(t: torch.Tensor, gen: torch.Generator, std: float = 0.02) 
     with torch.no_grad():
         t.copy_(v * std)
     return t
+
+
+class BERTAttention(nn.Module):
+    """sequential.py:86-137 (BERT's self-attention, the unit of BERT4REC).  ``qkv_kernel`` [C, 3C] / ``qkv_bias`` [3C] hold the
+    reference's Q | K | V dense layers as column blocks: the three read the same input, so they run as ONE GEMM and the
+    attention kernel (csrc/k_battn.hip) reads its operands as column blocks of that output.  Each block is truncated-normal with
+    sigma 0.02, the biases zero.  Bidirectional: the only mask is the key mask ``ids != 0`` (BERT4REC.py:75-77), a masked score is
+    REPLACED by float32(-2^32+1); no residual and no LayerNorm inside.
+
+    ``forward(queries, keys, ids, is_training, drop=...)``: the reference's arguments with the key ids in place of the [B,T,T]
+    mask it builds from them; ``queries is keys`` is the only form the reference uses (BERT4REC.py:90) and the only one taken."""
+
+    def __init__(self, num_units, num_heads, dropout_rate, gen=None):
+        super().__init__()
+        dh = num_units // num_heads if num_heads > 0 and num_units % num_heads == 0 else 0
+        ops.battn_check(1, num_heads, dh, torch.float32, "BERTAttention")
+        self.num_units, self.num_heads, self.dropout_rate = num_units, num_heads, dropout_rate
+        qkv = torch.cat([truncated_normal_(torch.empty(num_units, num_units), gen) for _ in range(3)], dim=1)
+        self.qkv_kernel = nn.Parameter(qkv)                                                           # Q | K | V
+        self.qkv_bias = nn.Parameter(torch.zeros(3 * num_units))
+        self.compute = lambda p: p  # replaced by the owning model (bf16 shadow lookup)
+
+    def forward(self, queries, keys, ids, is_training, *, drop: ops.Drop = ops.NO_DROP):
+        if keys is not queries:
+            raise ValueError("BERTAttention: the HIP path takes queries is keys (BERT4REC.py:90)")
+        qkv = ops.LinearFn.apply(queries, self.qkv_kernel, self.qkv_bias, self.compute(self.qkv_kernel), False)
+        return ops.BertAttnFn.apply(qkv, ids, self.num_heads, drop if is_training else ops.NO_DROP)
 
 
 class Conv1D(nn.Module):

@@ -2259,6 +2259,56 @@ class DConvLnFn(torch.autograd.Function):
         return dx, dw, dvec[2 * C:], dvec[:C], dvec[C:2 * C], None, None, None, (dy if has_r else None)
 
 
+# ------------------------------------------------------------------------------------------------
+# K14: bidirectional attention staged through LDS (BERT4REC; csrc/k_battn.hip)
+# ------------------------------------------------------------------------------------------------
+def battn_check(T: int, H: int, dh: int, dtype: torch.dtype, who: str = "BertAttnFn") -> None:
+    """Refuses, before any launch and with the flag names, a shape edgl_battn_* does not tile (edgl_battn_supported)."""
+    code = _DT.get(dtype)
+    if code is None:
+        raise ValueError(f"{who}: activation dtype {dtype} unsupported; the HIP attention takes float32 or bfloat16 (--dtype)")
+    if not lib.edgl_battn_supported(int(T), int(H), int(dh), code):
+        raise ValueError(f"{who}: head dim {dh} with {H} heads over {T} positions unsupported; the HIP bidirectional attention takes "
+                         "a head dim num_units/num_heads of 16 / 32 / 64 / 128 (--num_units / --num_heads) and 1 <= seqslen + 1 <= "
+                         "1025 positions (--seqslen)")
+
+
+class BertAttnFn(torch.autograd.Function):
+    """BERTAttention after its three dense layers (sequential.py:111-137): qkv [B,T,3C] = Q | K | V column blocks of one projection
+    output, ids int64 [B,T] (a key with id 0 has its score replaced); out [B,T,C] = dropout(softmax(Q K^T / sqrt(dh))) V per head,
+    no residual.  The backward returns d_qkv; no f32 atomics, so it is bitwise reproducible as it stands."""
+
+    @staticmethod
+    def forward(ctx, qkv, ids, H, drop: Drop):
+        B, T, C3 = qkv.shape
+        C = C3 // 3
+        dh = C // H if H > 0 and C3 == 3 * C and C % H == 0 else 0
+        battn_check(T, H, dh, qkv.dtype)
+        if ids.dtype != torch.int64 or tuple(ids.shape) != (B, T) or not ids.is_contiguous():
+            raise _lib.EdglError(f"attention key ids must be a contiguous int64 [B={B}, T={T}] tensor, got {tuple(ids.shape)} {ids.dtype}")
+        code = _code(qkv)
+        qkv = qkv.contiguous()
+        out = torch.empty((B, T, C), device=qkv.device, dtype=qkv.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty(int(lib.edgl_battn_saved_bytes(B, T, H)), device=qkv.device, dtype=torch.uint8) if need else None
+        scale = 1.0 / float(dh) ** 0.5                                                   # sequential.py:120
+        check(lib.edgl_battn_fwd(_ptr(qkv), _ptr(ids), B, T, H, C, scale, float(drop.rate), drop.ptr(), drop.stream_id, _ptr(out),
+                                 _ptr(saved), code, _stream()), "edgl_battn_fwd")
+        ctx.save_for_backward(qkv, ids, out, saved)
+        ctx.meta = (B, T, C, H, scale, drop, code)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qkv, ids, out, saved = ctx.saved_tensors
+        B, T, C, H, scale, drop, code = ctx.meta
+        d_out = d_out.contiguous()
+        d_qkv = torch.empty_like(qkv)
+        check(lib.edgl_battn_bwd(_ptr(qkv), _ptr(ids), _ptr(out), _ptr(d_out), _ptr(saved), B, T, H, C, scale, float(drop.rate),
+                                 drop.ptr(), drop.stream_id, _ptr(d_qkv), code, _stream()), "edgl_battn_bwd")
+        return d_qkv, None, None, None
+
+
 class GeluTanhFn(torch.autograd.Function):
     """The tanh form of GELU (GREC.py:14-26) as an op of its own behind a dense layer."""
 

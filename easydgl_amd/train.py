@@ -1,7 +1,7 @@
 """Train / evaluate driver — the role of the reference's ``src/main.py:78-151`` with ``util.EarlyStopping``
 (``src/util.py:14-58``), on the HIP model.
 
-Models: EasyDGL (masked batches, ``MAUPostProcessor``), GREC (host-side masked batches, ``GRECPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC (regressive batches,
+Models: EasyDGL and BERT4REC (masked batches, ``MAUPostProcessor``), GREC (host-side masked batches, ``GRECPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC (regressive batches,
 ``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``); TimelyREC is fed regressively with the four
 calendar fields of its records (``has_datetime=True``), derived from ``seqs_t`` where the files lack them.
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
@@ -35,7 +35,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC, TGREC or GREC (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC, TGREC, GREC or BERT4REC (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512
@@ -304,6 +304,11 @@ def run(FLAGS) -> Dict[str, float]:
             if getattr(FLAGS, flag, False):
                 raise ValueError(f"--{flag} with --model GREC: not supported; its masked batches are drawn on the host and every "
                                  "batch goes through model.train_step")
+    if FLAGS.model == "BERT4REC":     # EasyDGL's masked batches through model.train_step (model/bert4rec.py: Not built)
+        for flag in ("device_data", "graph"):
+            if getattr(FLAGS, flag, False):
+                raise ValueError(f"--{flag} with --model BERT4REC: not supported; every batch is masked per step and goes through "
+                                 "model.train_step")
     logging.info("1. read data")
     tr_i, tr_t = F.load_sequences(FLAGS.train, FLAGS.seqslen)
     vl_i, vl_t = F.load_sequences(FLAGS.valid, FLAGS.seqslen)
@@ -338,7 +343,7 @@ def run(FLAGS) -> Dict[str, float]:
     model = ranking(FLAGS)
     model.finalize(torch.device("cuda", torch.cuda.current_device()))
     bs = FLAGS.batch_size
-    masked = FLAGS.model == "EasyDGL"          # MAUPostProcessor; every other model is fed regressively (util.py:99-129)
+    masked = hasattr(model, "mask")            # MAUPostProcessor (EasyDGL, BERT4REC); the others are fed regressively (util.py:99-129)
     if FLAGS.model == "TGAT":                  # the time feature map needs time-sorted sequences (model/tgat.py)
         for name, (ii, tt) in (("train", (tr_i, tr_t)), ("valid", (vl_i, vl_t)), ("test", (te_i, te_t))):
             if np.any((np.diff(tt, axis=1) < 0) & (ii[:, :-1] != 0)):
@@ -369,7 +374,7 @@ def run(FLAGS) -> Dict[str, float]:
         if getattr(FLAGS, "eval_neg_sampler", "uniform") == "popularity":
             eval_dist = model.negative_dist(w, T_reject=int(vl_i.shape[1]))       # (a sequence rejects its history and its label)
     # sampled-softmax training: no static engine, every batch through model.train_step
-    engine =TrainEngine(model, bs, use_graph=engine_graph) if (masked and len(tr_i) >= bs and train_negatives <= 0 and shared_negatives <= 0) else None
+    engine = TrainEngine(model, bs, use_graph=engine_graph) if (model.static_engine_ok and masked and len(tr_i) >= bs and train_negatives <= 0 and shared_negatives <= 0) else None
     loader = vl_loader = te_loader = None
     if device_data:
         need = sum(D.DeviceSplit.nbytes(ii, tt) + 4 * len(ii) for ii, tt in ((tr_i, tr_t), (vl_i, vl_t), (te_i, te_t)))

@@ -996,6 +996,24 @@ int edgl_gelu_tanh_bwd(const void* x, const void* dy, void* dx, long n, int dtyp
 int edgl_gather_relu_fwd(const void* x, const int64_t* pos, void* out, int B, int T, int M, int C, int dtype, void* stream);
 int edgl_gather_relu_bwd(const void* out, const void* dout, const int64_t* pos, void* dx, int B, int T, int M, int C, int dtype,
                          void* stream);
+/* ---- K14: bidirectional attention staged through LDS (BERT4REC; csrc/k_battn.hip) -------------------------
+ * BERTAttention.__call__ (sequential.py:111-137) after its three dense layers.  qkv [B,T,3C] (`dtype`; Q | K | V column blocks of
+ * one projection output, heads are contiguous C/H-wide slices), ids int64 [B,T].  S = Q K^T * scale; a score whose key has id 0
+ * is REPLACED by float32(-2^32+1); softmax over all T keys; dropout on the probabilities (element index (b' T + q) T + k with
+ * the head-major b' = head B + b); out [B,T,C] = P V, no residual.  A 64-key block of padded keys is skipped in a sample that
+ * has a real key (its probabilities are exactly 0); a sample without one is uniform over all T keys.
+ * saved (NULL for inference): edgl_battn_saved_bytes bytes (row max | row sum | D).
+ * C/H in {16, 32, 64, 128}, 1 <= T <= 1025, H*B*T*T < 2^32; edgl_battn_supported answers without a launch (1 / 0); anything
+ * else is EDGL_ERR_SHAPE before any launch.
+ * edgl_battn_bwd: out, d_out [B,T,C] -> d_qkv [B,T,3C] (`dtype`, every element written).  Two sweeps, no f32 atomics: two
+ * calls give the same bits.  Replaced scores carry no gradient to Q / K; dV of a padded key is real in an all-padding sample. */
+int edgl_battn_supported(int T, int H, int dh, int dtype);
+long edgl_battn_saved_bytes(int B, int T, int H);
+int edgl_battn_fwd(const void* qkv, const int64_t* ids, int B, int T, int H, int C, float scale, float drop_rate,
+                   const uint64_t* rng_state, uint32_t stream_id, void* out, void* saved, int dtype, void* stream);
+int edgl_battn_bwd(const void* qkv, const int64_t* ids, const void* out, const void* d_out, void* saved, int B, int T, int H,
+                   int C, float scale, float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_qkv, int dtype,
+                   void* stream);
 /* y = x * (ids != 0) per row: `seqs_outs *= seqs_masks` (TGAT.py:58,70; TiSASREC.py:73); its own backward. */
 int edgl_mask_rows(const void* x, const int64_t* ids, void* y, long rows, int C, int dtype, void* stream);
 
