@@ -94,14 +94,17 @@ class GRU(nn.Module):
     dropout): gate order r, z, n.  ``w_kernel`` [in, 3C] / ``w_bias`` [3C] act on the input, ``r_kernel`` [C, 3C] / ``r_bias`` [3C]
     on the state; the gate blocks are column blocks, each of the six matrices drawn with the orthogonal initialiser, the six
     biases zero (cudnn_rnn.py:340-355; the opaque cuDNN blob is these twelve canonical parts).  Padded positions are NOT skipped:
-    a zero input row still moves the state through the biases.  ``forward(x)``: x [B,T,in] -> h [B,T,C]."""
+    a zero input row still moves the state through the biases.  ``forward(x)``: x [B,T,in] -> h [B,T,C].  ``wide``: where R is
+    not LDS-resident at the activation dtype the recurrence runs on the pipelined stream (csrc/k_gru_wide.hip); a
+    resident pack is at its LDS form already and keeps the existing kernels."""
 
-    def __init__(self, num_units, in_units=None, gen=None):
+    def __init__(self, num_units, in_units=None, gen=None, wide=False):
         super().__init__()
         if num_units % 16 or not 16 <= num_units <= 512:
             raise ValueError(f"GRU: num_units={num_units} unsupported; the HIP recurrence takes a multiple of 16 in [16, 512]")
         in_units = num_units if in_units is None else in_units
         self.num_units = num_units
+        self.wide = bool(wide)
         self.w_kernel = nn.Parameter(torch.cat([orthogonal_(torch.empty(in_units, num_units), gen) for _ in range(3)], dim=1))
         self.w_bias = nn.Parameter(torch.zeros(3 * num_units))
         self.r_kernel = nn.Parameter(torch.cat([orthogonal_(torch.empty(num_units, num_units), gen) for _ in range(3)], dim=1))
@@ -110,7 +113,8 @@ class GRU(nn.Module):
 
     def forward(self, x):
         xp = ops.LinearFn.apply(x, self.w_kernel, self.w_bias, self.compute(self.w_kernel), False)
-        return ops.GruSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel))
+        wide = self.wide and ops.lib.edgl_gru_seq_resident(self.num_units, ops._DT[xp.dtype]) == 0
+        return ops.GruSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel), wide)
 
 
 def truncated_normal_(t: torch.Tensor, gen: torch.Generator, std: float = 0.02) -> torch.Tensor:

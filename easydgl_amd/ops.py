@@ -1747,10 +1747,11 @@ class GruSeqFn(torch.autograd.Function):
     """The GRU recurrence over xp = x W + b_W (edgl_gru_seq_fwd / bwd): h [B,T,C] from xp [B,T,3C], R [C,3C] (r_c: its
     compute copy), b_R [3C].  Gate order r | z | n, cuDNN's form, zero initial state.  The backward carries dh in f32 through the
     recurrence and returns d_xp; dR = H_prev^T dG_h and db_R are one dense_grads call over the B*T rows.  No atomics anywhere:
-    the same bits in every call, so FLAGS.deterministic needs no second form."""
+    the same bits in every call, so FLAGS.deterministic needs no second form.  `wide`: the pipelined stream of R
+    (edgl_gru_wide_fwd / bwd) — same results and saved tensors, for the widths whose R is not LDS-resident."""
 
     @staticmethod
-    def forward(ctx, xp, r_master, r_bias, r_c):
+    def forward(ctx, xp, r_master, r_bias, r_c, wide=False):
         B, T, C3 = xp.shape
         C = C3 // 3
         xp = xp.contiguous()
@@ -1767,29 +1768,29 @@ class GruSeqFn(torch.autograd.Function):
         saved = torch.empty((B, T, 5 * C), device=xp.device, dtype=torch.float32) if need else None
         # the A operand of dR: in f32 mode the h_prev block of `saved` itself, else a copy in the activation dtype
         hprev = torch.empty((B, T, C), device=xp.device, dtype=xp.dtype) if need and xp.dtype != torch.float32 else None
-        check(lib.edgl_gru_seq_fwd(_ptr(xp), _ptr(r_c), _ptr(r_bias), B, T, C, _ptr(h), _ptr(saved), _ptr(hprev), _ptr(pack), code,
-                                   _stream()), "edgl_gru_seq_fwd")
+        fwd, who = (lib.edgl_gru_wide_fwd, "edgl_gru_wide_fwd") if wide else (lib.edgl_gru_seq_fwd, "edgl_gru_seq_fwd")
+        check(fwd(_ptr(xp), _ptr(r_c), _ptr(r_bias), B, T, C, _ptr(h), _ptr(saved), _ptr(hprev), _ptr(pack), code, _stream()), who)
         ctx.save_for_backward(r_c, saved, hprev)
-        ctx.meta = (B, T, C, code)
+        ctx.meta = (B, T, C, code, bool(wide))
         return h
 
     @staticmethod
     def backward(ctx, d_h):
         r_c, saved, hprev = ctx.saved_tensors
-        B, T, C, code = ctx.meta
+        B, T, C, code, wide = ctx.meta
         d_h = d_h.contiguous()
         d_xp = torch.empty((B, T, 3 * C), device=d_h.device, dtype=d_h.dtype)
         d_gh = torch.empty_like(d_xp)
         pack = torch.empty(int(lib.edgl_gru_seq_pack_bytes(C, code)), device=d_h.device, dtype=torch.uint8)
-        check(lib.edgl_gru_seq_bwd(_ptr(d_h), _ptr(r_c), _ptr(saved), B, T, C, _ptr(d_xp), _ptr(d_gh), _ptr(pack), code, _stream()),
-              "edgl_gru_seq_bwd")
+        bwd, who = (lib.edgl_gru_wide_bwd, "edgl_gru_wide_bwd") if wide else (lib.edgl_gru_seq_bwd, "edgl_gru_seq_bwd")
+        check(bwd(_ptr(d_h), _ptr(r_c), _ptr(saved), B, T, C, _ptr(d_xp), _ptr(d_gh), _ptr(pack), code, _stream()), who)
         hp = saved.view(B * T, 5 * C)[:, 4 * C:] if hprev is None else hprev.view(B * T, C)      # (row stride 5C / C)
         M, N = B * T, 3 * C
         both = torch.empty((C + 1) * N, device=d_h.device, dtype=torch.float32)
         ws = torch.empty(lib.edgl_gemm_dw_workspace(M, C, N, code), device=d_h.device, dtype=torch.float32)
         check(lib.edgl_gemm_dw(_vptr(hp), _ptr(d_gh), _ptr(both), both.data_ptr() + 4 * C * N, M, C, N, hp.stride(0), N, 0, _ptr(ws), code,
                                _stream()), "edgl_gemm_dw")
-        return d_xp, both[:C * N].view(C, N), both[C * N:], None
+        return d_xp, both[:C * N].view(C, N), both[C * N:], None, None
 
 
 class CatPosMaskFn(torch.autograd.Function):

@@ -36,4 +36,7 @@ def ranking(FLAGS):
     if FLAGS.model == "BERT4REC" and hasattr(FLAGS, "num_items"):     # (as GREC: the bare namespace keeps its refusal)
         from .model import BERT4REC
         return BERT4REC(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "GRU4REC" and hasattr(FLAGS, "num_items"):      # (as GREC: the bare namespace keeps its refusal)
+        from .model import GRU4REC
+        return GRU4REC(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

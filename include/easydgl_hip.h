@@ -1176,6 +1176,15 @@ int edgl_gru_seq_fwd(const void* xp, const void* R, const float* b_R, int B, int
                      void* hprev_c, void* pack, int dtype, void* stream);
 int edgl_gru_seq_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* d_gh,
                      void* pack, int dtype, void* stream);
+/* The same recurrence for the widths whose R is NOT LDS-resident (k_gru_wide.hip): arguments, results, saved layout,
+ * error codes and shape rules of the edgl_gru_seq_* pair (`pack`: edgl_gru_seq_pack_bytes bytes).  R is streamed from L2 through a
+ * per-wave register ring that stays in flight across the step barrier.  Every legal C is accepted (R is streamed at every
+ * width); the value is where edgl_gru_seq_resident(C, dtype) == 0.  No atomics, no waiting between workgroups: the same bits
+ * in every call. */
+int edgl_gru_wide_fwd(const void* xp, const void* R, const float* b_R, int B, int T, int C, void* h, float* saved,
+                      void* hprev_c, void* pack, int dtype, void* stream);
+int edgl_gru_wide_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* d_gh,
+                      void* pack, int dtype, void* stream);
 
 /* ---- S2PNM's element-wise pieces (S2PNM.py:52-66) and gradient clipping (k_s2pnm.hip) -----------------
  * edgl_cat_pos_mask_fwd: out [B,T,2C] = [h[b,t] | pos[t]] * (ids[b,t] != 0); h `dtype` [B,T,C], pos f32 [>=T, C].

@@ -8,8 +8,13 @@
   * one optimizer step (train_step) of SASREC and S2PNM at the published flags (runme.sh:39-55: 512 units, 8 heads / 1 head,
     2 blocks / 1 block, batch 512, seqslen 30, 17 771 items) beside TGAT's and TiSASRec's from the SAME run.
 
+  * --wide (profiles/gru_wide.txt): the pipelined stream (ops.GruSeqFn(..., wide=True), csrc/k_gru_wide.hip) beside the
+    existing path at B = 512, T in {30, 100}, C in {256, 512}, f32 and bf16 — the two ALTERNATE repeat by repeat in one process,
+    in the same device-event windows; forward microseconds per step against the L2 bound; whether h and the three gradients of
+    the two paths are bit-identical; and one GRU4REC train_step (T = 30, 17 771 items, 1 block) beside S2PNM's.
+
 Warm-up, device events around `iters` calls, `reps` repeats, median and min / max printed.
-    python tools/gru_bench.py [--iters 10] [--reps 5] [--json out.json] [--skip-models]"""
+    python tools/gru_bench.py [--iters 10] [--reps 5] [--json out.json] [--skip-models] [--wide]"""
 import argparse
 import json
 import os
@@ -50,22 +55,60 @@ def spread(fn, iters, reps):
     return dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v))
 
 
-def gru_op(T, C, dt, dev):
+def gru_op(T, C, dt, dev, wide=False):
     g = GRU(C, C, gen=torch.Generator().manual_seed(0)).to(dev)
     R, bR, Rc = g.r_kernel.detach().requires_grad_(True), g.r_bias.detach().requires_grad_(True), g.r_kernel.detach().to(dt)
     gen = torch.Generator(device=dev).manual_seed(1)
     xp = torch.randn((B, T, 3 * C), device=dev, generator=gen).to(dt).requires_grad_(True)
     d_h = torch.randn((B, T, C), device=dev, generator=gen).to(dt)
 
-    def both():
-        h = ops.GruSeqFn.apply(xp, R, bR, Rc)
+    def both(keep=False):
+        h = ops.GruSeqFn.apply(xp, R, bR, Rc, wide)
         h.backward(d_h)
+        out = (h.detach(), xp.grad, R.grad, bR.grad) if keep else None
         xp.grad = R.grad = bR.grad = None
+        return out
 
     def fwd():
         with torch.no_grad():
-            ops.GruSeqFn.apply(xp, R, bR, Rc)
+            ops.GruSeqFn.apply(xp, R, bR, Rc, wide)
     return both, fwd
+
+
+def spread_pair(fa, fb, iters, reps):
+    """Two callables timed alternately, repeat by repeat, in the same device-event windows."""
+    for _ in range(3):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    va, vb = [], []
+    for _ in range(reps):
+        va.append(timed(fa, iters))
+        vb.append(timed(fb, iters))
+    return tuple(dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v)) for v in (va, vb))
+
+
+def wide_rows(a, dev, out):
+    fmt = lambda r: f"{r['median_ms']:8.3f} ms ({r['min_ms']:.3f} - {r['max_ms']:.3f})"
+    for T in (30, 100):
+        for C in (256, 512):
+            for dt, nm in ((torch.float32, "f32"), (torch.bfloat16, "bf16")):
+                old_both, old_fwd = gru_op(T, C, dt, dev)
+                new_both, new_fwd = gru_op(T, C, dt, dev, wide=True)
+                same = all(torch.equal(x, y) for x, y in zip(old_both(keep=True), new_both(keep=True)))
+                ob, nb = spread_pair(old_both, new_both, a.iters, a.reps)
+                of, nf = spread_pair(old_fwd, new_fwd, a.iters, a.reps)
+                bounds = lower_bounds(C, 4 if nm == "f32" else 2)
+                row = dict(T=T, C=C, dtype=nm, bounds=bounds, bit_identical=same, fwd_bwd=ob, fwd=of, wide_fwd_bwd=nb, wide_fwd=nf)
+                out["wide"].append(row)
+                print(f"GRU B={B} T={T:3d} C={C:3d} {nm:4s}: fwd+bwd existing {fmt(ob)} wide {fmt(nb)}; fwd existing {fmt(of)} wide {fmt(nf)}; "
+                      f"fwd per step existing {of['median_ms'] / T * 1e3:6.2f} us wide {nf['median_ms'] / T * 1e3:6.2f} us >= "
+                      f"{bounds['mfma_us']:.2f} us MFMA / {bounds['l2_us']:.2f} us L2; h, d_xp, dR, db_R bit-identical: {'yes' if same else 'NO'}",
+                      flush=True)
+    for name, heads, blocks in (("GRU4REC", 1, 1), ("S2PNM", 1, 1)):
+        r = spread(model_step(name, heads, blocks, dev), a.iters, a.reps)
+        out["models"][name] = r
+        print(f"{name:9s} train_step B={B} T=30 C=512 H={heads} blocks={blocks} bf16: {fmt(r)}", flush=True)
 
 
 def vendor_gru(T, C, dt, dev):
@@ -116,10 +159,17 @@ def main():
     ap.add_argument("--skip-models", action="store_true")
     ap.add_argument("--vendor", choices=["on", "off", "only"], default="on",
                     help="torch.nn.GRU beside the op: on, off, or only (the vendor RNN alone, e.g. in a process of its own)")
+    ap.add_argument("--wide", action="store_true", help="the pipelined stream beside the existing path (DESIGN 4.23), and nothing else")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda", 0)
-    out = {"batch": B, "iters": a.iters, "reps": a.reps, "gru": [], "models": {}}
+    out = {"batch": B, "iters": a.iters, "reps": a.reps, "gru": [], "wide": [], "models": {}}
+    if a.wide:
+        wide_rows(a, dev, out)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     for T in (30, 100):
         for C in (128, 512):
             for dt, nm in ((torch.float32, "f32"), (torch.bfloat16, "bf16")):
