@@ -122,6 +122,10 @@ SIGNATURES = {
     "edgl_score_topk_fused_supported": (I, [I, I, I, I, I, I]),
     "edgl_score_topk_fused_workspace": (L, [I, I, I, I, I]),
     "edgl_score_topk_fused": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, I, P]),
+    "edgl_rows_to_fp8": (I, [P, I, I, I, P, P, P, P]),
+    "edgl_score_topk_fp8_supported": (I, [I, I, I, I, I]),
+    "edgl_score_topk_fp8_workspace": (L, [I, I, I, I, I]),
+    "edgl_score_topk_fp8": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, P]),
     "edgl_score_rank_supported": (I, [I, I, I, I, I]),
     "edgl_score_rank_workspace": (L, [I, I, I, I]),
     "edgl_score_rank_slices": (I, [I, I, I, I]),

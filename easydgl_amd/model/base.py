@@ -690,6 +690,69 @@ class Sequential(nn.Module):
         return ops.score_candidates(self._last_rows(features), self.compute(tab), self.output_bias, candidates,
                                     seen if mask_seen else None, lab, want_scores=False)[2]
 
+    # ---- two-stage retrieval: FP8 short list, exact re-rank -------------------------------------------------
+    @torch.no_grad()
+    def quantize_items(self) -> None:
+        """Builds the FP8 image (e4m3 bytes + one f32 scale per item) of the compute-dtype item table for retrieve().  The image
+        is a snapshot: call again after every weight update.  Raises if the table holds a non-finite value."""
+        tab = self.compute(self.item_embs.lookup_table).contiguous()
+        viol = torch.zeros(1, device=tab.device, dtype=torch.int32)
+        q8, scale = ops.rows_to_fp8(tab, viol)
+        if int(viol.item()):
+            raise RuntimeError(f"quantize_items: {int(viol.item())} rows of the item table hold a non-finite value")
+        self._fp8_items = (q8, scale, tuple(tab.shape))
+        self._fp8_violations = viol         # (zero here; retrieve() counts non-finite query rows into it: check_retrieve)
+
+    def check_retrieve(self) -> None:
+        """Raises if a retrieve() call since the last check met an encoded row with a non-finite value (such a row is scored as
+        NaN and returns an arbitrary list); reads the device counter back, so call it per pass, not per batch."""
+        viol = getattr(self, "_fp8_violations", None)
+        n = 0 if viol is None else int(viol.item())
+        if n:
+            viol.zero_()
+            raise RuntimeError(f"retrieve: {n} encoded rows held a non-finite value")
+
+    @torch.no_grad()
+    def retrieve(self, features, K, shortlist=None, mask_seen=True):
+        """(val f32, idx int32) [B, K]: the K best unseen items of the catalogue for each sequence, in two stages — an FP8 sweep
+        over the image of quantize_items() keeps `shortlist` ids per sequence (default min(4 K, 1024); K <= shortlist <= 1024),
+        ops.score_candidates re-scores them exactly on the compute-dtype table, the K best by (value desc, id asc) are returned.
+        The values are the exact scores of the returned ids; only the membership of the short list is approximate, and a short
+        list that covers the catalogue gives eval_topk's result.  A catalogue above ops.FP8_CHUNK_ITEMS items is swept in chunks whose
+        lists the merge kernel orders up to 1024 a row: the short list is then at most 512 (the default is clamped; K > 512 is
+        refused).  Non-finite query rows are counted on the device, not read back here: check_retrieve()."""
+        image = getattr(self, "_fp8_items", None)
+        if image is None:
+            raise RuntimeError("retrieve: no FP8 item image — call quantize_items() first (and again after every weight update)")
+        tab = self.compute(self.item_embs.lookup_table)
+        if image[2] != tuple(tab.shape):
+            raise RuntimeError(f"retrieve: the FP8 item image is of a table {image[2]}, the table is now {tuple(tab.shape)} — call "
+                               f"quantize_items() again")
+        most = 1024 if tab.shape[0] <= ops.FP8_CHUNK_ITEMS else 512
+        shortlist = max(K, min(4 * K, most)) if shortlist is None else int(shortlist)
+        if not K <= shortlist <= most:
+            raise ValueError(f"retrieve: shortlist={shortlist} outside [K={K}, {most}] ({most} for a table of {tab.shape[0]} items: "
+                             f"chunks of {ops.FP8_CHUNK_ITEMS} + the merge kernel's 1024 candidates a row)")
+        rows = self._last_rows(features)
+        seen = features["seqs_i"] if mask_seen else None
+        rq8, rscale = ops.rows_to_fp8(rows, self._fp8_violations)
+        _, cand = ops.score_topk_fp8(rq8, rscale, image[0], image[1], self.output_bias, seen, shortlist, 0, tab.shape[0])
+        scores = ops.score_candidates(rows, tab, self.output_bias, cand, seen)[0]
+        val, idx = ops.topk_merge(scores.unsqueeze(0), cand.unsqueeze(0))       # the whole list by (value desc, id asc)
+        return val[:, :K].contiguous(), idx[:, :K].contiguous()
+
+    @torch.no_grad()
+    def _eval_step_retrieve(self, features, labels, shortlist, mask_seen=True):
+        """evaluate(fp8_shortlist=N)'s step: eval_step's top-K step with the list of retrieve(K=100, shortlist) in place of eval_topk's: what the FP8 short list costs
+        in HR / NDCG.  Shares the top-K accumulation (not the by-rank one)."""
+        if self._metrics is None:
+            self.reset_metrics()
+        if self._rank_count:
+            raise RuntimeError("_eval_step_retrieve: by-rank and top-K steps cannot share one accumulation (call reset_metrics)")
+        _, idx = self.retrieve(features, 100, shortlist, mask_seen)
+        ops.rank_metrics(idx, labels[:, -1].contiguous(), self._metrics)
+        self._metric_count += labels.shape[0]
+
     def reset_metrics(self, ks=None):
         """`ks`: the cut-offs of the by-rank metrics (eval_step(by_rank=True)); default (10, 50, 100), at most 8."""
         dev = self._arena.device

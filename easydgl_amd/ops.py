@@ -1120,6 +1120,67 @@ def _merge_lists(cval, cidx, R, K):
     return cval[0], cidx[0]
 
 
+FP8_CHUNK_ITEMS = 262144     # item range of one edgl_score_topk_fp8 call; longer catalogues go in chunks + the merge kernel
+
+
+def rows_to_fp8(x: torch.Tensor, violations: Optional[torch.Tensor] = None):
+    """(q8 uint8 [R, C], scale f32 [R]) of f32 / bf16 rows [R, C] (csrc/k_eval_topk_fp8.hip): q8 holds OCP e4m3 (e4m3fn) bytes of
+    x / scale with scale = max|row| / 448 (1 for a zero row), rounded to nearest even.  A row with a non-finite element gets zero
+    bytes and scale NaN; `violations` (int32 [1], optional) counts such rows.  C a power of two in [32, 512]."""
+    _ptr(x)                                                  # (GPU tensors only: refused before anything else)
+    if x.dim() != 2:
+        raise _lib.EdglError(f"rows_to_fp8: rows [R, C] (got {tuple(x.shape)})")
+    R, C = x.shape
+    q8 = torch.empty((R, C), device=x.device, dtype=torch.uint8)
+    scale = torch.empty(R, device=x.device, dtype=torch.float32)
+    check(lib.edgl_rows_to_fp8(_ptr(x), R, C, _code(x), _ptr(q8), _ptr(scale), _ptr(violations), _stream()), "edgl_rows_to_fp8")
+    return q8, scale
+
+
+def score_topk_fp8(rows_q8, rows_scale, table_q8, table_scale, out_bias, seen, K, i0, i1):
+    """Stage 1 of the two-stage retrieval: (val f32, idx int32) [R, K], the K best unseen items of [i0, i1) by
+    logit = rows_scale[r] table_scale[i] sum_c q_r[c] q_i[c] + [-1000, out_bias][i] on the FP8 matrix pipe, (value desc, id asc);
+    -inf / -1 behind the last unseen item.  rows_q8 / table_q8: uint8 e4m3 bytes with their f32 row scales (rows_to_fp8); seen:
+    int64 [R, T] or None.  K <= 1024 (K <= 512 when the range needs more than one chunk of FP8_CHUNK_ITEMS: the merge kernel orders
+    1024 candidates per row)."""
+    for t in (rows_q8, rows_scale, table_q8, table_scale, out_bias):
+        _ptr(t)                                              # (GPU tensors only: refused before anything else)
+    if rows_q8.dtype != torch.uint8 or table_q8.dtype != torch.uint8 or rows_q8.dim() != 2 or table_q8.dim() != 2 \
+            or rows_q8.shape[1] != table_q8.shape[1]:
+        raise _lib.EdglError(f"score_topk_fp8: uint8 rows [R, C] and table [I, C] (got {rows_q8.dtype} {tuple(rows_q8.shape)}, "
+                             f"{table_q8.dtype} {tuple(table_q8.shape)})")
+    (R, C), I = rows_q8.shape, table_q8.shape[0]
+    if rows_scale.dtype != torch.float32 or rows_scale.shape != (R,) or table_scale.dtype != torch.float32 or table_scale.shape != (I,):
+        raise _lib.EdglError(f"score_topk_fp8: scales must be f32 [{R}] and [{I}]")
+    if seen is not None and (seen.dtype != torch.int64 or seen.dim() != 2 or seen.shape[0] != R):
+        raise _lib.EdglError(f"score_topk_fp8: seen ids must be int64 [{R}, T] (got {seen.dtype} {tuple(seen.shape)})")
+    seen = None if seen is None else seen.contiguous()
+    T = 0 if seen is None else seen.shape[1]
+    starts = list(range(i0, i1, FP8_CHUNK_ITEMS))
+    if len(starts) > 1 and i1 - starts[-1] < K:              # (a short last chunk takes from its neighbour: every range holds K items)
+        starts[-1] = max(starts[-2] + 8, (i1 - K) // 8 * 8)
+    bounds = [(lo, (starts[j + 1] if j + 1 < len(starts) else i1)) for j, lo in enumerate(starts)]
+    if len(bounds) > 1 and K > 512:
+        raise _lib.EdglError(f"score_topk_fp8: K={K} > 512 over {len(bounds)} chunks of {FP8_CHUNK_ITEMS} items (the merge kernel orders "
+                             f"up to 1024 candidates per row: two K-lists at least)")
+    span = max(hi - lo for lo, hi in bounds)
+    # (the exact fallback's [rows, items] f32 scratch is bounded by walking the rows in blocks, as score_topk does)
+    rb = R if R * span * 4 <= EVAL_FUSED_SCRATCH_BYTES else max(256, (EVAL_FUSED_SCRATCH_BYTES // (span * 4)) // 256 * 256)
+    rblocks = [(r0, min(R, r0 + rb)) for r0 in range(0, R, rb)]
+    wsb = max(int(lib.edgl_score_topk_fp8_workspace(r1 - r0, C, hi - lo, T, K)) for lo, hi in bounds for r0, r1 in rblocks)
+    st = _stream()
+    # (a shape the plan does not take has no workspace size: the call below refuses it with the bound in its text)
+    ws = _fused_eval_workspace(rows_q8.device, max(wsb, 256))
+    cval = torch.empty((len(bounds), R, K), device=rows_q8.device, dtype=torch.float32)
+    cidx = torch.empty((len(bounds), R, K), device=rows_q8.device, dtype=torch.int32)
+    for j, (lo, hi) in enumerate(bounds):
+        for r0, r1 in rblocks:
+            check(lib.edgl_score_topk_fp8(_ptr(rows_q8[r0:r1]), _ptr(rows_scale[r0:r1]), _ptr(table_q8), _ptr(table_scale), _ptr(out_bias),
+                                          None if seen is None else _ptr(seen[r0:r1]), T, r1 - r0, C, I, lo, hi, K,
+                                          _ptr(cval[j, r0:r1]), _ptr(cidx[j, r0:r1]), _ptr(ws), st), "edgl_score_topk_fp8")
+    return _merge_lists(cval, cidx, R, K)
+
+
 def rank_metrics(topk_idx: torch.Tensor, label: torch.Tensor, metrics: torch.Tensor) -> None:
     R, K = topk_idx.shape
     check(lib.edgl_rank_metrics(_ptr(topk_idx), R, K, _ptr(label), _ptr(metrics), _stream()), "edgl_rank_metrics")

@@ -84,6 +84,10 @@ def args(argv=None):
                         "user has not interacted with (ops.sample_negatives; the same N for every epoch), report H / N at 1, 5, 10 and "
                         "MRR, select the model on H10.  0: rank against the whole catalogue")
     p.add_argument("--eval_neg_seed", type=int, default=0, help="seed of the sampled negatives")
+    p.add_argument("--eval_fp8_shortlist", type=int, default=0,
+                   help="N > 0: evaluate on the lists of the two-stage retrieval (DESIGN 4.24) — an FP8 sweep keeps N ids per sequence "
+                        "(100 <= N <= 1024; at most 512 for a catalogue above 262144 items), the exact scores re-rank them — instead of the exact top-K: the same H / N metrics, so the "
+                        "difference to a plain run is what the short list costs.  0: off")
     p.add_argument("--train_negatives", type=int, default=0,
                    help="N > 0: sampled-softmax training (DESIGN 4.13) — the cross-entropy of every scored position over its label and N "
                         "negatives drawn uniformly from the catalogue (fresh lists every step) instead of the whole catalogue; every "
@@ -116,6 +120,11 @@ def args(argv=None):
         p.error("--sampled_loss needs --train_negatives N > 0 or --shared_negatives S > 0: the objective is defined over sampled negatives")
     if a.eval_neg_sampler != "uniform" and a.eval_negatives <= 0:
         p.error("--eval_neg_sampler needs --eval_negatives N > 0")
+    if a.eval_fp8_shortlist and (a.eval_by_rank or a.eval_negatives > 0):
+        p.error("--eval_fp8_shortlist with " + ("--eval_by_rank" if a.eval_by_rank else "--eval_negatives") +
+                ": the short list feeds the top-K metrics; the by-rank and sampled-negative protocols draw no list")
+    if a.eval_fp8_shortlist and not 100 <= a.eval_fp8_shortlist <= 1024:
+        p.error("--eval_fp8_shortlist: 100 <= N <= 1024 (the metrics read a top-100 list; the FP8 sweep keeps at most 1024 ids)")
     if a.train_negatives > 0 and a.shared_negatives > 0:
         p.error("--shared_negatives with --train_negatives: one estimator per run (per-row lists or one shared list)")
     if a.shared_negatives < 0 or a.shared_negatives > 8192:
@@ -246,17 +255,27 @@ def load_calendar_or_derive(patterns, seqslen, ids, ts, split):
 
 
 def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_rank: bool = False, negatives: int = 0,
-             neg_seed: int = 0, neg_dist=None, calendar=None) -> Dict[str, float]:
+             neg_seed: int = 0, neg_dist=None, calendar=None, fp8_shortlist: int = 0) -> Dict[str, float]:
     """One pass of ``Sequential.eval`` (Base.py:150-207) over a split: last position masked (EasyDGL) or predicted from the
     prefix (regressive models), streaming means.  `loader`: a data.DeviceLoader in an evaluation mode over the resident split
     (--device_data) — the batches are then assembled on the device, in file order.  `by_rank`: the metrics from the label's rank
     (model.eval_step(by_rank=True)) — the same H / N values plus "MRR".  `negatives` > 0: the sampled-negative protocol —
     the label ranked among that many negatives per sequence, keyed by (neg_seed, step 0, the sequence's index in the split): every
     pass over a split ranks against the same lists, whatever the batch size; cut-offs (1, 5, 10).  `neg_dist` (ops.NegDist): those
-    negatives are drawn by its weights.  `calendar`: the split's four calendar arrays (TimelyREC)."""
+    negatives are drawn by its weights.  `calendar`: the split's four calendar arrays (TimelyREC).  `fp8_shortlist` > 0:
+    the top-K metrics from the lists of the two-stage retrieval (model.retrieve) with that many short-listed ids; the
+    FP8 item image is rebuilt from the current weights first.  Not with by_rank or negatives."""
     import torch
     from . import data as D
-    if negatives > 0:
+    if fp8_shortlist and (by_rank or negatives > 0):
+        raise ValueError("evaluate: fp8_shortlist with by_rank / negatives (--eval_fp8_shortlist with --eval_by_rank / --eval_negatives)")
+    if fp8_shortlist:
+        model.reset_metrics()
+        model.quantize_items()
+
+        def step(feats, labels):
+            model._eval_step_retrieve(feats, labels, fp8_shortlist, mask_seen=mask_seen)
+    elif negatives > 0:
         model.reset_metrics((1, 5, 10))
         row0 = [0]      # running sequence offset of the split
         extra = {} if neg_dist is None else {"neg_dist": neg_dist}
@@ -269,12 +288,16 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_r
 
         def step(feats, labels):
             model.eval_step(feats, labels, mask_seen=mask_seen, by_rank=by_rank)
+    def done():
+        if fp8_shortlist:
+            model.check_retrieve()      # (one read-back per pass: a non-finite encoded row would have been scored as NaN)
+        return model.metrics()
     if loader is not None:
         loader.set_epoch(None)
         for _ in range(len(loader)):
             feats, labels = loader.next()
             step(feats, labels)
-        return model.metrics()
+        return done()
     n = ids.shape[0]
     masked = hasattr(model, "mask")
     for lo in range(0, n, batch_size):
@@ -286,7 +309,7 @@ def evaluate(model, ids, ts, batch_size: int, mask_seen: bool, loader=None, by_r
         else:
             feats, labels = D.device_mask_last(tok, tim, model.mask) if masked else regressive_batch(tok, tim, False)
         step(feats, labels)
-    return model.metrics()
+    return done()
 
 
 def run(FLAGS) -> Dict[str, float]:
@@ -356,6 +379,12 @@ def run(FLAGS) -> Dict[str, float]:
     device_data = bool(getattr(FLAGS, "device_data", False))
     by_rank = bool(getattr(FLAGS, "eval_by_rank", False))     # (the default cut-offs keep "H100": early stopping reads it either way)
     negatives, neg_seed = int(getattr(FLAGS, "eval_negatives", 0) or 0), int(getattr(FLAGS, "eval_neg_seed", 0) or 0)
+    fp8_shortlist = int(getattr(FLAGS, "eval_fp8_shortlist", 0) or 0)
+    if fp8_shortlist:
+        from . import ops as _ops
+        if fp8_shortlist > 512 and model.num_items > _ops.FP8_CHUNK_ITEMS:
+            raise ValueError(f"--eval_fp8_shortlist {fp8_shortlist}: a catalogue of {model.num_items} items is swept in chunks of "
+                             f"{_ops.FP8_CHUNK_ITEMS}, whose lists the merge kernel orders up to 1024 candidates a row: at most 512")
     select_on = "H10" if negatives > 0 else "H100"            # (H100 of N + 1 <= 101 candidates is constant)
     # --device_data --graph: the batch no longer arrives from the host, so the EasyDGL step can be replayed as one graph
     engine_graph = device_data and bool(getattr(FLAGS, "graph", False))
@@ -468,10 +497,10 @@ def run(FLAGS) -> Dict[str, float]:
         if epoch % FLAGS.eval_per_steps:
             continue
         vl = evaluate(model, vl_i, vl_t, bs, FLAGS.mask_seen, vl_loader, by_rank, negatives, neg_seed, eval_dist,
-                      None if cals is None else cals["valid"])
+                      None if cals is None else cals["valid"], fp8_shortlist)
         logging.info("%03d: %s", epoch, {k: "{0:.5f}".format(v) for k, v in vl.items()})
         te = evaluate(model, te_i, te_t, bs, FLAGS.mask_seen, te_loader, by_rank, negatives, neg_seed, eval_dist,
-                      None if cals is None else cals["test"])
+                      None if cals is None else cals["test"], fp8_shortlist)
         if stopper.step(running_loss, vl[select_on], vl, te):
             break
     return stopper.summary()

@@ -485,6 +485,22 @@ int edgl_score_topk_fused_supported(int R, int C, int n_items, int T, int K, int
 long edgl_score_topk_fused_workspace(int R, int C, int n_items, int T, int K);
 int edgl_score_topk_fused(const void* rows, const void* table, const float* out_bias, const int64_t* seen, int T, int R, int C,
                           int I, int i0, int i1, int K, float* out_val, int32_t* out_idx, void* workspace, int dtype, void* stream);
+/* ---- K6q: FP8 item-table retrieval, stage 1.  edgl_rows_to_fp8: rows [R, C] (`dtype` f32 or bf16, 16-byte aligned)
+ * -> q8_out [R, C] OCP e4m3 bytes and scale_out f32 [R]: scale = max|row| / 448 (1 for a zero row), byte = round-to-nearest-even of
+ * row / scale (f32 division).  A row with a non-finite element gets zero bytes, scale NaN and one count added into `violations`
+ * (int32 [1], may be NULL).  C a power of two in [32, 512].  The same call serves the item table and the query rows.
+ * edgl_score_topk_fp8: logit[r, i] = rows_scale[r] * table_scale[i] * sum_c q_r[c] q_i[c] + [-1000, out_bias][i] over [i0, i1) on the
+ * FP8 matrix pipe (item 0 reads -1000), -inf at the row's seen ids (int64 [R, T], NULL with T = 0), top-K by (value desc, id asc):
+ * out_val f32 [R, K], out_idx int32 [R, K] (global ids; -inf / -1 behind the last unseen item).  Exact over these FP8 scores for any
+ * ties: a row whose candidate list overflows is redone from its scores in a scratch row.  C a power of two in [32, 512],
+ * 1 <= K <= 1024, i0 % 8 == 0, K <= i1 - i0 <= 262144 per call (longer catalogues: item chunks + edgl_topk_merge); anything else is
+ * EDGL_ERR_SHAPE with the bound in the text, before any launch.  _supported: 1 / 0; _workspace: BYTES (-1: shape not taken). */
+int edgl_rows_to_fp8(const void* src, int R, int C, int dtype, void* q8_out, float* scale_out, int* violations, void* stream);
+int edgl_score_topk_fp8_supported(int R, int C, int n_items, int T, int K);
+long edgl_score_topk_fp8_workspace(int R, int C, int n_items, int T, int K);
+int edgl_score_topk_fp8(const void* rows_q8, const float* rows_scale, const void* table_q8, const float* table_scale,
+                        const float* out_bias, const int64_t* seen, int T, int R, int C, int I, int i0, int i1, int K,
+                        float* out_val, int32_t* out_idx, void* workspace, void* stream);
 /* ---- K7: merge of per-shard candidates (after an RCCL all-gather): cand_val/idx [S, R, K] ->
  * global top-K per row by (value desc, global index asc); entries with index < 0 are ignored; S*K <= 1024.  (Candidates above the
  * K-th largest thread maximum are ranked by counting; inputs with more than 256 of them — tie blocks — are sorted.) */
