@@ -220,6 +220,9 @@ SIGNATURES = {
     "edgl_gru_seq_bwd": (I, [P, P, P, I, I, I, P, P, P, I, P]),
     "edgl_gru_wide_fwd": (I, [P, P, P, I, I, I, P, P, P, P, I, P]),
     "edgl_gru_wide_bwd": (I, [P, P, P, I, I, I, P, P, P, I, P]),
+    "edgl_lstm_seq_pack_bytes": (L, [I, I]),
+    "edgl_lstm_seq_fwd": (I, [P, P, P, I, I, I, P, P, P, P, I, P]),
+    "edgl_lstm_seq_bwd": (I, [P, P, P, I, I, I, P, P, I, P]),
     "edgl_cat_pos_mask_fwd": (I, [P, P, P, I, I, I, P, I, P]),
     "edgl_cat_pos_mask_bwd": (I, [P, P, I, I, I, P, P, I, P]),
     "edgl_dict_feat_fwd": (I, [P, P, L, I, P, I, P]),

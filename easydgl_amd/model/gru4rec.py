@@ -18,6 +18,10 @@ The opaque cuDNN parameter blob is built under the reference's stray scope (:43)
 the weights in tf.layers.dense orientation [in, out]: ``S2PNM/Reccurency/GRU4REC/GRU/opaque_kernel/{l}/{w,r}_{r,z,n}`` and
 ``.../{l}/b_{w,r}{r,z,n}``; each of a layer's six matrices is drawn with the orthogonal initialiser, the biases are zero.
 
+``FLAGS.rnn_cell == "lstm"`` (default "gru") swaps the layers for the LSTM of the same cuDNN layer (module.sequential.LSTM on
+csrc/k_lstm.hip) and nothing else; its parts are ``.../{l}/{w,r}_{i,f,c,o}`` and ``.../{l}/b_{w,r}{i,f,c,o}`` under
+the same scope (cuDNN's canonical names: ``c`` is the candidate gate g), 2 + 16 L variables in all.
+
 Not built: channel padding (--num_units is a power of two in [32, 512]), the static TrainEngine and lazy_adam; in the driver
 --device_data, --graph and --lazy_adam are refused by flag name."""
 from __future__ import annotations
@@ -52,7 +56,13 @@ class GRU4REC(Sequential):
         if int(FLAGS.num_blocks) < 1:
             raise ValueError(f"GRU4REC: num_blocks={FLAGS.num_blocks} unsupported: the number of GRU layers, at least 1 (--num_blocks)")
         self.item_embs = C.Embedding(num_items, C_, self.l2_reg, zero_pad=True, scale=True, gen=gen)     # GRU4REC.py:24-25
-        self.layers = nn.ModuleList(S.GRU(C_, C_, gen=gen, wide=True) for _ in range(int(FLAGS.num_blocks)))   # :27-29
+        self.rnn_cell = getattr(FLAGS, "rnn_cell", "gru")
+        if self.rnn_cell not in ("gru", "lstm"):
+            raise ValueError(f"GRU4REC: rnn_cell={self.rnn_cell!r} unsupported: gru or lstm (--rnn_cell)")
+        if self.rnn_cell == "lstm":       # the CUDNN_LSTM form of the same layer (csrc/k_lstm.hip)
+            self.layers = nn.ModuleList(S.LSTM(C_, C_, gen=gen) for _ in range(int(FLAGS.num_blocks)))
+        else:
+            self.layers = nn.ModuleList(S.GRU(C_, C_, gen=gen, wide=True) for _ in range(int(FLAGS.num_blocks)))   # :27-29
         self.output_bias = self.make_output_bias()                                                        # :31
 
     def _pad_specs(self):
@@ -96,7 +106,7 @@ class GRU4REC(Sequential):
              "GRU4REC/output_bias": (self.output_bias, None)}
         for l, gru in enumerate(self.layers):
             g = GRU_SCOPE + f"{l}/"
-            for j, gate in enumerate(("r", "z", "n")):
+            for j, gate in enumerate(("i", "f", "c", "o") if self.rnn_cell == "lstm" else ("r", "z", "n")):
                 sl = slice(j * C_, (j + 1) * C_)
                 m[g + f"w_{gate}"], m[g + f"r_{gate}"] = (gru.w_kernel, sl), (gru.r_kernel, sl)
                 m[g + f"b_w{gate}"], m[g + f"b_r{gate}"] = (gru.w_bias, sl), (gru.r_bias, sl)

@@ -117,6 +117,31 @@ class GRU(nn.Module):
         return ops.GruSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel), wide)
 
 
+class LSTM(nn.Module):
+    """One unidirectional LSTM layer in cuDNN's form (compat/cudnn_rnn.py: the CUDNN_LSTM branches of _CudnnRNN; linear input,
+    zero initial h and c, no forget-gate offset, no projection, no peepholes, no dropout): gate order i, f, g, o — cuDNN's and
+    torch.nn.LSTM's.  ``w_kernel`` [in, 4C] / ``w_bias`` [4C] act on the input, ``r_kernel`` [C, 4C] / ``r_bias`` [4C] on the state;
+    the gate blocks are column blocks, each of the eight matrices drawn with the orthogonal initialiser on its own, the biases
+    zero.  Padded positions are steps like any other.  ``forward(x)``: x [B,T,in] -> h [B,T,C] on csrc/k_lstm.hip,
+    one kernel family at every width."""
+
+    def __init__(self, num_units, in_units=None, gen=None):
+        super().__init__()
+        if num_units % 16 or not 16 <= num_units <= 512:
+            raise ValueError(f"LSTM: num_units={num_units} unsupported; the HIP recurrence takes a multiple of 16 in [16, 512]")
+        in_units = num_units if in_units is None else in_units
+        self.num_units = num_units
+        self.w_kernel = nn.Parameter(torch.cat([orthogonal_(torch.empty(in_units, num_units), gen) for _ in range(4)], dim=1))
+        self.w_bias = nn.Parameter(torch.zeros(4 * num_units))
+        self.r_kernel = nn.Parameter(torch.cat([orthogonal_(torch.empty(num_units, num_units), gen) for _ in range(4)], dim=1))
+        self.r_bias = nn.Parameter(torch.zeros(4 * num_units))
+        self.compute = lambda p: p  # replaced by the owning model (bf16 shadow lookup)
+
+    def forward(self, x):
+        xp = ops.LinearFn.apply(x, self.w_kernel, self.w_bias, self.compute(self.w_kernel), False)
+        return ops.LstmSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel))
+
+
 def truncated_normal_(t: torch.Tensor, gen: torch.Generator, std: float = 0.02) -> torch.Tensor:
     """tf.truncated_normal_initializer(stddev=std): N(0, std), a value beyond two standard deviations is drawn again."""
     v = torch.randn(t.shape, generator=gen)

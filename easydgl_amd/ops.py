@@ -1854,6 +1854,53 @@ class GruSeqFn(torch.autograd.Function):
         return d_xp, both[:C * N].view(C, N), both[C * N:], None, None
 
 
+class LstmSeqFn(torch.autograd.Function):
+    """The LSTM recurrence over xp = x W + b_W (edgl_lstm_seq_fwd / bwd): h [B,T,C] from xp [B,T,4C], R [C,4C] (r_c: its
+    compute copy), b_R [4C].  Gate order i | f | g | o, cuDNN's form, zero initial h and c.  The backward carries dh and dc in f32
+    through the recurrence and returns d_xp, which is the gradient of h R + b_R too (both biases enter linearly); dR = H_prev^T d_xp
+    and db_R are one dense_grads call over the B*T rows.  No atomics anywhere: the same bits in every call, so FLAGS.deterministic
+    needs no second form."""
+
+    @staticmethod
+    def forward(ctx, xp, r_master, r_bias, r_c):
+        B, T, C4 = xp.shape
+        C = C4 // 4
+        xp = xp.contiguous()
+        code = _code(xp)
+        if r_c.dtype != xp.dtype or tuple(r_c.shape) != (C, C4) or tuple(r_bias.shape) != (C4,) or r_bias.dtype != torch.float32:
+            raise _lib.EdglError(f"LstmSeqFn: R must be {xp.dtype} [{C}, {C4}] and b_R f32 [{C4}] (got {r_c.dtype} {tuple(r_c.shape)}, "
+                                 f"{r_bias.dtype} {tuple(r_bias.shape)})")
+        nbytes = int(lib.edgl_lstm_seq_pack_bytes(C, code))
+        if nbytes <= 0:
+            raise _lib.EdglError(f"LstmSeqFn: width C={C} unsupported (a multiple of 16 in [16, 512])")
+        pack = torch.empty(nbytes, device=xp.device, dtype=torch.uint8)
+        h = torch.empty((B, T, C), device=xp.device, dtype=xp.dtype)
+        need = any(ctx.needs_input_grad)
+        saved = torch.empty((B, T, 5 * C), device=xp.device, dtype=torch.float32) if need else None
+        hprev = torch.empty((B, T, C), device=xp.device, dtype=xp.dtype) if need else None       # the A operand of dR
+        check(lib.edgl_lstm_seq_fwd(_ptr(xp), _ptr(r_c), _ptr(r_bias), B, T, C, _ptr(h), _ptr(saved), _ptr(hprev), _ptr(pack), code,
+                                    _stream()), "edgl_lstm_seq_fwd")
+        ctx.save_for_backward(r_c, saved, hprev)
+        ctx.meta = (B, T, C, code, nbytes)
+        return h
+
+    @staticmethod
+    def backward(ctx, d_h):
+        r_c, saved, hprev = ctx.saved_tensors
+        B, T, C, code, nbytes = ctx.meta
+        d_h = d_h.contiguous()
+        d_xp = torch.empty((B, T, 4 * C), device=d_h.device, dtype=d_h.dtype)
+        pack = torch.empty(nbytes, device=d_h.device, dtype=torch.uint8)
+        check(lib.edgl_lstm_seq_bwd(_ptr(d_h), _ptr(r_c), _ptr(saved), B, T, C, _ptr(d_xp), _ptr(pack), code, _stream()),
+              "edgl_lstm_seq_bwd")
+        M, N = B * T, 4 * C
+        both = torch.empty((C + 1) * N, device=d_h.device, dtype=torch.float32)
+        ws = torch.empty(lib.edgl_gemm_dw_workspace(M, C, N, code), device=d_h.device, dtype=torch.float32)
+        check(lib.edgl_gemm_dw(_ptr(hprev), _ptr(d_xp), _ptr(both), both.data_ptr() + 4 * C * N, M, C, N, C, N, 0, _ptr(ws), code,
+                               _stream()), "edgl_gemm_dw")
+        return d_xp, both[:C * N].view(C, N), both[C * N:], None
+
+
 class CatPosMaskFn(torch.autograd.Function):
     """[h | pos[0..T)] * (ids != 0) (S2PNM.py:52-53; PositionCoding concatenates): edgl_cat_pos_mask_fwd / bwd.  d_pos is summed over
     b in a fixed order, without atomics."""

@@ -61,6 +61,8 @@ def args(argv=None):
     p.add_argument("--hidden_dropout_rate", type=float, default=0.0)
     p.add_argument("--attention_probs_dropout_rate", type=float, default=0.0)
     p.add_argument("--eval_per_steps", type=int, default=1)
+    p.add_argument("--rnn_cell", choices=("gru", "lstm"), default="gru",
+                   help="GRU4REC: the cell of its recurrent layers; lstm is the cuDNN-form LSTM on csrc/k_lstm.hip (DESIGN 4.25)")
     p.add_argument("--mask_seen", action="store_true")
     # build-specific
     p.add_argument("--dtype", choices=["bf16", "f32"], default="bf16", help="activation dtype of the HIP kernels")
@@ -337,6 +339,8 @@ def run(FLAGS) -> Dict[str, float]:
             if getattr(FLAGS, flag, False):
                 raise ValueError(f"--{flag} with --model GRU4REC: not supported; every batch comes from the host and goes through "
                                  "model.train_step")
+    if getattr(FLAGS, "rnn_cell", "gru") != "gru" and FLAGS.model != "GRU4REC":
+        raise ValueError(f"--rnn_cell {FLAGS.rnn_cell} with --model {FLAGS.model}: not supported; only GRU4REC has recurrent layers to switch")
     logging.info("1. read data")
     tr_i, tr_t = F.load_sequences(FLAGS.train, FLAGS.seqslen)
     vl_i, vl_t = F.load_sequences(FLAGS.valid, FLAGS.seqslen)

@@ -1201,6 +1201,24 @@ int edgl_gru_wide_fwd(const void* xp, const void* R, const float* b_R, int B, in
                       void* hprev_c, void* pack, int dtype, void* stream);
 int edgl_gru_wide_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* d_gh,
                       void* pack, int dtype, void* stream);
+/* One unidirectional LSTM layer in cuDNN's form (k_lstm.hip): gate order i, f, g, o as column blocks, linear input,
+ * zero initial h and c, no forget-gate offset, no projection, no peepholes; every position is a step:
+ *   a = xp + h R + b_R   i, f, o = s(a_i), s(a_f), s(a_o)   g = tanh(a_g)   c' = f c + i g   h' = o tanh(c')
+ * xp [B,T,4C] `dtype` = x W + b_W (a plain edgl_gemm), R [C,4C] `dtype`, b_R f32 [4C].
+ * edgl_lstm_seq_fwd: h [B,T,C] `dtype`; saved f32 [B,T,5C] = i | f | g | o (post-activation) | c' per position and hprev_c
+ * [B,T,C] `dtype` = the state h BEFORE each step (the A operand of dR) — both may be NULL: evaluation writes nothing.
+ * edgl_lstm_seq_bwd: d_h [B,T,C] -> d_xp [B,T,4C], the gradient of the pre-activations: of xp and of h R + b_R alike (both
+ * biases enter linearly, so there is no d_gh); dh and dc are carried in f32; dR = H_prev^T d_xp and db_R = colsum(d_xp) are ONE
+ * edgl_gemm_dw over the B*T rows afterwards.  `pack`: edgl_lstm_seq_pack_bytes(C, dtype) bytes (-1 for a bad C / dtype), 16-byte
+ * aligned, written by the call (R as MFMA fragments, read as a per-wave stream through a register ring as in edgl_gru_wide_*).
+ * One workgroup owns 16 samples for all T steps; c and the carried dc never leave the registers of the lane that owns them; no
+ * atomics, no waiting between workgroups: the same bits in every call.  C a multiple of 16 in [16, 512], B >= 1, T >= 1;
+ * anything else is EDGL_ERR_SHAPE / _DTYPE / _NULL before a launch. */
+long edgl_lstm_seq_pack_bytes(int C, int dtype);
+int edgl_lstm_seq_fwd(const void* xp, const void* R, const float* b_R, int B, int T, int C, void* h, float* saved,
+                      void* hprev_c, void* pack, int dtype, void* stream);
+int edgl_lstm_seq_bwd(const void* d_h, const void* R, const float* saved, int B, int T, int C, void* d_xp, void* pack, int dtype,
+                      void* stream);
 
 /* ---- S2PNM's element-wise pieces (S2PNM.py:52-66) and gradient clipping (k_s2pnm.hip) -----------------
  * edgl_cat_pos_mask_fwd: out [B,T,2C] = [h[b,t] | pos[t]] * (ids[b,t] != 0); h `dtype` [B,T,C], pos f32 [>=T, C].

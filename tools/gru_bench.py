@@ -13,8 +13,12 @@
     in the same device-event windows; forward microseconds per step against the L2 bound; whether h and the three gradients of
     the two paths are bit-identical; and one GRU4REC train_step (T = 30, 17 771 items, 1 block) beside S2PNM's.
 
+  * --cell lstm (profiles/lstm_seq.txt): module.sequential.LSTM as a layer (input GEMM, csrc/k_lstm.hip, dR GEMM) beside
+    torch.nn.LSTM at the --wide shapes, alternating repeat by repeat, forward alone and forward plus backward; the recurrence's
+    forward microseconds per step against its L2 bound (4 C^2 elements per step); one GRU4REC train_step with each cell.
+
 Warm-up, device events around `iters` calls, `reps` repeats, median and min / max printed.
-    python tools/gru_bench.py [--iters 10] [--reps 5] [--json out.json] [--skip-models] [--wide]"""
+    python tools/gru_bench.py [--iters 10] [--reps 5] [--json out.json] [--skip-models] [--wide] [--cell lstm]"""
 import argparse
 import json
 import os
@@ -28,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from easydgl_amd import data as D  # noqa: E402
 from easydgl_amd import ops  # noqa: E402
-from easydgl_amd.module.sequential import GRU  # noqa: E402
+from easydgl_amd.module.sequential import GRU, LSTM  # noqa: E402
 from easydgl_amd.util import ranking  # noqa: E402
 
 B = 512
@@ -111,6 +115,76 @@ def wide_rows(a, dev, out):
         print(f"{name:9s} train_step B={B} T=30 C=512 H={heads} blocks={blocks} bf16: {fmt(r)}", flush=True)
 
 
+def lstm_layer(T, C, dt, dev):
+    """module.sequential.LSTM as a layer, x -> h (the input GEMM, csrc/k_lstm.hip, the dR GEMM), and the recurrence alone."""
+    m = LSTM(C, C, gen=torch.Generator().manual_seed(0)).to(dev)
+    m.compute = lambda p: p.detach().to(dt)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    x = torch.randn((B, T, C), device=dev, generator=gen).to(dt).requires_grad_(True)
+    xp = torch.randn((B, T, 4 * C), device=dev, generator=gen).to(dt)
+    d_h = torch.randn((B, T, C), device=dev, generator=gen).to(dt)
+    Rc = m.r_kernel.detach().to(dt)
+
+    def both():
+        m(x).backward(d_h)
+        x.grad = None
+        m.zero_grad(set_to_none=True)
+
+    def fwd():
+        with torch.no_grad():
+            m(x)
+
+    def rec():
+        with torch.no_grad():
+            ops.LstmSeqFn.apply(xp, m.r_kernel, m.r_bias, Rc)
+    return both, fwd, rec
+
+
+def vendor_lstm(T, C, dt, dev):
+    g = torch.nn.LSTM(C, C, batch_first=True).to(dev).to(dt)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    x = torch.randn((B, T, C), device=dev, generator=gen).to(dt).requires_grad_(True)
+    d_h = torch.randn((B, T, C), device=dev, generator=gen).to(dt)
+
+    def both():
+        g(x)[0].backward(d_h)
+        x.grad = None
+        g.zero_grad(set_to_none=True)
+
+    def fwd():
+        with torch.no_grad():
+            g(x)
+    return both, fwd
+
+
+def lstm_rows(a, dev, out):
+    """--cell lstm (profiles/lstm_seq.txt): the LSTM layer beside torch.nn.LSTM, alternating repeat by repeat."""
+    fmt = lambda r: f"{r['median_ms']:8.3f} ms ({r['min_ms']:.3f} - {r['max_ms']:.3f})"
+    for T in (30, 100):
+        for C in (256, 512):
+            for dt, nm in ((torch.float32, "f32"), (torch.bfloat16, "bf16")):
+                both, fwd, rec = lstm_layer(T, C, dt, dev)
+                l2_us = 4.0 * C * C * (4 if nm == "f32" else 2) / L2_BYTES_PER_CLK_CU / CLOCK_HZ * 1e6
+                row = dict(T=T, C=C, dtype=nm, l2_us=l2_us, vendor_error=None)
+                try:
+                    vboth, vfwd = vendor_lstm(T, C, dt, dev)
+                    row["fwd_bwd"], row["vendor_fwd_bwd"] = spread_pair(both, vboth, a.iters, a.reps)
+                    row["fwd"], row["vendor_fwd"] = spread_pair(fwd, vfwd, a.iters, a.reps)
+                except Exception as e:       # (the vendor RNN does not run at this dtype / on this box: said, not hidden)
+                    row["vendor_error"] = f"{type(e).__name__}: {str(e)[:200]}"
+                    row["fwd_bwd"], row["fwd"] = spread(both, a.iters, a.reps), spread(fwd, a.iters, a.reps)
+                row["rec_fwd"] = spread(rec, a.iters, a.reps)
+                out["lstm"].append(row)
+                v = (f"torch.nn.LSTM fwd+bwd {fmt(row['vendor_fwd_bwd'])} fwd {fmt(row['vendor_fwd'])}" if row["vendor_error"] is None
+                     else f"torch.nn.LSTM did not run: {row['vendor_error']}")
+                print(f"LSTM B={B} T={T:3d} C={C:3d} {nm:4s}: layer fwd+bwd {fmt(row['fwd_bwd'])} fwd {fmt(row['fwd'])}; {v}; recurrence fwd per "
+                      f"step {row['rec_fwd']['median_ms'] / T * 1e3:6.2f} us >= {l2_us:.2f} us L2", flush=True)
+    for cell in ("gru", "lstm"):
+        r = spread(model_step("GRU4REC", 1, 1, dev, rnn_cell=cell), a.iters, a.reps)
+        out["models"]["GRU4REC " + cell] = r
+        print(f"GRU4REC --rnn_cell {cell:4s} train_step B={B} T=30 C=512 blocks=1 bf16: {fmt(r)}", flush=True)
+
+
 def vendor_gru(T, C, dt, dev):
     g = torch.nn.GRU(C, C, batch_first=True).to(dev).to(dt)
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -131,12 +205,12 @@ def lower_bounds(C, elem):
     return dict(mfma_us=flop / MFMA_BF16_FLOP_PER_CLK_CU / CLOCK_HZ * 1e6, l2_us=3.0 * C * C * elem / L2_BYTES_PER_CLK_CU / CLOCK_HZ * 1e6)
 
 
-def model_step(name, heads, blocks, dev):
+def model_step(name, heads, blocks, dev, **extra):
     I, T, C = 17771, 30, 512
     drop = 0.2 if name == "S2PNM" else (0.0 if name == "SASREC" else 0.1)
     F = SimpleNamespace(model=name, num_items=I, num_units=C, num_heads=heads, num_blocks=blocks, seqslen=T, timelen=256,
                         time_scale=86400.0, learning_rate=1e-4, l2_reg=1e-4, hidden_dropout_rate=drop,
-                        attention_probs_dropout_rate=drop, compute_dtype="bf16", num_train_steps=None, num_warmup_steps=None, seed=9876)
+                        attention_probs_dropout_rate=drop, compute_dtype="bf16", num_train_steps=None, num_warmup_steps=None, seed=9876, **extra)
     m = ranking(F).finalize(dev)
     batches = []
     for k in range(4):
@@ -160,12 +234,14 @@ def main():
     ap.add_argument("--vendor", choices=["on", "off", "only"], default="on",
                     help="torch.nn.GRU beside the op: on, off, or only (the vendor RNN alone, e.g. in a process of its own)")
     ap.add_argument("--wide", action="store_true", help="the pipelined stream beside the existing path (DESIGN 4.23), and nothing else")
+    ap.add_argument("--cell", choices=["gru", "lstm"], default="gru",
+                    help="lstm: the LSTM layer (DESIGN 4.25) beside torch.nn.LSTM and GRU4REC's train_step with each cell, and nothing else")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda", 0)
-    out = {"batch": B, "iters": a.iters, "reps": a.reps, "gru": [], "wide": [], "models": {}}
-    if a.wide:
-        wide_rows(a, dev, out)
+    out = {"batch": B, "iters": a.iters, "reps": a.reps, "gru": [], "wide": [], "lstm": [], "models": {}}
+    if a.wide or a.cell == "lstm":
+        (lstm_rows if a.cell == "lstm" else wide_rows)(a, dev, out)
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(out, f, indent=1)
