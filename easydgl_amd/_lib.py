@@ -199,6 +199,9 @@ SIGNATURES = {
     "edgl_battn_saved_bytes": (L, [I, I, I]),
     "edgl_battn_fwd": (I, [P, P, I, I, I, I, F, F, P, U32, P, P, I, P]),
     "edgl_battn_bwd": (I, [P, P, P, P, P, I, I, I, I, F, F, P, U32, P, I, P]),
+    "edgl_addattn_bwd_workspace": (L, [I, I, I]),
+    "edgl_addattn_fwd": (I, [P, P, P, P, I, I, I, P, I, P, I, P]),
+    "edgl_addattn_bwd": (I, [P, P, P, P, P, I, P, I, I, I, P, P, P, P, I, P]),
     "edgl_gelu_tanh_fwd": (I, [P, P, L, I, P]),
     "edgl_gelu_tanh_bwd": (I, [P, P, P, L, I, P]),
     "edgl_gather_relu_fwd": (I, [P, P, P, I, I, I, I, I, P]),

@@ -2,7 +2,8 @@
 kernel in its plain-head form (Dq == Dv, csrc/k_tattn.hip), and the GRU layer S2PNM puts in front of it (the reference's
 compat/cudnn_rnn.py CudnnGRU) on the recurrence kernel csrc/k_gru.hip; TimelyREC's MATEncoder and TAHEncoder on csrc/k_mate.hip
 and csrc/k_tahe.hip; GREC's MaskedCNN (two dilated convolutions, each with LayerNorm and ReLU, and a residual) on csrc/k_dconv.hip;
-BERT4REC's BERTAttention (bidirectional, key mask only, no residual) on csrc/k_battn.hip."""
+BERT4REC's BERTAttention (bidirectional, key mask only, no residual) on csrc/k_battn.hip.  Not in the reference: the LSTM form of
+the GRU layer (csrc/k_lstm.hip) and NARM's AdditiveAttention over the GRU states (csrc/k_addattn.hip)."""
 from __future__ import annotations
 
 import torch
@@ -140,6 +141,28 @@ class LSTM(nn.Module):
     def forward(self, x):
         xp = ops.LinearFn.apply(x, self.w_kernel, self.w_bias, self.compute(self.w_kernel), False)
         return ops.LstmSeqFn.apply(xp, self.r_kernel, self.r_bias, self.compute(self.r_kernel))
+
+
+class AdditiveAttention(nn.Module):
+    """The attention of NARM (Li et al., CIKM'17, eq. 7-8) over the states of a recurrent encoder, every position a query:
+    alpha[t,j] = v^T sigmoid(A1 h[t] + A2 h[j]) for the keys j <= t with ids[j] != 0, c[t] = sum_j alpha[t,j] h[j]; no softmax,
+    as in the paper.  ``a_kernel`` [C, 2C] holds A1 | A2 as column blocks (each glorot uniform, no bias: both read the same
+    input, one GEMM), ``v`` [C] is glorot uniform as a [C, 1] matrix.  ``forward(h, ids, cat=False)``: h [B,T,C] -> c [B,T,C], or
+    [h | c] [B,T,2C] with ``cat`` (csrc/k_addattn.hip)."""
+
+    def __init__(self, num_units, gen=None):
+        super().__init__()
+        if num_units % 16 or not 16 <= num_units <= 512:
+            raise ValueError(f"AdditiveAttention: num_units={num_units} unsupported; the HIP kernels take a multiple of 16 in [16, 512]")
+        self.num_units = num_units
+        self.a_kernel = nn.Parameter(torch.cat([glorot_uniform_(torch.empty(num_units, num_units), gen) for _ in range(2)], dim=1))
+        self.v = nn.Parameter(glorot_uniform_(torch.empty(num_units, 1), gen).reshape(num_units))
+        self.register_buffer("no_bias", torch.zeros(2 * num_units), persistent=False)     # (tf.layers.dense(use_bias=False))
+        self.compute = lambda p: p  # replaced by the owning model (bf16 shadow lookup)
+
+    def forward(self, h, ids, cat=False):
+        a12 = ops.LinearFn.apply(h, self.a_kernel, self.no_bias, self.compute(self.a_kernel), False)
+        return ops.AddAttnFn.apply(h, a12, self.v, ids, cat)
 
 
 def truncated_normal_(t: torch.Tensor, gen: torch.Generator, std: float = 0.02) -> torch.Tensor:

@@ -2418,6 +2418,50 @@ class BertAttnFn(torch.autograd.Function):
         return d_qkv, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------
+# K15: causal additive attention over recurrent states (NARM; csrc/k_addattn.hip)
+# ------------------------------------------------------------------------------------------------
+class AddAttnFn(torch.autograd.Function):
+    """out[t] = sum_j alpha[t,j] h[j] with alpha[t,j] = sum_c v[c] sigmoid(a1[t,c] + a2[j,c]) where j <= t and ids[j] != 0, else 0
+    (edgl_addattn_fwd / bwd): h [B,T,C], a12 [B,T,2C] = a1 | a2, v f32 [C], ids int64 [B,T] -> [B,T,C].  No softmax.  ``cat``: the
+    result is [h | out] [B,T,2C], the concatenation written by the kernels (the backward then adds the left half of the
+    upstream gradient to d_h).  Nothing per pair is saved; the backward recomputes the sigmoids and uses no f32 atomics, so two
+    calls give the same bits."""
+
+    @staticmethod
+    def forward(ctx, h, a12, v, ids, cat=False):
+        B, T, C = h.shape
+        if a12.dtype != h.dtype or tuple(a12.shape) != (B, T, 2 * C) or v.dtype != torch.float32 or tuple(v.shape) != (C,):
+            raise _lib.EdglError(f"AddAttnFn: a12 must be {h.dtype} [{B}, {T}, {2 * C}] and v f32 [{C}] (got {a12.dtype} "
+                                 f"{tuple(a12.shape)}, {v.dtype} {tuple(v.shape)})")
+        if ids.dtype != torch.int64 or tuple(ids.shape) != (B, T) or not ids.is_contiguous():
+            raise _lib.EdglError(f"attention key ids must be a contiguous int64 [B={B}, T={T}] tensor, got {tuple(ids.shape)} {ids.dtype}")
+        code = _code(h)
+        h, a12, v = h.contiguous(), a12.contiguous(), v.contiguous()
+        W = 2 * C if cat else C
+        out = torch.empty((B, T, W), device=h.device, dtype=h.dtype)
+        po = _ptr(out)
+        check(lib.edgl_addattn_fwd(_ptr(h), _ptr(a12), _ptr(v), _ptr(ids), B, T, C, po + (W - C) * out.element_size(), W,
+                                   po if cat else None, code, _stream()), "edgl_addattn_fwd")
+        ctx.save_for_backward(h, a12, v, ids)
+        ctx.meta = (B, T, C, W, code)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        h, a12, v, ids = ctx.saved_tensors
+        B, T, C, W, code = ctx.meta
+        d_out = d_out.contiguous()
+        d_a12, d_h = torch.empty_like(a12), torch.empty_like(h)
+        d_v = torch.empty(C, device=h.device, dtype=torch.float32)
+        ws = torch.empty(int(lib.edgl_addattn_bwd_workspace(B, T, C)), device=h.device, dtype=torch.float32)
+        pd = _ptr(d_out)
+        check(lib.edgl_addattn_bwd(_ptr(h), _ptr(a12), _ptr(v), _ptr(ids), pd + (W - C) * d_out.element_size(), W,
+                                   pd if W != C else None, B, T, C, _ptr(d_a12), _ptr(d_h), _ptr(d_v), _ptr(ws), code, _stream()),
+              "edgl_addattn_bwd")
+        return d_h, d_a12, d_v, None, None
+
+
 class GeluTanhFn(torch.autograd.Function):
     """The tanh form of GELU (GREC.py:14-26) as an op of its own behind a dense layer."""
 

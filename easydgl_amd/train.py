@@ -1,7 +1,7 @@
 """Train / evaluate driver — the role of the reference's ``src/main.py:78-151`` with ``util.EarlyStopping``
 (``src/util.py:14-58``), on the HIP model.
 
-Models: EasyDGL and BERT4REC (masked batches, ``MAUPostProcessor``), GREC (host-side masked batches, ``GRECPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC / GRU4REC (regressive batches,
+Models: EasyDGL and BERT4REC (masked batches, ``MAUPostProcessor``), GREC (host-side masked batches, ``GRECPostProcessor``) and CTSMA / TGAT / TiSASREC / SASREC / S2PNM / TGREC / GRU4REC / NARM (regressive batches,
 ``RegressivePostProcessor``), chosen as ``util.reader`` does (``util.py:99-129``); TimelyREC is fed regressively with the four
 calendar fields of its records (``has_datetime=True``), derived from ``seqs_t`` where the files lack them.
 Same flags as ``main.py:22-75`` for everything these paths read (``--train/--valid/--test`` file patterns,
@@ -35,7 +35,7 @@ def args(argv=None):
     p.add_argument("--train", required=True, help="training data file patterns (.tfrec or .npz)")
     p.add_argument("--valid", required=True)
     p.add_argument("--test", required=True)
-    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC, TGREC, GREC, BERT4REC or GRU4REC (util.ranking keys)")
+    p.add_argument("--model", required=True, help="algorithm name: EasyDGL, CTSMA, TGAT, TiSASREC, SASREC, S2PNM, TimelyREC, TGREC, GREC, BERT4REC, GRU4REC or NARM (util.ranking keys)")
     p.add_argument("--num_items", type=int, required=True)
     # reference default: 50 (main.py:35) — head dim 50 with the default single head: every model runs it zero-padded at head dim 64
     # (model/base.py, model/easydgl.py: exact, the padded channels stay zero); every published recipe passes --num_units=512
@@ -338,6 +338,11 @@ def run(FLAGS) -> Dict[str, float]:
         for flag in ("device_data", "graph", "lazy_adam"):
             if getattr(FLAGS, flag, False):
                 raise ValueError(f"--{flag} with --model GRU4REC: not supported; every batch comes from the host and goes through "
+                                 "model.train_step")
+    if FLAGS.model == "NARM":         # as GRU4REC (model/narm.py: Not built)
+        for flag in ("device_data", "graph", "lazy_adam"):
+            if getattr(FLAGS, flag, False):
+                raise ValueError(f"--{flag} with --model NARM: not supported; every batch comes from the host and goes through "
                                  "model.train_step")
     if getattr(FLAGS, "rnn_cell", "gru") != "gru" and FLAGS.model != "GRU4REC":
         raise ValueError(f"--rnn_cell {FLAGS.rnn_cell} with --model {FLAGS.model}: not supported; only GRU4REC has recurrent layers to switch")

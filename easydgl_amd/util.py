@@ -39,4 +39,7 @@ def ranking(FLAGS):
     if FLAGS.model == "GRU4REC" and hasattr(FLAGS, "num_items"):      # (as GREC: the bare namespace keeps its refusal)
         from .model import GRU4REC
         return GRU4REC(FLAGS.num_items, FLAGS)
+    if FLAGS.model == "NARM" and hasattr(FLAGS, "num_items"):         # (not a reference model; guarded like its neighbours)
+        from .model import NARM
+        return NARM(FLAGS.num_items, FLAGS)
     raise NotImplementedError("The ranking model: {0} not implemented".format(FLAGS.model))

@@ -1030,6 +1030,24 @@ int edgl_battn_fwd(const void* qkv, const int64_t* ids, int B, int T, int H, int
 int edgl_battn_bwd(const void* qkv, const int64_t* ids, const void* out, const void* d_out, void* saved, int B, int T, int H,
                    int C, float scale, float drop_rate, const uint64_t* rng_state, uint32_t stream_id, void* d_qkv, int dtype,
                    void* stream);
+/* ---- K15: causal additive attention over recurrent states (NARM; csrc/k_addattn.hip) ------------------------
+ * h [B,T,C] and a12 [B,T,2C] = a1 | a2 (`dtype`, contiguous), v f32 [C], ids int64 [B,T]:
+ *   e[t,j] = sum_c v[c] sigmoid(a1[t,c] + a2[j,c]);  alpha[t,j] = e[t,j] if j <= t and ids[j] != 0 else 0;  out[t] = sum_j alpha[t,j] h[j]
+ * No softmax; the diagonal is kept; a query whose own id is 0 is computed; a sample without a real key gives zeros.
+ * edgl_addattn_fwd: out rows [B*T] of C channels with the row stride ld_out (`dtype`).  h_copy (may be NULL): the rows of h are
+ * copied there with the same stride — out = h_copy + C over one [B,T,2C] buffer gives the concatenation h | out.  Nothing is saved.
+ * edgl_addattn_bwd: d_out rows with the row stride ld_dout -> d_a12 [B,T,2C] and d_h [B,T,C] (`dtype`, every element written;
+ * d_h = sum_t alpha[t,j] d_out[t], plus the rows of d_res (same stride; may be NULL), i.e. whatever else reaches h) and d_v f32 [C].
+ * The sigmoids are recomputed.  workspace: edgl_addattn_bwd_workspace(B, T, C) floats (-1: shape not taken), one partial row of
+ * d_v per workgroup, summed by a finishing launch in a fixed order.  No f32 atomics and one writer per address: two calls on
+ * equal inputs give equal bits.  C a multiple of 16 in [16, 512], 1 <= T <= 1024, B >= 1, B*T*T < 2^32, row strides multiples
+ * of 4 and >= C; anything else is EDGL_ERR_SHAPE / _DTYPE / _NULL with the bound in the text, before any launch. */
+long edgl_addattn_bwd_workspace(int B, int T, int C);
+int edgl_addattn_fwd(const void* h, const void* a12, const float* v, const int64_t* ids, int B, int T, int C, void* out, int ld_out,
+                     void* h_copy, int dtype, void* stream);
+int edgl_addattn_bwd(const void* h, const void* a12, const float* v, const int64_t* ids, const void* d_out, int ld_dout,
+                     const void* d_res, int B, int T, int C, void* d_a12, void* d_h, float* d_v, float* workspace, int dtype,
+                     void* stream);
 /* y = x * (ids != 0) per row: `seqs_outs *= seqs_masks` (TGAT.py:58,70; TiSASREC.py:73); its own backward. */
 int edgl_mask_rows(const void* x, const int64_t* ids, void* y, long rows, int C, int dtype, void* stream);
 
